@@ -7,7 +7,13 @@ One "step" = one full render() forward + backward to the 3x4 camera pose over on
 are sharded across ranks (strong scaling) and the only collective is the 48-byte pose-gradient
 all-reduce.  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds per timed step).  --full adds everything else the bench measures: per-kernel times (HIP events around every
+launch of the timed steps) and the roofline built on them, the sustained matrix-core clock, the committed HBM traffic, the CPU oracle
+baseline, the multi-GPU diagnostics; the secondary workloads' extras (`train`: kernel times and the CPU leg) likewise.
+--dump-outputs DIR writes what the last timed step computed (the maps render() returns, the loss, the pose gradient) as DIR/<name>.npy.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -268,10 +274,11 @@ def refinement_loop(dev, iters=50, graph=True, images=1, mode="upsampled", strea
     return sec, iters * (H // ts) * (W // ts), err
 
 
-def train_steps(dev, steps=10, warmup=2):
+def train_steps(dev, steps=10, warmup=2, full=True):
     """BASELINE configs[0] on the HIP path: stage-1 colour-only training step of script/run_nefes.py:42-108 --
     200x200 crop (40 000 rays), 64 coarse samples, N_importance=0, reference-default net (8x128, C=128), stratified
-    jitter, img2mse loss, backward to the NeRF weights, Adam step.  Returns (seconds per step, rays per step, kernel ms)."""
+    jitter, img2mse loss, backward to the NeRF weights, Adam step.  Returns (seconds per step, rays per step, kernel ms, first / last
+    loss, CPU leg); kernel ms and the CPU leg only with `full` (None otherwise)."""
     from nefes_amd import ops
     from nefes_amd.field import NeRFH_NFF
     from nefes_amd.render import render
@@ -298,13 +305,15 @@ def train_steps(dev, steps=10, warmup=2):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    ops.TIMERS = {}
+    ops.TIMERS = {} if full else None
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     timers, ops.TIMERS = ops.TIMERS, None
+    if not full:
+        return dt, H * W, None, [float(l) for l in (losses[0], losses[-1])], None
     kern = {k: round(sum(s.elapsed_time(e) for s, e in v) / len(v), 4) for k, v in timers.items()}
     # CPU oracle on a bounded slice of the same step (reference settings: netchunk=1024 slices, autograd to the weights)
     from oracle import ref_cpu as O
@@ -421,6 +430,25 @@ def hbm_kernel_lines(kern, rays, Nc, Ni, Wd, C):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor as out_dir/<name>.npy in float32.  Past DUMP_LIMIT_BYTES in all, every array of more than 1 MB keeps
+    the same fixed, seeded, sorted sample of its rows (the fraction that brings the total under the limit), so two runs stay comparable."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    big = {k for k, v in arrays.items() if v.nbytes > 1 << 20}
+    small = sum(v.nbytes for k, v in arrays.items() if k not in big)
+    frac = min(1.0, 0.99 * (DUMP_LIMIT_BYTES - small) / max(sum(arrays[k].nbytes for k in big), 1))
+    for name, v in arrays.items():
+        if frac < 1.0 and name in big:
+            keep = max(1, int(v.shape[0] * frac))
+            v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -428,12 +456,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--height", type=int, default=0, help="override the workload's frame height (debugging)")
     ap.add_argument("--width", type=int, default=0, help="override the workload's frame width (debugging)")
-    ap.add_argument("--cpu-rows", type=int, default=12, help="rows of the frame timed on the host cores (0 = skip)")
+    ap.add_argument("--cpu-rows", type=int, default=12, help="with --full: rows of the frame timed on the host cores (0 = skip)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["loop50", "train"], default="metric")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times + roofline, sustained MFMA clock, committed "
+                         "traffic, CPU baseline, multi-GPU diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     a = ap.parse_args()
 
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.workload in ("loop50", "train"):
+        raise SystemExit(f"bench.py: --dump-outputs is for the per-step workloads ({', '.join(sorted(WORKLOADS))}), not '{a.workload}'")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # Not started by a launcher: start the N ranks ourselves (one process per GPU) and relay rank 0's JSON line.
         # This parent makes no GPU call (torch.cuda.device_count() does not initialise the runtime on this image).
@@ -476,16 +513,18 @@ def main():
     from nefes_amd.render import render
 
     if a.workload == "train":
-        sec, rays, kern, ls, cpu = train_steps(dev)
+        sec, rays, kern, ls, cpu = train_steps(dev, full=a.full)
         # weight-gradient training step: forward + dX + dW = 3 x the forward MACs of the static coarse net
         flop = 3 * 2 * (130944 + 128 * 128 + (128 + 27) * 64 + 64 * 131) * rays * 64
-        print(json.dumps({"metric": "rays/s (training step), secondary workload 'train'", "value": rays / sec, "unit": "rays/s",
-                          "n_gpus": 1, "higher_is_better": True, "dtype": "f32", "data": "synthetic", "vs_baseline": None,
-                          "ms_per_step": sec * 1e3, "kernels_ms": kern, "loss_first_last": ls,
-                          "algorithmic_tflops": flop / sec / 1e12, "cpu_baseline": cpu,
-                          "config": {"workload": "BASELINE configs[0] on the HIP path: stage-1 colour-only training step, 200x200 "
-                                                 "crop, 64 coarse samples, N_importance=0, 8x128 net with 128-ch feature head, "
-                                                 "perturb=1, img2mse, backward to weights, Adam"}}), flush=True)
+        out = {"metric": "rays/s (training step), secondary workload 'train'", "value": rays / sec, "unit": "rays/s",
+               "n_gpus": 1, "higher_is_better": True, "dtype": "f32", "data": "synthetic", "vs_baseline": None,
+               "ms_per_step": sec * 1e3, "loss_first_last": ls, "algorithmic_tflops": flop / sec / 1e12,
+               "config": {"workload": "BASELINE configs[0] on the HIP path: stage-1 colour-only training step, 200x200 "
+                                      "crop, 64 coarse samples, N_importance=0, 8x128 net with 128-ch feature head, "
+                                      "perturb=1, img2mse, backward to weights, Adam"}}
+        if a.full:
+            out["kernels_ms"], out["cpu_baseline"] = kern, cpu
+        print(json.dumps(out), flush=True)
         return
     if a.workload == "loop50":
         sec_e, rays, _ = refinement_loop(dev, graph=False)
@@ -539,12 +578,16 @@ def main():
     row0, nrows = D.row_shard(H, rank, world)
     n_total = H * W
 
-    def step():
+    last = {}
+
+    def step(keep=False):
         c2w = pose.clone().requires_grad_()
         rgb, disp, acc, ex = render(H, W, focal, c2w=D.replicate_pose(c2w), near=near, far=far, row_range=(row0, nrows), **kw)
         feat = ex["feat_map"]
         loss = (feat ** 2).sum() / (n_total * C) + (rgb ** 2).sum() / (n_total * 3)   # = mean over the full frame
         loss.backward()                                                               # pose all-reduce happens here
+        if keep:                                                                      # --dump-outputs: what a caller receives
+            last.update(rgb_map=rgb, disp_map=disp, acc_map=acc, feat_map=feat, loss=loss)
         return c2w.grad
 
     def barrier():
@@ -555,13 +598,13 @@ def main():
     for _ in range(a.warmup):
         step()
     barrier()
-    ops.TIMERS = {}
-    D.ALLREDUCE_TIMES = [] if grouped else None
+    ops.TIMERS = {} if a.full else None
+    D.ALLREDUCE_TIMES = [] if grouped and a.full else None
     t0 = time.perf_counter()
     trace = os.environ.get("NEFES_BENCH_TRACE", "0") == "1"           # debugging: host time of every step (adds a sync per step)
-    for _ in range(a.steps):
+    for i in range(a.steps):
         ts = time.perf_counter()
-        g = step()
+        g = step(keep=bool(a.dump_outputs) and i == a.steps - 1)
         if trace:
             if os.environ.get("NEFES_BENCH_TRACE_SYNC", "1") == "1":
                 torch.cuda.synchronize()
@@ -582,11 +625,11 @@ def main():
         rank_ms = [float(t.item()) / a.steps * 1e3 for t in every]
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-        multi = multi_gpu_diagnostics(dist, dev, world, rank, ar_times, a)
+        multi = multi_gpu_diagnostics(dist, dev, world, rank, ar_times, a) if a.full else None
 
-    if rank == 0:
-        ms_step = dt / a.steps * 1e3
-        value = n_total * a.steps / dt
+    def full_fields(value):
+        """--full: per-kernel times of the timed steps and the roofline built on them, the committed HBM traffic and the sustained
+        matrix-core clock (a probe run of its own after the timed region).  Returns the keys it adds to the line."""
         kern = {k: sum(s.elapsed_time(e) for s, e in v) / len(v) for k, v in timers.items()}   # ms per launch, rank 0
         rays_local = nrows * W
         # Dominant kernel = the longest-running launch of the step.  Fine-field forward (FULL mode) and backward-to-inputs
@@ -620,22 +663,14 @@ def main():
         if (a.workload, H, W, world) == ("metric", 480, 640, 1):
             traffic, traffic_source = committed_traffic(dom_key == bwd_key, h3, x6)
         out = {
-            "metric": "rays/s (fwd+bwd) at 640x480x(64+128) samples, 8x256 MLP" if a.workload == "metric"
-                      else f"rays/s (fwd+bwd), secondary workload '{a.workload}'", "value": value, "unit": "rays/s",
-            "n_gpus": world, "world_size": dist.get_world_size() if grouped else 1,
-            "collective_backend": (dist.get_backend() if grouped else None), "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
             "matrix_core_arithmetic": "fp16 two-part split (3 products)" if h3 else ("bf16x6" if x6 else "fp32 MFMA"),
-            "data": "synthetic",
-            "config": {"workload": f"{wl['name']}; {W}x{H}, random seed-0 weights, fwd + bwd to the 3x4 pose",
-                       "rays_per_step": n_total, "samples_per_ray": [Nc, Ni], "parallelism": f"rows/{world}",
-                       "arithmetic": ("fp32 in, fp32 out; matrix products as fp16 two-part split products (hi, lo fp16 pairs of power-of-two "
-                                      "scaled operands, 22 significant bits, three cross terms, fp32 accumulation: fp32-level accuracy, "
-                                      "tests/test_gpu_h3.py); NEFES_SPLIT=x6 / f32 select the bf16x6 / fp32-MFMA kernels"
-                                      if h3 else
-                                      "fp32 in, fp32 out; matrix products as exact bf16x6 split products with fp32 accumulation "
-                                      "(fp32-level accuracy, tests/test_gpu_x6.py); NEFES_X6=0 selects the fp32-MFMA kernels"
-                                      if any(k.endswith("x6]") for k in kern) else "fp32 MFMA")},
+            "arithmetic": ("fp32 in, fp32 out; matrix products as fp16 two-part split products (hi, lo fp16 pairs of power-of-two "
+                           "scaled operands, 22 significant bits, three cross terms, fp32 accumulation: fp32-level accuracy, "
+                           "tests/test_gpu_h3.py); NEFES_SPLIT=x6 / f32 select the bf16x6 / fp32-MFMA kernels"
+                           if h3 else
+                           "fp32 in, fp32 out; matrix products as exact bf16x6 split products with fp32 accumulation "
+                           "(fp32-level accuracy, tests/test_gpu_x6.py); NEFES_X6=0 selects the fp32-MFMA kernels"
+                           if any(k.endswith("x6]") for k in kern) else "fp32 MFMA"),
             "roofline": {"bound": "mfma", "kernel": dom_name, "achieved": ach,
                          "peak": peak, "unit": "TFLOP/s", "frac": ach / peak,
                          "peak_basis": ("dense fp16 MFMA peak 2500 / 3: fp16 two-part split, three products per algorithmic product, "
@@ -650,16 +685,7 @@ def main():
                          "end_to_end_vs_fp32_mfma_peak": value * (flop_frame / n_total) / (PEAK_F32_MFMA_TFLOPS * 1e12 * world),
                          "hbm_kernels": hbm_kernel_lines(kern, rays_local, Nc, Ni, Wd, C)},
             "kernels_ms": {k: round(v, 4) for k, v in sorted(kern.items())},
-            "pose_grad_abs_max": float(g.abs().max()),
-            # the all-reduced 3x4 pose gradient itself (row-major), so that an N-rank run can be compared with the 1-rank run number
-            # by number (tests/test_gpu_a_bench_launch.py), and each rank's own step time
-            "pose_grad": [float(v) for v in g.detach().reshape(-1).cpu().tolist()],
-            "ms_per_step_by_rank": {"min": min(rank_ms), "max": max(rank_ms), "all": [round(t, 4) for t in rank_ms]},
         }
-        if multi is not None:
-            out["multi_gpu"] = multi
-            if "one_gpu_shard_ms_reference" in multi:
-                out["multi_gpu"]["scaling_efficiency_vs_one_gpu_shard"] = multi["one_gpu_shard_ms_reference"] / ms_step
         if h3 or x6:
             # The 2 500 TFLOP/s data-sheet peak is a 2.4 GHz figure; under sustained MFMA issue with operands whose bits toggle
             # the chip's power management holds a lower clock.  Measured here, on this box, right after the timed region
@@ -676,7 +702,45 @@ def main():
                              "(power-limited clock; the data-sheet peak assumes 2.4 GHz)"}
             except Exception as e:                       # the probe is an aid, never a reason to lose the bench line
                 out["roofline"]["sustained"] = {"error": str(e)}
-        if world == 1 and a.cpu_rows > 0 and a.workload in ("metric", "metric128"):
+        return out
+
+    if a.dump_outputs:
+        # what the last timed step handed its caller: the maps of the whole frame (gathered from the row shards with N ranks), the loss
+        # and the all-reduced pose gradient
+        maps = {k: D.gather_maps(v.detach(), H, W=W) for k, v in last.items() if k != "loss"}
+        loss = last["loss"].detach().clone()
+        if grouped and world > 1:
+            dist.all_reduce(loss)                                        # each rank holds its rows' share of the frame's mean
+        if rank == 0:
+            dump_outputs(a.dump_outputs, dict(maps, loss=loss, pose_grad=g.detach()))
+
+    if rank == 0:
+        ms_step = dt / a.steps * 1e3
+        value = n_total * a.steps / dt
+        out = {
+            "metric": "rays/s (fwd+bwd) at 640x480x(64+128) samples, 8x256 MLP" if a.workload == "metric"
+                      else f"rays/s (fwd+bwd), secondary workload '{a.workload}'", "value": value, "unit": "rays/s",
+            "n_gpus": world, "world_size": dist.get_world_size() if grouped else 1,
+            "collective_backend": (dist.get_backend() if grouped else None), "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_step, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": f"{wl['name']}; {W}x{H}, random seed-0 weights, fwd + bwd to the 3x4 pose",
+                       "rays_per_step": n_total, "samples_per_ray": [Nc, Ni], "parallelism": f"rows/{world}"},
+            "pose_grad_abs_max": float(g.abs().max()),
+            # the all-reduced 3x4 pose gradient itself (row-major), so that an N-rank run can be compared with the 1-rank run number
+            # by number (tests/test_gpu_a_bench_launch.py), and each rank's own step time
+            "pose_grad": [float(v) for v in g.detach().reshape(-1).cpu().tolist()],
+            "ms_per_step_by_rank": {"min": min(rank_ms), "max": max(rank_ms), "all": [round(t, 4) for t in rank_ms]},
+        }
+        if a.full:
+            extra = full_fields(value)
+            out["config"]["arithmetic"] = extra.pop("arithmetic")
+            out.update(extra)
+        if multi is not None:
+            out["multi_gpu"] = multi
+            if "one_gpu_shard_ms_reference" in multi:
+                out["multi_gpu"]["scaling_efficiency_vs_one_gpu_shard"] = multi["one_gpu_shard_ms_reference"] / ms_step
+        if a.full and world == 1 and a.cpu_rows > 0 and a.workload in ("metric", "metric128"):
             out["cpu_baseline"] = cpu_baseline(Wd, C, Nc, Ni, a.cpu_rows, W, focal)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)

@@ -14,10 +14,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "1", "--warmup", "1", "--height", "48", "--width", "64", "--cpu-rows", "0"]
+SMALL = ["--steps", "1", "--warmup", "1", "--height", "48", "--width", "64", "--cpu-rows", "0", "--full"]
 # BASELINE configs[2] functionally: the frame's 480 rows over 8 ranks = 60 rows per rank, exactly the 8-GPU partition (the width is
 # shrunk instead of the row count, so that eight ranks sharing one GPU stay a functional check)
-ROWS480 = ["--steps", "1", "--warmup", "1", "--height", "480", "--width", "8", "--cpu-rows", "0"]
+ROWS480 = ["--steps", "1", "--warmup", "1", "--height", "480", "--width", "8", "--cpu-rows", "0", "--full"]
 
 
 def bench(extra, env_extra, timeout=900):
@@ -127,7 +127,7 @@ def test_the_n_rank_code_path_of_bench_through_rccl_under_the_drivers_launcher()
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--height", "48", "--width", "64", "--cpu-rows", "0"]
+           "--height", "48", "--width", "64", "--cpu-rows", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=900, close_fds=True)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and lines, (r.stdout[-1000:], r.stderr[-3000:])
@@ -143,3 +143,37 @@ def test_the_n_rank_code_path_of_bench_through_rccl_under_the_drivers_launcher()
     r1, j1 = bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--height", "48", "--width", "64", "--cpu-rows", "0"], {})
     assert r1.returncode == 0 and j1 is not None, r1.stderr[-2000:]
     assert j1["pose_grad"] == j["pose_grad"]                                # all-reduce over one rank: the identity
+
+
+def test_plain_run_is_the_headline_and_dumps_what_the_last_step_computed(tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the --full extras; --dump-outputs writes the maps render() returned
+    in the last timed step, the loss and the pose gradient as float32 .npy files.  The dumped arrays are those of the line (the pose
+    gradient), agree with each other (the loss is mean(feat^2) + mean(rgb^2) of the dumped maps), repeat exactly in a second run, and
+    the row shards of two ranks gathered back equal the one-rank frame."""
+    import numpy as np
+    H, W = 48, 64
+    args = ["--steps", "2", "--warmup", "1", "--height", str(H), "--width", str(W)]
+    r1, j1 = bench(["--gpus", "1"] + args + ["--dump-outputs", str(tmp_path / "a")], {})
+    assert r1.returncode == 0 and j1 is not None, r1.stderr[-2000:]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in j1, key
+    assert j1["steps"] == 2 and j1["ms_per_step"] > 0 and j1["unit"] == "rays/s" and j1["higher_is_better"] is True
+    assert abs(j1["value"] - H * W / (j1["ms_per_step"] * 1e-3)) <= 1e-6 * j1["value"]
+    for key in ("roofline", "kernels_ms", "cpu_baseline", "multi_gpu"):
+        assert key not in j1, key
+    d = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("rgb_map", "disp_map", "acc_map", "feat_map", "loss", "pose_grad")}
+    assert all(v.dtype == np.float32 for v in d.values())
+    assert d["rgb_map"].shape == (H * W, 3) and d["feat_map"].shape == (H * W, 16)
+    assert d["disp_map"].shape == (H * W,) and d["acc_map"].shape == (H * W,) and d["pose_grad"].shape == (3, 4)
+    assert np.array_equal(d["pose_grad"].reshape(-1), np.asarray(j1["pose_grad"], dtype=np.float32))
+    loss = (d["feat_map"].astype(np.float64) ** 2).mean() + (d["rgb_map"].astype(np.float64) ** 2).mean()
+    assert abs(float(d["loss"].reshape(-1)[0]) - loss) <= 1e-5 * loss
+    r2, _ = bench(["--gpus", "1"] + args + ["--dump-outputs", str(tmp_path / "b")], {})
+    assert r2.returncode == 0, r2.stderr[-2000:]
+    for n, v in d.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")), n          # same arguments: same inputs, same outputs
+    rn, jn = bench(["--gpus", "2"] + args + ["--dump-outputs", str(tmp_path / "n")], {"NEFES_BENCH_ONE_GPU": "1", "NEFES_BENCH_BACKEND": "gloo"})
+    assert rn.returncode == 0 and jn is not None, rn.stderr[-2000:]
+    for n in ("rgb_map", "disp_map", "acc_map", "feat_map"):
+        vn = np.load(tmp_path / "n" / f"{n}.npy")
+        assert vn.shape == d[n].shape and np.abs(vn - d[n]).max() <= 1e-6 * max(1.0, np.abs(d[n]).max()), n

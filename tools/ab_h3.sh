@@ -20,7 +20,7 @@ else
     lib=$OUT/libnefes_$name.so; [ $name = shipped ] && lib=$ROOT/nefes_amd/libnefes_hip.so
     for wl in ${AB_WORKLOADS:-metric ref}; do
       EXTRA="--steps 2 --warmup 1"; [ $wl = ref ] && EXTRA="--steps 50 --warmup 5"; [ $wl = train ] && EXTRA=""
-      NEFES_HIP_LIB=$lib python $ROOT/bench.py --workload $wl $EXTRA --cpu-rows 0 2>/dev/null | python -c "
+      NEFES_HIP_LIB=$lib python $ROOT/bench.py --workload $wl $EXTRA --cpu-rows 0 --full 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels_ms']
 import hashlib

@@ -11,7 +11,8 @@ python -m pytest tests -q -m gpu > gpurun_out/${R}_gputest.log 2>&1; tail -3 gpu
 bash tools/profile_round.sh $R > gpurun_out/${R}_profile.log 2>&1
 bash tools/profile_secondary.sh $R > gpurun_out/${R}_secondary.log 2>&1
 mkdir -p profiles/$R && cp gpurun_out/$R/pmc_per_launch.json profiles/$R/
-python bench.py > gpurun_out/$R/bench_full.json 2> gpurun_out/$R/bench_full.err; cat gpurun_out/$R/bench_full.json
+OUT=$(dirname "$NEFES_PARITY_LOG")/$R      # this round's output folder, beside the parity log
+python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; cat $OUT/bench_full.json
 cd /tmp; export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/$R/loop1 -- python3 $ROOT/tools/prof_loop1.py > $ROOT/gpurun_out/$R/loop1.log 2>&1
 cd $ROOT
