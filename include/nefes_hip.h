@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define NEFES_ABI_VERSION 14
+#define NEFES_ABI_VERSION 15
 
 #define NEFES_E_BADARG (-1)     /* null pointer / non-positive size */
 #define NEFES_E_UNSUPPORTED (-2) /* width / feat_dim / sample count outside the compiled set */
@@ -197,6 +197,14 @@ int nefes_hashgrid_fwd(const NefesHashGridDesc* desc, const float* table, int64_
 /* backward to the positions (frozen table): g_x [M,3]. */
 int nefes_hashgrid_bwd_x(const NefesHashGridDesc* desc, const float* table, int64_t M, const float* x, const float* g_enc,
                          float* g_x, void* stream);
+/* backward to the table (training the grid): g_table [entries][n_features] += d loss / d table for enc = grid(x), given
+ * g_enc [M, n_levels*n_features].  g_table is fp32, zeroed by the caller (several calls may add into one buffer).  `workspace`:
+ * nefes_hashgrid_bwd_table_workspace(desc) bytes of device memory (any contents; the call clears it): the dense levels' sums are
+ * accumulated there in fp64 and rounded once into g_table, the hashed levels' in fp32 directly.  Atomics: reproducible to rounding,
+ * not bitwise (the order of the adds to one entry is not fixed). */
+size_t nefes_hashgrid_bwd_table_workspace(const NefesHashGridDesc* desc);
+int nefes_hashgrid_bwd_table(const NefesHashGridDesc* desc, int64_t M, const float* x, const float* g_enc, float* g_table,
+                             void* workspace, void* stream);
 
 /* nefes_field_fwd(mode = NEFES_FIELD_SIGMA or NEFES_FIELD_FULL) with the hidden 256x256 products (layers 2..8 and
  * xyz_encoding_final) as bf16x6 split products on v_mfma_f32_32x32x16_bf16 -- exact hi/mid/lo bf16 triples, six cross terms,
@@ -312,6 +320,15 @@ int nefes_field_bwd_train_h3(const NefesNetDesc* desc, const void* packed, int m
                              const float* rays_d, const float* z, const float* viewdirs, const float* raw_t,
                              const float* g_raw_t, const uint32_t* masks, float* dacts, float* g_pts, float* g_viewdirs_s,
                              void* stream);
+/* Train mode of a NEFES_XYZ_EXTERNAL32 network (a trainable hash grid in front of the MLP): the forward reads the caller's encoding
+ * xyz_enc [N*S, 32] and stores it into rows 0..31 of the E block of `acts` in natural feature order; the backward writes `dacts` as
+ * nefes_field_bwd_train_h3 does plus g_xyz_enc [N*S, 32] = d loss / d xyz_enc (no ray gradients: those pass through the encoding).
+ * fp16 two-part pipe, width 256, head class 0 (3 + C <= 32) only; mode NEFES_FIELD_STATIC or NEFES_FIELD_FULL. */
+int nefes_field_fwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* xyz_enc,
+                                 const float* viewdirs, float* raw_t, float* acts, uint32_t* masks, void* stream);
+int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* viewdirs,
+                                 const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* dacts, float* g_xyz_enc,
+                                 float* g_viewdirs_s, void* stream);
 /* d raw_t [N][R][S] -> head pre-activation gradients in dacts blocks RGB, SIG (, TH); samples beyond N*S are zeroed. */
 int nefes_train_head_grad(const NefesNetDesc* desc, int mode, int N, int S, const float* raw_t, const float* g_raw_t,
                           float* dacts, void* stream);

@@ -580,7 +580,8 @@ static int launch_bwd_h3(const FieldBwdH3Args& a, hipStream_t st) {
 #ifndef NEFES_TU_PART
 #define NEFES_TU_PART 0
 #endif
-enum { BWD_H3_EXT = 0, BWD_H3_FULL, BWD_H3_TRAIN_STATIC, BWD_H3_TRAIN_FULL, BWD_H3_STATIC, BWD_H3_HG, BWD_H3_FH };
+enum { BWD_H3_EXT = 0, BWD_H3_FULL, BWD_H3_TRAIN_STATIC, BWD_H3_TRAIN_FULL, BWD_H3_STATIC, BWD_H3_HG, BWD_H3_FH, BWD_H3_TRAIN_EXT_STATIC,
+       BWD_H3_TRAIN_EXT_FULL };
 int nefes_bwd_h3_launch_part1(int which, const FieldBwdH3Args& a, hipStream_t st);
 int nefes_bwd_h3_launch_part2(int which, const FieldBwdH3Args& a, hipStream_t st);
 int nefes_bwd_h3_launch_part3(int which, const FieldBwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 256, class 0
@@ -611,6 +612,8 @@ int nefes_bwd_h3_launch_part2(int which, const FieldBwdH3Args& a, hipStream_t st
 int nefes_bwd_h3_launch_part3(int which, const FieldBwdH3Args& a, hipStream_t st) {
     if (which == BWD_H3_TRAIN_STATIC) return launch_bwd_h3<256, 2, NEFES_XYZ_FREQ10, false, true>(a, st);
     if (which == BWD_H3_TRAIN_FULL) return launch_bwd_h3<256, 2, NEFES_XYZ_FREQ10, true, true>(a, st);
+    if (which == BWD_H3_TRAIN_EXT_STATIC) return launch_bwd_h3<256, 2, NEFES_XYZ_EXTERNAL32, false, true>(a, st);   // trainable hash grid
+    if (which == BWD_H3_TRAIN_EXT_FULL) return launch_bwd_h3<256, 2, NEFES_XYZ_EXTERNAL32, true, true>(a, st);
     return NEFES_E_UNSUPPORTED;
 }
 #elif NEFES_TU_PART == 4      // (built like part 2)
@@ -679,6 +682,36 @@ extern "C" int nefes_field_bwd_train_h3(const NefesNetDesc* desc, const void* pa
     hipStream_t st = (hipStream_t)stream;
     if (desc->width == 256) return cls == 0 ? nefes_bwd_h3_launch_part3(which, a, st) : nefes_bwd_h3_launch_part7(which, a, st);
     return cls == 1 ? nefes_bwd_h3_launch_part4(which, a, st) : nefes_bwd_h3_launch_part8(which, a, st);
+}
+
+// The same for a NEFES_XYZ_EXTERNAL32 network (nefes_field_fwd_train_h3_ext): `dacts` as above, g_xyz_enc [N*S, 32] = d loss / d its
+// encoding (what the hash grid's table gradient consumes), g_viewdirs_s per sample.  Width 256, head class 0.
+extern "C" int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* viewdirs,
+                                            const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* dacts,
+                                            float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
+    if (!desc || !packed || !viewdirs || !raw_t || !g_raw_t || !masks || !dacts || !g_xyz_enc || !g_viewdirs_s || N <= 0 || S <= 0)
+        return NEFES_E_BADARG;
+    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
+    const bool full = mode == NEFES_FIELD_FULL;
+    if (full && !desc->has_transient) return NEFES_E_UNSUPPORTED;
+    if (desc->width != 256 || nefes_head_class(desc->feat_dim) != 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
+    NefesBlobInfo info;
+    int rc = nefes_blob_info(desc, &info);
+    if (rc) return rc;
+    const NefesStreamInfo& si = info.stream[full ? NEFES_STREAM_BWD_FULL_H3 : NEFES_STREAM_BWD_STATIC_H3];
+    if (si.n_slabs == 0 || si.scale_count < 2 * (uint32_t)(full ? NEFES_H3B_N : NEFES_H3B_N_STATIC)) return NEFES_E_UNSUPPORTED;
+    FieldBwdH3Args a;
+    a.stream = (const char*)packed + si.slab_off;
+    a.tab = (const int*)((const char*)packed + si.bias_off) + si.scale_off;
+    a.n_slabs = si.n_slabs;
+    a.rays_o = nullptr; a.rays_d = nullptr; a.z = nullptr; a.pts = nullptr; a.viewdirs = viewdirs;
+    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.g_pts = nullptr; a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
+    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = 3 + a.C + (full ? 6 : 1);
+    a.M = (long long)N * S;
+    a.n_tiles = (int)((a.M + 127) / 128);
+    a.dacts = dacts; a.gout = 0; a.hg_table = nullptr; a.g_gmap = nullptr;
+    a.rows = nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END);
+    return nefes_bwd_h3_launch_part3(full ? BWD_H3_TRAIN_EXT_FULL : BWD_H3_TRAIN_EXT_STATIC, a, (hipStream_t)stream);
 }
 
 // nefes_field_bwd_static on the fp16 pipe: backward-to-inputs of a NEFES_FIELD_STATIC forward with frozen weights (round 5: every

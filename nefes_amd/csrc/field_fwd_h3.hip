@@ -512,7 +512,8 @@ static int launch_h3(const FieldFwdH3Args& a, hipStream_t st) {
 #ifndef NEFES_TU_PART
 #define NEFES_TU_PART 0
 #endif
-enum { H3_EXT_SIGMA = 0, H3_EXT_FULL, H3_SIGMA, H3_FULL, H3_TRAIN_STATIC, H3_TRAIN_FULL, H3_STATIC, H3_HG_SIGMA, H3_HG_FULL, H3_FH_FULL };
+enum { H3_EXT_SIGMA = 0, H3_EXT_FULL, H3_SIGMA, H3_FULL, H3_TRAIN_STATIC, H3_TRAIN_FULL, H3_STATIC, H3_HG_SIGMA, H3_HG_FULL, H3_FH_FULL,
+       H3_TRAIN_EXT_STATIC, H3_TRAIN_EXT_FULL };
 int nefes_fwd_h3_launch_part1(int which, const FieldFwdH3Args& a, hipStream_t st);
 int nefes_fwd_h3_launch_part2(int which, const FieldFwdH3Args& a, hipStream_t st);
 int nefes_fwd_h3_launch_part3(int which, const FieldFwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 256, class 0
@@ -553,6 +554,10 @@ int nefes_fwd_h3_launch_part3(int which, const FieldFwdH3Args& a, hipStream_t st
     switch (which) {
         case H3_TRAIN_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 256, 1, true>(a, st);
         case H3_TRAIN_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 256, 1, true>(a, st);
+        // an external 32-feature encoding (a trainable hash grid): its features go to the E block in natural order (compact slot
+        // (s, h) = feature 2s + h = row 2s + h)
+        case H3_TRAIN_EXT_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_EXTERNAL32, 256, 1, true>(a, st);
+        case H3_TRAIN_EXT_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_EXTERNAL32, 256, 1, true>(a, st);
     }
     return NEFES_E_UNSUPPORTED;
 }
@@ -627,6 +632,36 @@ extern "C" int nefes_field_fwd_train_h3(const NefesNetDesc* desc, const void* pa
     hipStream_t st = (hipStream_t)stream;
     if (desc->width == 256) return cls == 0 ? nefes_fwd_h3_launch_part3(which, a, st) : nefes_fwd_h3_launch_part7(which, a, st);
     return cls == 1 ? nefes_fwd_h3_launch_part4(which, a, st) : nefes_fwd_h3_launch_part8(which, a, st);
+}
+
+// Train-mode forward of a NEFES_XYZ_EXTERNAL32 network on its caller-supplied encoding xyz_enc [N*S, 32] (a trainable hash grid):
+// as nefes_field_fwd_train_h3, with the 32 features in rows 0..31 of the E block, natural order.  Width 256, head class 0.
+extern "C" int nefes_field_fwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* xyz_enc,
+                                            const float* viewdirs, float* raw_t, float* acts, uint32_t* masks, void* stream) {
+    if (!desc || !packed || !xyz_enc || !raw_t || !acts || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
+    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_UNSUPPORTED;
+    if (mode == NEFES_FIELD_FULL && !desc->has_transient) return NEFES_E_BADARG;
+    if (desc->width != 256 || nefes_head_class(desc->feat_dim) != 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
+    NefesBlobInfo info;
+    int rc = nefes_blob_info(desc, &info);
+    if (rc) return rc;
+    const NefesStreamInfo& si = info.stream[mode == NEFES_FIELD_STATIC ? NEFES_STREAM_FWD_STATIC_H3 : NEFES_STREAM_FWD_FULL_H3];
+    if (si.n_slabs == 0) return NEFES_E_UNSUPPORTED;
+    FieldFwdH3Args a;
+    a.stream = (const char*)packed + si.slab_off;
+    a.bias = (const float*)((const char*)packed + si.bias_off);
+    a.n_slabs = si.n_slabs; a.bias_floats = si.bias_floats; a.scale_off = si.scale_off;
+    a.rays_o = nullptr; a.rays_d = nullptr; a.z = nullptr; a.pts = nullptr; a.xyz_enc = xyz_enc; a.viewdirs = viewdirs; a.raw_t = raw_t;
+    a.masks = masks;
+    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = 3 + a.C + (mode == NEFES_FIELD_STATIC ? 1 : 6);
+    a.M = (long long)N * S;
+    if (a.M >= (1ll << 31) - 256) return NEFES_E_UNSUPPORTED;      // the kernel indexes samples with 32 bits
+    a.n_tiles = (int)((a.M + 127) / 128);
+    a.acts = acts;
+    a.rows = nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END);
+    a.z_row = 0; a.gout = 0; a.hg_table = nullptr;
+    magic_div((uint32_t)S, a.s_magic, a.s_shift);
+    return nefes_fwd_h3_launch_part3(mode == NEFES_FIELD_STATIC ? H3_TRAIN_EXT_STATIC : H3_TRAIN_EXT_FULL, a, (hipStream_t)stream);
 }
 
 static int field_fwd_h3_impl(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,

@@ -481,7 +481,7 @@ bool build(const NefesNetDesc* d, const float* const* tensors, Net& n, Stream (&
     if (h3_shape) {
         add_trunk(n, st[NEFES_STREAM_FWD_SIGMA_H3], 2);
         st[NEFES_STREAM_FWD_SIGMA_H3].h3 = true;
-        if (!n.ext) {                                   // static head only: what a coarse network runs in train mode
+        {                                               // static head only: what a coarse network runs in train mode
             add_trunk(n, st[NEFES_STREAM_FWD_STATIC_H3], 2);
             add_static_head_h3(n, st[NEFES_STREAM_FWD_STATIC_H3]);
             add_backward(n, st[NEFES_STREAM_BWD_STATIC_H3], 2, false);

@@ -848,7 +848,11 @@ def sample_pdf_merge(z_coarse, weights, Ni, u=None, cdf=None, want_debug=False, 
 # hash-grid encoding (BASELINE config 4; parity unpinned, see oracle/hashgrid_ref.py)
 # ---------------------------------------------------------------------------------------------
 class HashGrid:
-    """Table + geometry of a tiny-cuda-nn style multiresolution hash grid (nerfh_tcnn.py:60-75)."""
+    """Table + geometry of a tiny-cuda-nn style multiresolution hash grid (nerfh_tcnn.py:60-75).
+
+    `table` is a plain fp32 tensor [entries, 2] that does not require grad: the grid is frozen and every path runs as it always did.
+    `grid.table.requires_grad_(True)` makes it trainable -- HashGridEncode then returns d loss / d table (nefes_hashgrid_bwd_table),
+    render() routes the grid through the separate encode + field launches, and `grid.parameters()` hands it to an optimiser."""
 
     def __init__(self, bound, table=None, n_levels=16, log2_hashmap_size=19, base_resolution=16, max_resolution=2048,
                  device="cuda"):
@@ -867,7 +871,16 @@ class HashGrid:
         self.table = table.to(device, torch.float32).contiguous()
 
     def __call__(self, x):
-        return HashGridEncode.apply(x, self)
+        return HashGridEncode.apply(x, self.table, self)
+
+    def parameters(self):
+        """[table] -- for torch.optim, e.g. Adam([*net.parameters(), *grid.parameters()]) after table.requires_grad_(True)."""
+        return [self.table]
+
+    @property
+    def trainable(self):
+        """autograd records a gradient for the table in the current context."""
+        return torch.is_grad_enabled() and self.table.requires_grad
 
 
 # BASELINE configs[3] with the hash grid evaluated INSIDE the field kernels (csrc/hashgrid.h, nefes_field_fwd_h3_hashgrid /
@@ -927,14 +940,31 @@ class FieldFromRaysHashGrid(torch.autograd.Function):
         return g_o, g_d, g_v, None, None, None, None
 
 
+def hashgrid_bwd_table(grid, x, g_enc, g_table=None):
+    """g_table [entries, 2] (+)= d loss / d table for enc = grid(x), x [M, 3], g_enc [M, 32] (atomics: reproducible to rounding, not
+    bitwise; the dense levels are summed in fp64 and rounded once).  g_table=None: a fresh zeroed buffer; otherwise the call adds into
+    the one given."""
+    lib = L.load()
+    if g_table is None:
+        g_table = torch.zeros_like(grid.table, dtype=torch.float32)
+    ws = torch.empty(max(1, int(lib.nefes_hashgrid_bwd_table_workspace(grid.desc))), dtype=torch.uint8, device=g_table.device)
+    with _timed("hashgrid_bwd_table"):
+        L.check(lib.nefes_hashgrid_bwd_table(grid.desc, x.shape[0], _chk(x, "x"), _chk(g_enc, "g_enc"), _chk(g_table, "g_table"),
+                                             C.c_void_p(ws.data_ptr()), _stream()), "nefes_hashgrid_bwd_table")
+    return g_table
+
+
 class HashGridEncode(torch.autograd.Function):
+    """enc = grid(x): x [..., 3] -> [..., 32]; differentiable w.r.t. x (nefes_hashgrid_bwd_x) and, when it requires grad, the table
+    (nefes_hashgrid_bwd_table).  `table` is grid.table, passed as an input so that autograd routes its gradient."""
+
     @staticmethod
-    def forward(ctx, x, grid):
+    def forward(ctx, x, table, grid):
         shape = x.shape
         xf = _f32(x).reshape(-1, 3)
         enc = torch.empty(xf.shape[0], grid.n_out, device=xf.device)
         with _timed("hashgrid_fwd"):
-            L.check(L.load().nefes_hashgrid_fwd(grid.desc, _chk(grid.table, "table"), xf.shape[0], _chk(xf, "x"),
+            L.check(L.load().nefes_hashgrid_fwd(grid.desc, _chk(table, "table"), xf.shape[0], _chk(xf, "x"),
                                                 _chk(enc, "enc"), _stream()), "nefes_hashgrid_fwd")
         ctx.save_for_backward(xf)
         ctx.grid, ctx.shape = grid, shape
@@ -944,11 +974,16 @@ class HashGridEncode(torch.autograd.Function):
     def backward(ctx, g_enc):
         (xf,) = ctx.saved_tensors
         g = _f32(g_enc).reshape(-1, ctx.grid.n_out)
-        g_x = torch.empty_like(xf)
-        with _timed("hashgrid_bwd_x"):
-            L.check(L.load().nefes_hashgrid_bwd_x(ctx.grid.desc, _chk(ctx.grid.table, "table"), xf.shape[0], _chk(xf, "x"),
-                                                  _chk(g, "g_enc"), _chk(g_x, "g_x"), _stream()), "nefes_hashgrid_bwd_x")
-        return g_x.reshape(ctx.shape), None
+        g_x = g_table = None
+        if ctx.needs_input_grad[0]:
+            g_x = torch.empty_like(xf)
+            with _timed("hashgrid_bwd_x"):
+                L.check(L.load().nefes_hashgrid_bwd_x(ctx.grid.desc, _chk(ctx.grid.table, "table"), xf.shape[0], _chk(xf, "x"),
+                                                      _chk(g, "g_enc"), _chk(g_x, "g_x"), _stream()), "nefes_hashgrid_bwd_x")
+            g_x = g_x.reshape(ctx.shape)
+        if ctx.needs_input_grad[1]:
+            g_table = hashgrid_bwd_table(ctx.grid, xf, g)
+        return g_x, g_table, None
 
 
 _CONV_PACK = {}     # (id(weight), backward) -> (weakref to the weight, its version, packed [Cin even][K*K][Cout multiple of 32])

@@ -104,11 +104,18 @@ def _trainable(net):
                     if not n.startswith(("fusion_net", "exposure_embedding"))))
 
 
+def _grid_trainable(xyz_encoder):
+    """A hash grid whose table asks for a gradient (ops.HashGrid.trainable)."""
+    return xyz_encoder is not None and bool(getattr(xyz_encoder, "trainable", False))
+
+
 def _field(pk, mode, rays_o, rays_d, viewdirs, z, xyz_encoder):
     """raw_t [N,R,S] for samples z along the rays; differentiable w.r.t. rays_o, rays_d, viewdirs in FULL mode."""
     if xyz_encoder is None:
         return ops.FieldFromRays.apply(rays_o, rays_d, viewdirs, z, pk, mode)
-    if mode != L.FIELD_STATIC and ops.hashgrid_fused_ok(pk, xyz_encoder) and z.shape[0] * z.shape[1] < (1 << 31) - 256:
+    if (mode != L.FIELD_STATIC and ops.hashgrid_fused_ok(pk, xyz_encoder) and z.shape[0] * z.shape[1] < (1 << 31) - 256
+            and not _grid_trainable(xyz_encoder)):
+        # (a trainable table takes the separate launches below: they hand HashGridEncode the gradient of the encoding)
         # BASELINE configs[3]: the field kernels gather the hash grid themselves (no [M, 32] encoding, no pts tensor)
         return ops.FieldFromRaysHashGrid.apply(rays_o, rays_d, viewdirs, z, pk, mode, xyz_encoder)
     pts = rays_o[:, None, :] + rays_d[:, None, :] * z[..., None]                    # rendering.py:114,142 (torch glue)
@@ -127,10 +134,13 @@ def _render_core(rays_o, rays_d, viewdirs, near, far, network_fn, network_fine, 
     trainable = _trainable
 
     def field(net, pk, mode, z_):
-        if trainable(net) and mode != L.FIELD_SIGMA:
-            if cfg.xyz_encoder is not None:
-                raise NotImplementedError("nefes_amd: train mode is built for the frequency embedding only")
+        # a trainable hash-grid table behind a frozen network: the static head (coarse pass, test_time False) has no backward on the
+        # inference instances, so it runs on the train-mode ones too (without the weight gradients); the full head does (_field)
+        grid_static = mode == L.FIELD_STATIC and _grid_trainable(cfg.xyz_encoder)
+        if (trainable(net) or grid_static) and mode != L.FIELD_SIGMA:
             from . import train as T
+            if cfg.xyz_encoder is not None:
+                return T.field_train_encoded(net, mode, cfg.xyz_encoder, rays_o, rays_d, viewdirs, z_)
             return T.field_train(net, mode, rays_o, rays_d, viewdirs, z_)
         return _field(pk, mode, rays_o, rays_d, viewdirs, z_, cfg.xyz_encoder)
 

@@ -150,19 +150,27 @@ def fp16_pipe(pk):
     return ops._h3(pk) and ops.h3_shape(pk) and pk.xyz_encoding == L.XYZ_FREQ10
 
 
+def ext_pipe(pk):
+    """The train-mode instances of a network on an external 32-feature encoding (a hash grid): fp16 two-part pipe, width 256, head
+    class 0 (csrc/field_fwd_h3.hip H3_TRAIN_EXT_*)."""
+    return ops._h3(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32 and pk.width == 256 and ops.head_class(pk.feat_dim) == 0
+
+
 FUSED_DX = True       # one fused backward launch (nefes_field_bwd_train) instead of the layer-by-layer nefes_train_dx chain
 
 
-def weight_grads(net, pk, mode, N, S, raw_t, g_raw_t, acts, fused=None):
+def weight_grads(net, pk, mode, N, S, raw_t, g_raw_t, acts, fused=None, ext=False, want_w=True):
     """-> dict parameter name -> gradient (fp32, parameter shape) for every parameter on the path of `mode`.
-    fused = (rays_o, rays_d, viewdirs, z, masks): run the dX chain as one fused kernel launch."""
+    fused = (rays_o, rays_d, viewdirs, z, masks): run the dX chain as one fused kernel launch.
+    ext: a network on an external 32-feature encoding; fused = (viewdirs, masks), and "__rays__" holds (d encoding [N*S, 32],
+    d viewdirs per sample) instead of the per-sample ray gradients.  want_w=False: the dX chain alone (no parameter gradients)."""
     lib, desc = L.load(), pk.desc
     W, Cf = net.W, net.W_features
     C3, H2 = 3 + Cf, W // 2
     full = mode == L.FIELD_FULL
     n_tiles = acts.shape[0]
     dacts = torch.empty_like(acts)
-    if not (fused is not None and fp16_pipe(pk)):             # (the fp16 dX kernel writes the head blocks itself)
+    if not (fused is not None and (ext or fp16_pipe(pk))):    # (the fp16 dX kernel writes the head blocks itself)
         L.check(lib.nefes_train_head_grad(C.byref(desc), mode, N, S, raw_t.data_ptr(), g_raw_t.data_ptr(), dacts.data_ptr(),
                                           ops._stream()), "nefes_train_head_grad")
     P = _Pass(net, desc, n_tiles, acts, dacts)
@@ -171,7 +179,13 @@ def weight_grads(net, pk, mode, N, S, raw_t, g_raw_t, acts, fused=None):
     keep = []
     TB = lambda l: L.TB_L1 + (l - 1)
     # ---- backward through the layers: dacts rows of every hidden block become d loss / d pre-activation ----
-    if fused is not None:
+    if ext:
+        v, masks = fused
+        g_pts, g_vs = torch.empty(N * S, 32, device=acts.device), torch.empty(N * S, 3, device=acts.device)     # (g_pts: d encoding)
+        L.check(lib.nefes_field_bwd_train_h3_ext(C.byref(desc), pk.blob.data_ptr(), mode, N, S, v.data_ptr(), raw_t.data_ptr(),
+                                                 g_raw_t.data_ptr(), masks.data_ptr(), dacts.data_ptr(), g_pts.data_ptr(), g_vs.data_ptr(),
+                                                 ops._stream()), "nefes_field_bwd_train_h3_ext")
+    elif fused is not None:
         o, d, v, zz, masks = fused
         g_pts, g_vs = torch.empty(N * S, 3, device=acts.device), torch.empty(N * S, 3, device=acts.device)
         bwd = lib.nefes_field_bwd_train_h3 if fp16_pipe(pk) else lib.nefes_field_bwd_train
@@ -198,13 +212,18 @@ def weight_grads(net, pk, mode, N, S, raw_t, g_raw_t, acts, fused=None):
         for l in range(8, 1, -1):
             wl = w(f"xyz_encoding_{l}.0")
             keep.append(P.dx(TB(l), W, wl[:, EMB_XYZ:] if l == 5 else wl, W, TB(l - 1), False, True))
-    # ---- weight gradients ----
-    e_idx = _slot_rows(10, 64, EMB_XYZ, acts.device)
-    d_idx = _slot_rows(4, 28, EMB_DIR, acts.device)
     g = {}
-    h1 = P.dw(TB(1), W, L.TB_E, 64, False)
+    if not want_w:
+        g["__rays__"] = (g_pts, g_vs)
+        return g
+    # ---- weight gradients ----
+    # E block: the frequency embedding's 63 features in slot order (64 rows), or an external encoding's 32 in natural order
+    e_idx = torch.arange(32, device=acts.device) if ext else _slot_rows(10, 64, EMB_XYZ, acts.device)
+    n_e = 32 if ext else 64
+    d_idx = _slot_rows(4, 28, EMB_DIR, acts.device)
+    h1 = P.dw(TB(1), W, L.TB_E, n_e, False)
     hl = {l: P.dw(TB(l), W, TB(l - 1), W, True) for l in range(2, 9)}
-    h5e = P.dw(TB(5), W, L.TB_E, 64, False, bias=False)
+    h5e = P.dw(TB(5), W, L.TB_E, n_e, False, bias=False)
     hsig, hfin = P.dw(L.TB_SIG, 1, TB(8), W, True), P.dw(L.TB_FINAL, W, TB(8), W, True)
     hdir, hdird = P.dw(L.TB_DIR, H2, L.TB_FINAL, W, False), P.dw(L.TB_DIR, H2, L.TB_DV, 32, False, bias=False)
     hrgb = P.dw(L.TB_RGB, C3, L.TB_DIR, H2, True)
@@ -315,3 +334,68 @@ class FieldTrain(torch.autograd.Function):
 def field_train(net, mode, rays_o, rays_d, viewdirs, z):
     sd = dict(net.named_parameters())
     return FieldTrain.apply(rays_o, rays_d, viewdirs, z, net, mode, *[sd[n] for n in param_names(net, mode)])
+
+
+class FieldTrainEncoded(torch.autograd.Function):
+    """FieldTrain for a network on an external 32-feature xyz encoding (a hash grid, BASELINE configs[3]): raw_t [N,R,S] from
+    enc [N,S,32] and viewdirs [N,3], differentiable w.r.t. enc (-> the grid's table and the sample positions, HashGridEncode),
+    viewdirs and the network parameters (*params in `param_names` order).  fp16 two-part train instances, width 256, head class 0."""
+
+    @staticmethod
+    def forward(ctx, enc, viewdirs, net, mode, *params):
+        pk = net.packed()
+        lib = L.load()
+        if mode not in (L.FIELD_STATIC, L.FIELD_FULL):
+            raise ValueError("nefes_amd: train mode evaluates the static or the full head")
+        if not ext_pipe(pk):
+            raise NotImplementedError(f"nefes_amd: train mode on an external (hash-grid) encoding is built for width 256 with 3 + f_dim <= 32 "
+                                      f"on the fp16 two-part instances (NEFES_SPLIT=h3); got W={pk.width}, f_dim={pk.feat_dim}, "
+                                      f"NEFES_SPLIT={ops.SPLIT}.  Compiled: {ops.COMPILED_SET}")
+        N, S = enc.shape[0], enc.shape[1]
+        if N * S >= (1 << 31) - 256:
+            raise RuntimeError("nefes_amd: too many samples for one launch of the fp16 two-part kernels (32-bit sample index)")
+        e, v = ops._f32(enc).reshape(N * S, 32), ops._f32(viewdirs)
+        R = 3 + pk.feat_dim + (1 if mode == L.FIELD_STATIC else 6)
+        n_tiles = (N * S + 127) // 128
+        rows = int(lib.nefes_train_rows(C.byref(pk.desc)))
+        raw_t = torch.empty(N, R, S, device=e.device)
+        acts = torch.empty(n_tiles, rows, 128, device=e.device)
+        masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=e.device)
+        with ops._timed("field_fwd_train[h3,ext]"):
+            L.check(lib.nefes_field_fwd_train_h3_ext(C.byref(pk.desc), pk.blob.data_ptr(), mode, N, S, ops._chk(e, "enc"),
+                                                     ops._chk(v, "viewdirs"), raw_t.data_ptr(), acts.data_ptr(), masks.data_ptr(),
+                                                     ops._stream()), "nefes_field_fwd_train_h3_ext")
+        ops._tap("masks", (masks, N, S, pk.width, mode))
+        ctx.save_for_backward(raw_t, acts, v, masks)
+        if DEBUG is not None:
+            DEBUG.update(acts=rows_view(acts), rows=rows, off={b: int(lib.nefes_train_row_offset(C.byref(pk.desc), b)) for b in range(19)})
+        ctx.net, ctx.pk, ctx.mode, ctx.NS, ctx.pk_gen = net, pk, mode, (N, S), pk.generation
+        return raw_t
+
+    @staticmethod
+    def backward(ctx, g_raw_t):
+        ctx.pk.check_generation(ctx.pk_gen)
+        raw_t, acts, v, masks = ctx.saved_tensors
+        N, S = ctx.NS
+        want_w = any(ctx.needs_input_grad[4:])
+        with ops._timed("field_bwd_train[h3,ext]"):
+            g = weight_grads(ctx.net, ctx.pk, ctx.mode, N, S, raw_t, ops._f32(g_raw_t), acts, fused=(v, masks), ext=True, want_w=want_w)
+        g_enc, g_vs = g.pop("__rays__")
+        g_v = None
+        if ctx.needs_input_grad[1]:
+            _, _, g_v = ops.ray_grad_reduce(N, S, torch.zeros(N, S, device=v.device), g_vs, g_vs)
+        g_params = (None,) * (len(ctx.needs_input_grad) - 4)
+        if want_w:
+            g = ctx.net.shrink_grads(g)
+            g_params = tuple(g[n].contiguous() if need else None
+                             for n, need in zip(param_names(ctx.net, ctx.mode), ctx.needs_input_grad[4:]))
+        return (g_enc.reshape(N, S, 32) if ctx.needs_input_grad[0] else None, g_v, None, None) + g_params
+
+
+def field_train_encoded(net, mode, grid, rays_o, rays_d, viewdirs, z):
+    """Train-mode field of a network behind an xyz encoder (ops.HashGrid): pts = o + d z (rendering.py:114,142) -> grid(pts) ->
+    FieldTrainEncoded.  Gradients reach the network's parameters, the grid's table (if it requires grad) and the rays (through
+    nefes_hashgrid_bwd_x) in one backward."""
+    pts = rays_o[:, None, :] + rays_d[:, None, :] * z[..., None]
+    sd = dict(net.named_parameters())
+    return FieldTrainEncoded.apply(grid(pts), viewdirs, net, mode, *[sd[n] for n in param_names(net, mode)])
