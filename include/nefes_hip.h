@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define NEFES_ABI_VERSION 15
+#define NEFES_ABI_VERSION 16
 
 #define NEFES_E_BADARG (-1)     /* null pointer / non-positive size */
 #define NEFES_E_UNSUPPORTED (-2) /* width / feat_dim / sample count outside the compiled set */
@@ -291,6 +291,38 @@ int nefes_feat_head_bwd(int N, int C, int F, const float* g_feat, const float* w
 int nefes_field_bwd_static_h3(const NefesNetDesc* desc, const void* packed, int N, int S, const float* rays_o, const float* rays_d,
                               const float* z, const float* pts, const float* viewdirs, const float* raw_t, const float* g_raw_t,
                               const uint32_t* masks, float* g_pts, float* g_viewdirs_s, void* stream);
+
+/* ---- generic field kernels: any --netwidth / --netdepth (script/models/options.py:30-31, nerfh_nff.py:452-478,640-662) ----
+ * The calls above serve the tuned instances (depth 8, skip at layer 5, widths 128 / 256).  These serve every other shape on one
+ * pair of untuned kernels (nefes_amd/csrc/field_generic.hip): strict fp32 on v_mfma_f32_32x32x2_f32, shape as run-time arguments,
+ * frequency embedding (63 / 27 features) computed in the kernel, frozen weights (backward to the inputs only).
+ * width: a multiple of 32 in 32..512; depth 1..8; skip: index (0-based, 1 <= skip < depth) of the layer that takes
+ * [embedding, h] (the reference's skips=[4] when depth > 4), or -1; 0 < feat_dim <= 141.  NEFES_E_UNSUPPORTED otherwise. */
+typedef struct NefesGenericNetDesc {
+    int32_t width;
+    int32_t depth;
+    int32_t skip;
+    int32_t feat_dim;
+    int32_t has_transient;
+} NefesGenericNetDesc;
+/* bytes of the packed blob; 0 for an unsupported description */
+size_t nefes_generic_blob_bytes(const NefesGenericNetDesc* desc);
+/* Host-side packing: `tensors` as for nefes_pack_weights with xyz_encoding_1..depth in front (2 * (depth + 4) pointers, 2 * (depth + 10)
+ * with the transient head).  Blob = per layer (xyz_encoding_1..depth, final, static_sigma, dir_encoding, static_rgb [, transient_encoding
+ * .0/.2/.4, transient rgb|sigma|beta as one 5-row layer]) three plain fp32 arrays back to back: wt[Kp][Mp] (transposed), wb[Mp][Kp],
+ * bias[Mp]; Mp = outputs rounded up to 32, Kp = inputs with a 63-feature embedding padded to 64 and a 27-feature one to 32 (zeros). */
+int nefes_generic_pack(const NefesGenericNetDesc* desc, const float* const* tensors, int n_tensors, void* blob, size_t blob_bytes);
+/* ReLU mask words of M samples: uint32 [tiles][words][64 lanes], tiles of 64 samples (32 above width 256); 0 = unsupported */
+size_t nefes_generic_mask_bytes(const NefesGenericNetDesc* desc, int64_t M);
+/* nefes_field_fwd's arguments and raw_t layout (no external encoding); masks nullable (needed by the backward). */
+int nefes_field_fwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
+                            const float* rays_d, const float* z, const float* pts, const float* viewdirs, float* raw_t,
+                            uint32_t* masks, void* stream);
+/* backward of a NEFES_FIELD_FULL or NEFES_FIELD_STATIC forward (`mode`) to g_pts [M,3] and g_viewdirs_s [M,3] (per sample: feed
+ * nefes_ray_grad_reduce). */
+int nefes_field_bwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
+                            const float* rays_d, const float* z, const float* pts, const float* viewdirs, const float* raw_t,
+                            const float* g_raw_t, const uint32_t* masks, float* g_pts, float* g_viewdirs_s, void* stream);
 
 /* ---- train mode: weight gradients (script/run_nefes.py:42-108 `loss.backward()` through models/nerfh_nff.py:525-576) ----
  * Buffers `acts` / `dacts`: fp32 [n_tiles = ceil(N*S/128)][rows x 128 samples], rows = nefes_train_rows(desc); inside a tile

@@ -9,7 +9,7 @@ import torch
 from nefes_amd import lib as _L
 from nefes_amd import ops as _ops
 from nefes_amd.field import (FEATURE_DIM, ExposureMLP, FusionNet, NeRFH_NFF, get_embedder,  # noqa: F401
-                             run_network_NeRFH_NFF)
+                             run_network_NeRFH_NFF, strip_module_prefix)
 
 APPLY_HISTOGRAM = True
 img2mse = lambda x, y: torch.mean((x - y) ** 2)
@@ -82,9 +82,9 @@ def create_nerf(args):
         print('Reloading from', ckpts[-1])
         ckpt = torch.load(ckpts[-1], map_location=device)
         start = ckpt['global_step']
-        model.load_state_dict(ckpt['network_fn_state_dict'], strict=False)
+        model.load_state_dict(strip_module_prefix(ckpt['network_fn_state_dict']), strict=False)
         if model_fine is not None:
-            model_fine.load_state_dict(ckpt['network_fine_state_dict'])
+            model_fine.load_state_dict(strip_module_prefix(ckpt['network_fine_state_dict']))
     render_kwargs_train = {'network_query_fn': network_query_fn, 'perturb': args.perturb, 'N_importance': args.N_importance,
                            'N_samples': args.N_samples, 'network_fn': model, 'use_viewdirs': args.use_viewdirs,
                            'white_bkgd': args.white_bkgd, 'raw_noise_std': args.raw_noise_std, 'test_time': False,

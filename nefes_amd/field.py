@@ -202,6 +202,8 @@ class NeRFH_NFF(nn.Module):
             self.sigmoid = nn.Sigmoid()
         self._pk = None
         self._pk_key = None
+        self._pk_gen = None
+        self._pk_gen_key = None
 
     # -- the HIP path ---------------------------------------------------------------------------
     def _supported(self):
@@ -244,12 +246,70 @@ class NeRFH_NFF(nn.Module):
                 g[name] = torch.cat([g[name][:, :at + have], g[name][:, at + want:]], 1)
         return g
 
+    def _generic_supported(self):
+        """The generic kernels (csrc/field_generic.hip) serve this network: any width that is a multiple of 32 up to 512, depth 1..8 with
+        the reference's skips=[4] (a no-op when D <= 4), the frequency embeddings or a prefix of them, a feature head."""
+        return (ops.generic_shape_ok(self.W, self.D, self.skips, self.W_features) and self.out_ch_size != 3
+                and self.in_channels_xyz in range(3, 64, 6) and self.in_channels_dir in range(3, 28, 6))
+
+    def _shape(self):
+        return (f"D={self.D}, skips={self.skips}, W={self.W}, f_dim={self.W_features}, in_channels_xyz={self.in_channels_xyz}, "
+                f"in_channels_dir={self.in_channels_dir}")
+
+    def _generic_embedding_columns(self):
+        """_embedding_columns for any depth: the layers that read an embedding shorter than the kernels' 63 / 27 features."""
+        ex, ed, W = self.in_channels_xyz, self.in_channels_dir, self.W
+        cols = []
+        if ex < 63:
+            cols += [(f"xyz_encoding_{i + 1}.0.weight", 0, ex, 63) for i in range(self.D) if i == 0 or i in self.skips]
+        if ed < 27:
+            cols += [("dir_encoding.0.weight", W, ed, 27)]
+            if self.encode_transient:
+                cols += [("transient_encoding.0.weight", W, ed, 27)]
+        return cols
+
+    def packed_generic(self) -> ops.PackedGeneric:
+        """The network packed for the generic kernels; cached and invalidated like packed().  Frozen weights only."""
+        if not self._generic_supported():
+            raise RuntimeError(f"nefes_amd: no field kernel serves {self._shape()}.  Compiled: {ops.COMPILED_SET}")
+        names = ops.PackedGeneric.layer_names(self.D, self.encode_transient)
+        sd = dict(self.named_parameters())
+        prm = [sd[n + s] for n in names for s in (".weight", ".bias")]
+        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in prm)
+        if self._pk_gen is None or key != self._pk_gen_key:
+            dev = prm[0].device if prm[0].is_cuda else torch.device("cuda")
+            ksd = {n: p.detach() for n, p in sd.items()}
+            for name, at, have, want in self._generic_embedding_columns():
+                w = ksd[name]
+                ksd[name] = torch.cat([w[:, :at + have], w.new_zeros(w.shape[0], want - have), w[:, at + have:]], 1)
+            skip = 4 if (4 in self.skips and self.D > 4) else -1
+            self._pk_gen = ops.PackedGeneric(ksd, self.W, self.D, skip, self.W_features, self.encode_transient, dev)
+            self._pk_gen_key = key
+        return self._pk_gen
+
+    def uses_generic(self):
+        """The routing decision: True when renders of this network take the generic kernels -- the tuned instances do not serve it, or
+        NEFES_FIELD_GENERIC=1 asks for the comparison."""
+        if self._supported() and not (ops.FIELD_GENERIC and self._generic_supported()):
+            return False
+        return True
+
+    def packed_any(self):
+        """What the callers (render, refine, run_network_NeRFH_NFF) hand the kernels: the tuned pack where an instance serves this
+        network, the generic one otherwise."""
+        return self.packed_generic() if self.uses_generic() else self.packed()
+
+    def require_frozen_for_generic(self, what):
+        raise NotImplementedError(f"nefes_amd: {what} is not built for the generic field kernels ({self._shape()}); they serve frozen "
+                                  f"weights with the frequency embedding only.  Tuned instances: {ops.COMPILED_SET}")
+
     def invalidate_packed(self):
         """Force a re-pack on the next render.  The cache key is (data_ptr, _version, device) per parameter, which sees
         optimizer steps, load_state_dict and no_grad in-place ops on the parameter itself -- but NOT edits made through
         `.data` (`p.data.mul_()`, `p.data.copy_()`, EMA / clipping code): those leave both unchanged.  Call this after
         such an edit (a captured PoseRefiner graph must be re-captured as well)."""
         self._pk_key = None
+        self._pk_gen_key = None
 
     def packed(self) -> ops.PackedField:
         """Fragment streams for the fused kernels; re-packed when any path parameter changes (see invalidate_packed for
@@ -288,7 +348,7 @@ class NeRFH_NFF(nn.Module):
     def factored_head_ok(self):
         """The factored-head kernels apply (csrc/field_fwd_h3.hip FH): a FROZEN fine network of width 128 on the frequency embedding whose
         rgb+feature head has more channels than g = relu(dir_encoding) has features (+ the ones channel), on the fp16 two-part pipe."""
-        return (ops.FACTORED_HEAD and self.encode_transient and self.W == 128 and self.in_channels_xyz != 32 and self._supported()
+        return (ops.FACTORED_HEAD and not ops.FIELD_GENERIC and self.encode_transient and self.W == 128 and self.in_channels_xyz != 32 and self._supported()
                 and 3 + self.W_features > 3 + self.W // 2 + 1 and ops.SPLIT == "h3"
                 and not any(p.requires_grad for n, p in self.named_parameters()
                             if not n.startswith(("fusion_net", "exposure_embedding"))))
@@ -363,7 +423,7 @@ def run_network_NeRFH_NFF(inputs, viewdirs, ts, fn, embed_fn=None, embeddirs_fn=
     """Reference signature (nerfh_nff.py:168-170).  inputs [N,S,3], viewdirs [N,3] -> raw [N,S,R].
     The embedders and `netchunk` are accepted for compatibility; the fused kernel embeds in-register and
     tiles internally.  The result is a permuted view of the kernel's channel-major raw_t [N,R,S]."""
-    pk = fn.packed()
+    pk = fn.packed_any()
     if typ == 'coarse' and test_time:
         mode = L.FIELD_SIGMA
     elif typ == 'coarse' or not output_transient:
@@ -371,8 +431,16 @@ def run_network_NeRFH_NFF(inputs, viewdirs, ts, fn, embed_fn=None, embeddirs_fn=
     else:
         mode = L.FIELD_FULL
     dev = pk.blob.device
-    raw_t = ops.FieldFromPoints.apply(inputs.to(dev), None if viewdirs is None else viewdirs.to(dev), pk, mode)
+    raw_t = ops.field_from_points(inputs.to(dev), None if viewdirs is None else viewdirs.to(dev), pk, mode)
     return raw_t.permute(0, 2, 1)
+
+
+def strip_module_prefix(state_dict):
+    """A checkpoint saved from a torch.nn.DataParallel / DistributedDataParallel wrapper (the reference under --multi_gpu,
+    run_nefes.py:378-382) carries `module.` in front of every key; the bare module's names come back."""
+    if state_dict and all(k.startswith("module.") for k in state_dict):
+        return {k[len("module."):]: v for k, v in state_dict.items()}
+    return state_dict
 
 
 class _Embedder:

@@ -18,6 +18,10 @@ class NefesNetDesc(C.Structure):
     _fields_ = [("width", C.c_int32), ("feat_dim", C.c_int32), ("has_transient", C.c_int32), ("xyz_encoding", C.c_int32)]
 
 
+class NefesGenericNetDesc(C.Structure):
+    _fields_ = [("width", C.c_int32), ("depth", C.c_int32), ("skip", C.c_int32), ("feat_dim", C.c_int32), ("has_transient", C.c_int32)]
+
+
 class NefesStreamInfo(C.Structure):
     _fields_ = [("slab_off", C.c_uint64), ("n_slabs", C.c_uint32), ("bias_floats", C.c_uint32), ("bias_off", C.c_uint64),
                 ("scale_off", C.c_uint32), ("scale_count", C.c_uint32)]
@@ -32,7 +36,7 @@ class NefesHashGridDesc(C.Structure):
                 ("base_resolution", C.c_int32), ("per_level_scale", C.c_float), ("bound", C.c_float)]
 
 
-ABI_VERSION = 15       # NEFES_ABI_VERSION of include/nefes_hip.h
+ABI_VERSION = 16       # NEFES_ABI_VERSION of include/nefes_hip.h
 STREAM_FWD_SIGMA, STREAM_FWD_STATIC, STREAM_FWD_FULL, STREAM_BWD_FULL, STREAM_FWD_SIGMA_X6, STREAM_FWD_FULL_X6, STREAM_BWD_FULL_X6, STREAM_BWD_STATIC = 0, 1, 2, 3, 4, 5, 6, 7
 STREAM_FWD_SIGMA_H3, STREAM_FWD_FULL_H3, STREAM_BWD_FULL_H3, STREAM_FWD_STATIC_H3, STREAM_BWD_STATIC_H3 = 8, 9, 10, 11, 12
 FIELD_SIGMA, FIELD_STATIC, FIELD_FULL = 0, 1, 2
@@ -43,6 +47,7 @@ COMP_TRANSIENT, COMP_STATIC_ONLY, COMP_SIGMA_ONLY, COMP_WHITE_BKGD, COMP_FEAT_WE
 
 _p, _i, _f, _u32, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.c_size_t
 _desc = C.POINTER(NefesNetDesc)
+_gdesc = C.POINTER(NefesGenericNetDesc)
 
 # name -> (restype, argtypes); mirrors include/nefes_hip.h declaration by declaration
 SIGNATURES = {
@@ -108,6 +113,11 @@ SIGNATURES = {
     "nefes_probe_pk_mul": (_i, [_p, C.c_int64, _i, _p]),
     "nefes_probe_hazard": (_i, [_i, _i, _i, _i, _p, _p]),
     "nefes_probe_aggressor": (_i, [_i, _i, _i, _p, _p]),
+    "nefes_generic_blob_bytes": (_sz, [_gdesc]),
+    "nefes_generic_pack": (_i, [_gdesc, C.POINTER(_p), _i, _p, _sz]),
+    "nefes_generic_mask_bytes": (_sz, [_gdesc, C.c_int64]),
+    "nefes_field_fwd_generic": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_field_bwd_generic": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_train_rows": (_sz, [_desc]),
     "nefes_train_row_offset": (_i, [_desc, _i]),
     "nefes_field_fwd_train": (_i, [_desc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
@@ -158,6 +168,9 @@ def load():
 COMPILED_SET = ("fp16 two-part instances (default): widths 128 / 256 x feature heads of 0..29 or 30..141 channels with the frequency "
                 "embedding, width 256 x 0..29 channels with an external 32-feature embedding; bf16x6 and fp32-MFMA instances "
                 "(NEFES_SPLIT=x6 / f32): width 256 x 16 channels and width 128 x 128 channels only")
+GENERIC_SET = ("generic fp32-MFMA kernels (frozen weights, frequency embedding): any width that is a multiple of 32 from 32 to 512, "
+               "depth 1..8 with skips=[4] (or none when depth <= 4), feature heads of 1..141 channels")
+COMPILED_SET += ".  Other shapes (NeRFH_NFF.packed_generic): " + GENERIC_SET
 
 
 def check(rc, what):

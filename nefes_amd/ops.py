@@ -723,6 +723,167 @@ class FieldFromPoints(torch.autograd.Function):
         return g_pts.reshape(N, S, 3), g_v, None, None
 
 
+# ---------------------------------------------------------------------------------------------
+# generic field kernels (csrc/field_generic.hip): any --netwidth / --netdepth, frozen weights
+# ---------------------------------------------------------------------------------------------
+# "1": networks the tuned instances DO serve run on the generic kernels too (off by default; so that the two can be compared on
+# the same weights).  Networks the tuned instances do not serve always take the generic kernels.
+FIELD_GENERIC = os.environ.get("NEFES_FIELD_GENERIC", "0") == "1"
+GENERIC_SET = L.GENERIC_SET
+
+
+def generic_shape_ok(width, depth, skips, feat_dim):
+    """csrc/field_generic.hip gen_desc_ok with the reference's skip rule (nerfh_nff.py:469-477,549-553: skips=[4] acts when D > 4)."""
+    skips = [s for s in skips if 0 <= s < depth]
+    return (width % 32 == 0 and 32 <= width <= 512 and 1 <= depth <= 8 and skips in ([], [4])
+            and 0 < feat_dim <= HEAD_MAX_C)
+
+
+class PackedGeneric:
+    """Device-resident weights of one NeRFH_NFF network in the generic kernels' layout (nefes_generic_pack): per layer the matrix
+    transposed, the matrix, the bias -- plain padded fp32.  Frozen weights only: no device re-pack."""
+
+    generic = True
+    h3_valid = False             # (never on the fp16 two-part instances: fused_coarse_pass_ok and friends say no)
+    xyz_encoding = L.XYZ_FREQ10
+
+    @staticmethod
+    def layer_names(depth, has_transient):
+        names = [f"xyz_encoding_{i}.0" for i in range(1, depth + 1)] + ["xyz_encoding_final", "dir_encoding.0", "static_sigma.0", "static_rgb.0"]
+        if has_transient:
+            names += PackedField.LAYERS_FINE[len(PackedField.LAYERS_COARSE):]
+        return names
+
+    def __init__(self, state_dict, width, depth, skip, feat_dim, has_transient, device):
+        lib = L.load()
+        self.desc = L.NefesGenericNetDesc(int(width), int(depth), int(skip), int(feat_dim), 1 if has_transient else 0)
+        self.width, self.depth, self.skip = int(width), int(depth), int(skip)
+        self.feat_dim, self.has_transient = int(feat_dim), bool(has_transient)
+        n = int(lib.nefes_generic_blob_bytes(self.desc))
+        if n == 0:
+            raise RuntimeError(f"nefes_amd: no field kernel serves W={width}, D={depth}, skip={skip}, f_dim={feat_dim}.  "
+                               f"Compiled: {COMPILED_SET}")
+        host = []
+        for name in self.layer_names(self.depth, self.has_transient):
+            host.append(state_dict[name + ".weight"].detach().to("cpu", torch.float32).contiguous())
+            host.append(state_dict[name + ".bias"].detach().to("cpu", torch.float32).contiguous())
+        ptrs = (C.c_void_p * len(host))(*[t.data_ptr() for t in host])
+        blob = torch.zeros(n, dtype=torch.uint8)
+        L.check(lib.nefes_generic_pack(self.desc, ptrs, len(host), C.c_void_p(blob.data_ptr()), blob.numel()), "nefes_generic_pack")
+        self.blob = blob.to(device)
+        self.generation = 0
+        self.tile = 64 if self.width <= 256 else 32
+
+    def check_generation(self, gen):
+        if gen != self.generation:
+            raise RuntimeError("nefes_amd: the network weights were re-packed between this forward pass and its backward pass")
+
+    def mask_bytes(self, M):
+        return L.load().nefes_generic_mask_bytes(self.desc, M)
+
+    def n_raw(self, mode):
+        return 1 if mode == L.FIELD_SIGMA else (3 + self.feat_dim + (1 if mode == L.FIELD_STATIC else 6))
+
+
+def is_generic(pk):
+    return bool(getattr(pk, "generic", False))
+
+
+def field_fwd_generic(pk: PackedGeneric, mode, N, S, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, want_masks=False):
+    dev = pk.blob.device
+    raw_t = torch.empty(N, pk.n_raw(mode), S, device=dev)
+    masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=dev) if want_masks else None
+    with _timed(f"field_fwd[{('sigma', 'static', 'full')[mode]},generic]"):
+        L.check(L.load().nefes_field_fwd_generic(pk.desc, _chk(pk.blob, "blob", torch.uint8), mode, N, S, _chk(rays_o, "rays_o"),
+                                                 _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
+                                                 _chk(raw_t, "raw_t"), _chk(masks, "masks", torch.int32), _stream()),
+                "nefes_field_fwd_generic")
+    if masks is not None:
+        _tap("masks_generic", (masks, N, S, pk, mode))
+    return raw_t, masks
+
+
+def field_bwd_generic(pk: PackedGeneric, mode, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None):
+    dev = pk.blob.device
+    g_pts, g_vs = torch.empty(N * S, 3, device=dev), torch.empty(N * S, 3, device=dev)
+    with _timed(f"field_bwd[{('sigma', 'static', 'full')[mode]},generic]"):
+        L.check(L.load().nefes_field_bwd_generic(pk.desc, _chk(pk.blob, "blob", torch.uint8), mode, N, S, _chk(rays_o, "rays_o"),
+                                                 _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
+                                                 _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32),
+                                                 _chk(g_pts, "g_pts"), _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_generic")
+    return g_pts, g_vs
+
+
+class FieldFromRaysGeneric(torch.autograd.Function):
+    """FieldFromRays on the generic kernels: same arguments, same raw_t [N, R, S]; differentiable w.r.t. rays_o, rays_d, viewdirs in
+    FULL and STATIC mode (frozen weights)."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, viewdirs, z, pk, mode):
+        rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
+        N, S = z.shape
+        need = mode in (L.FIELD_FULL, L.FIELD_STATIC) and any(ctx.needs_input_grad[:3])
+        raw_t, masks = field_fwd_generic(pk, mode, N, S, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs, want_masks=need)
+        ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
+        if need:
+            ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks)
+        return raw_t
+
+    @staticmethod
+    def backward(ctx, g_raw_t):
+        if not ctx.have:
+            raise NotImplementedError("nefes_amd: the sigma-only field pass has no backward (the reference evaluates it "
+                                      "without gradients at test time: nerfh_nff.py:192-202)")
+        rays_o, rays_d, viewdirs, z, raw_t, masks = ctx.saved_tensors
+        N, S = z.shape
+        ctx.pk.check_generation(ctx.pk_gen)
+        g_pts, g_vs = field_bwd_generic(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, rays_o=rays_o, rays_d=rays_d, z=z,
+                                        viewdirs=viewdirs)
+        g_o, g_d, g_v = ray_grad_reduce(N, S, z, g_pts, g_vs)
+        return g_o, g_d, g_v, None, None, None
+
+
+class FieldFromPointsGeneric(torch.autograd.Function):
+    """FieldFromPoints on the generic kernels."""
+
+    @staticmethod
+    def forward(ctx, pts, viewdirs, pk, mode):
+        pts = _f32(pts)
+        N, S = pts.shape[0], pts.shape[1]
+        if viewdirs is None:
+            viewdirs = torch.zeros(N, 3, device=pts.device)
+        viewdirs = _f32(viewdirs)
+        need = mode in (L.FIELD_FULL, L.FIELD_STATIC) and any(ctx.needs_input_grad[:2])
+        raw_t, masks = field_fwd_generic(pk, mode, N, S, pts=pts.reshape(-1, 3), viewdirs=viewdirs, want_masks=need)
+        ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
+        if need:
+            ctx.save_for_backward(pts, viewdirs, raw_t, masks)
+        return raw_t
+
+    @staticmethod
+    def backward(ctx, g_raw_t):
+        if not ctx.have:
+            raise NotImplementedError("nefes_amd: the sigma-only field pass has no backward (nerfh_nff.py:192-202 runs it without gradients)")
+        pts, viewdirs, raw_t, masks = ctx.saved_tensors
+        N, S = pts.shape[0], pts.shape[1]
+        ctx.pk.check_generation(ctx.pk_gen)
+        g_pts, g_vs = field_bwd_generic(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, pts=pts.reshape(-1, 3), viewdirs=viewdirs)
+        zeros = torch.zeros(N, S, device=pts.device)
+        _, _, g_v = ray_grad_reduce(N, S, zeros, g_pts, g_vs)
+        return g_pts.reshape(N, S, 3), g_v, None, None
+
+
+def field_from_rays(rays_o, rays_d, viewdirs, z, pk, mode):
+    """The field along rays on whichever kernels `pk` was packed for (NeRFH_NFF.packed_any)."""
+    fn = FieldFromRaysGeneric if is_generic(pk) else FieldFromRays
+    return fn.apply(rays_o, rays_d, viewdirs, z, pk, mode)
+
+
+def field_from_points(pts, viewdirs, pk, mode):
+    fn = FieldFromPointsGeneric if is_generic(pk) else FieldFromPoints
+    return fn.apply(pts, viewdirs, pk, mode)
+
+
 class FieldFromEncoding(torch.autograd.Function):
     """Field MLP on a caller-supplied 32-feature xyz embedding (hash grid, BASELINE config 4): enc [N,S,32], viewdirs [N,3]
     -> raw_t [N,R,S]; backward to enc and viewdirs."""

@@ -545,7 +545,7 @@ def _apr_kernels_bit_stable(r, photo, feature_target, hist, trials=6):
     from . import lib as L
     dev = r.dev
     fine = r.kw["network_fine"]
-    pk = fine.packed()
+    pk = fine.packed_any()
     g = torch.Generator().manual_seed(5)
     N, S = 4800, 128
     ro = (torch.randn(N, 3, generator=g) * 0.1).to(dev)
@@ -561,7 +561,7 @@ def _apr_kernels_bit_stable(r, photo, feature_target, hist, trials=6):
         if storm:
             with torch.cuda.stream(side), torch.no_grad():
                 for _ in range(8):                         # ~5 ms of field kernels: longer than the sequence under test
-                    keep.append(ops.FieldFromRays.apply(ro, rd, rd, z, pk, L.FIELD_FULL))
+                    keep.append(ops.field_from_rays(ro, rd, rd, z, pk, L.FIELD_FULL))
         r._apr_iteration()
         r._apr_iteration()
         ps, ss = r._verification(as_tensors=True)

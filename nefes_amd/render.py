@@ -112,7 +112,10 @@ def _grid_trainable(xyz_encoder):
 def _field(pk, mode, rays_o, rays_d, viewdirs, z, xyz_encoder):
     """raw_t [N,R,S] for samples z along the rays; differentiable w.r.t. rays_o, rays_d, viewdirs in FULL mode."""
     if xyz_encoder is None:
-        return ops.FieldFromRays.apply(rays_o, rays_d, viewdirs, z, pk, mode)
+        return ops.field_from_rays(rays_o, rays_d, viewdirs, z, pk, mode)
+    if ops.is_generic(pk):
+        raise NotImplementedError(f"nefes_amd: an external / hash-grid encoding is not built for the generic field kernels "
+                                  f"(W={pk.width}, D={pk.depth}, f_dim={pk.feat_dim})")
     if (mode != L.FIELD_STATIC and ops.hashgrid_fused_ok(pk, xyz_encoder) and z.shape[0] * z.shape[1] < (1 << 31) - 256
             and not _grid_trainable(xyz_encoder)):
         # (a trainable table takes the separate launches below: they hand HashGridEncode the gradient of the encoding)
@@ -138,13 +141,15 @@ def _render_core(rays_o, rays_d, viewdirs, near, far, network_fn, network_fine, 
         # inference instances, so it runs on the train-mode ones too (without the weight gradients); the full head does (_field)
         grid_static = mode == L.FIELD_STATIC and _grid_trainable(cfg.xyz_encoder)
         if (trainable(net) or grid_static) and mode != L.FIELD_SIGMA:
+            if ops.is_generic(pk):
+                net.require_frozen_for_generic("train mode (weight gradients)")
             from . import train as T
             if cfg.xyz_encoder is not None:
                 return T.field_train_encoded(net, mode, cfg.xyz_encoder, rays_o, rays_d, viewdirs, z_)
             return T.field_train(net, mode, rays_o, rays_d, viewdirs, z_)
         return _field(pk, mode, rays_o, rays_d, viewdirs, z_, cfg.xyz_encoder)
 
-    pk_c = network_fn.packed()
+    pk_c = network_fn.packed_any()
     C = pk_c.feat_dim
     store_rgb = (Ni == 0)
     if (cfg.test_time and cfg.perturb == 0. and cfg.raw_noise_std == 0. and bounds is None
@@ -224,7 +229,7 @@ def _fine_pass(rays_o, rays_d, viewdirs, z_fine, z_samples, network_fine, cfg, C
         if cfg.feat_as_gmap:
             ret["feat_is_gmap"] = True
         return ret
-    pk_f = network_fine.packed()
+    pk_f = network_fine.packed_any()
     mode = L.FIELD_FULL if cfg.NeRFW else L.FIELD_STATIC
     raw_f = field(network_fine, pk_f, mode, z_f)
     if cfg.raw_noise_std > 0. and not cfg.NeRFW:
