@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define NEFES_ABI_VERSION 16
+#define NEFES_ABI_VERSION 17
 
 #define NEFES_E_BADARG (-1)     /* null pointer / non-positive size */
 #define NEFES_E_UNSUPPORTED (-2) /* width / feat_dim / sample count outside the compiled set */
@@ -40,6 +40,11 @@ typedef struct NefesNetDesc {
     int32_t has_transient; /* 1 for the 'fine' net (encode_transient), 0 for 'coarse' */
     int32_t xyz_encoding;  /* NEFES_XYZ_FREQ10: 63 frequency features computed in-kernel from the sample position;
                             * NEFES_XYZ_EXTERNAL32: 32 features supplied per sample (xyz_enc), e.g. nefes_hashgrid_fwd */
+    int32_t fold_final;    /* 0: every layer packed as it is.  1 (frozen networks): xyz_encoding_final, a Linear with no activation behind
+                            * it, is multiplied into its two consumers by the packer -- the fp16 two-part full / static streams carry
+                            * W_head[:, :W] W_final and W_head[:, :W] b_final + b_head in dir_encoding's (and transient_encoding.0's)
+                            * place and no segment for xyz_encoding_final (csrc/layout.h NEFES_H3FF_* / NEFES_H3BF_*).  Every other
+                            * stream is the same as with 0.  Such a blob cannot be refreshed by nefes_pack_device. */
 } NefesNetDesc;
 #define NEFES_XYZ_FREQ10 0
 #define NEFES_XYZ_EXTERNAL32 1

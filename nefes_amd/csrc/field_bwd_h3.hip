@@ -17,7 +17,7 @@
 // runs -- behind an MFMA that has not written them yet.  So the three embedding-gradient tiles are consumed
 // where they are produced (below), layer 5's two extra output tiles live in VGPRs for the length of that run, and
 // tests/test_pack_stream.py disassembles the library and fails if a v_accvgpr_mov shows up in these kernels.
-#if !defined(NEFES_TU_PART) || NEFES_TU_PART == 0 || NEFES_TU_PART == 1 || NEFES_TU_PART == 5
+#if !defined(NEFES_TU_PART) || NEFES_TU_PART == 0 || NEFES_TU_PART == 1 || NEFES_TU_PART == 5 || NEFES_TU_PART == 9 || NEFES_TU_PART == 11
 #define H3B_WIDE
 #define H3_ACC_READ_ASM        // source tiles are read out of their AGPRs inside the MFMA gaps (field_h3.h acc_read)
 #define NEFES_ASM_READS_ACC    // ... by asm statements: compiler-placed runs end with field_common.h mfma_results_fence_tiles
@@ -121,8 +121,15 @@ __device__ __forceinline__ T ld_stream(const T* p) {
 // a run-time argument (a.C).  ENC = NEFES_XYZ_*
 // FH: the factored head of field_fwd_h3.hip -- the upstream gradient carries d loss / d g (g = relu(dir_encoding)) in raw channels
 // 3 .. 3 + W/2, which joins the 3-row colour head's transposed product in front of dir_encoding^T.
-template <int W, int KR16, int ENC, bool HAS_T = true, bool TRAIN = false, bool FH = false>
+// FOLD (NefesNetDesc.fold_final): the stream carries the packer's folded head matrices and no xyz_encoding_final^T segment -- the
+// transposed head products deliver d h8 (before layer 8's mask) themselves, static_sigma^T's k-step joins them, layer 8 follows.
+// The folded instances carry the flag in their head-class parameter (KRF = KR16 | NEFES_H3B_FOLD: the kernel keeps its template signature).
+#define NEFES_H3B_FOLD 16
+template <int W, int KRF, int ENC, bool HAS_T = true, bool TRAIN = false, bool FH = false>
 __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kernel(FieldBwdH3Args a) {
+    constexpr bool FOLD = (KRF & NEFES_H3B_FOLD) != 0;
+    constexpr int KR16 = KRF & ~NEFES_H3B_FOLD;
+    static_assert(!FOLD || (!TRAIN && !FH), "the fold serves frozen networks with their own feature head");
     constexpr int NTW = W / 32, NTH = W / 64, HS = W / 2, GS = W / 4;
     constexpr int MW = 8 * (W / 64) + 4 * (W / 128);
     constexpr int WT = (NTW + 1) / 2, WH = (NTH + 1) / 2;   // mask words per trunk / half-width layer
@@ -147,13 +154,13 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
     constexpr int SX = ENC == NEFES_XYZ_HASHGRID_FUSED ? 24 : 8;
     int* tab_i = (int*)(smem + NEFES_H3B_SLOTS * NEFES_SLAB_BYTES + (size_t)4 * (MW + SX) * 256);
     const float* tab_f = (const float*)tab_i;
-    if (threadIdx.x < 2 * (HAS_T ? NEFES_H3B_N : NEFES_H3B_N_STATIC)) tab_i[threadIdx.x] = a.tab[threadIdx.x];
+    if (threadIdx.x < 2 * ((HAS_T ? NEFES_H3B_N : NEFES_H3B_N_STATIC) - (FOLD ? 1 : 0))) tab_i[threadIdx.x] = a.tab[threadIdx.x];
     HgGeom* hg_lds = (HgGeom*)(tab_i + 64);                     // NEFES_XYZ_HASHGRID_FUSED: level geometry behind the scale table (see field_fwd_h3.hip)
     if constexpr (ENC == NEFES_XYZ_HASHGRID_FUSED) {
         if (threadIdx.x == 0) *hg_lds = a.hg;
     }
-    auto wexp = [&](int seg) { return tab_i[nefes_h3_tab_exp(nefes_h3b_seg(HAS_T, seg))]; };     // (segment ordinals of the full stream)
-    auto rowb = [&](int seg) { return tab_f[nefes_h3_tab_bound(nefes_h3b_seg(HAS_T, seg))]; };
+    auto wexp = [&](int seg) { return tab_i[nefes_h3_tab_exp(nefes_h3b_seg(HAS_T, nefes_h3b_fold_seg(FOLD, seg)))]; };     // (segment ordinals of the full, unfolded stream)
+    auto rowb = [&](int seg) { return tab_f[nefes_h3_tab_bound(nefes_h3b_seg(HAS_T, nefes_h3b_fold_seg(FOLD, seg)))]; };
     StagedRing ring;
     ring.init(a.stream, a.n_slabs, smem, wave, lane);
     const char* ring_lane = smem + lane * 16;
@@ -432,10 +439,28 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
 #pragma unroll
                 for (int c = 0; c < 3; ++c) STASH(3 + c) = gv[c];
             }
+            // FOLD: the tile's consumption is pinned HERE -- the next product already is a full-width one reading the other eight tiles
+            // of this set, and with this tile's reads sunk behind it a seventeenth accumulator tile is alive in the asm-scheduled runs
+            if constexpr (FOLD) asm volatile("" : "+v"(gv[0]), "+v"(gv[1]), "+v"(gv[2]));
         }
         // ---- xyz_encoding_final^T (no ReLU on its output) + static_sigma^T (one extra fp32 k-step) -> d h8 ----
+        // XP holds d h8 and every second layer's output from there on, XQ the others.  FOLD: d h8 is what the head products left in XA
+        // (the packer's folded matrices), static_sigma^T accumulates onto it at that set's exponent, and the ping-pong is the other way round.
+        f32x16 (&XP)[NTW + 2] = FOLD ? XA : XB;
+        f32x16 (&XQ)[NTW + 2] = FOLD ? XB : XA;
         int es_b;
-        {
+        if constexpr (FOLD) {
+            es_b = es_dt;
+            const float dsig = STASH(6);
+            float dsg[1];
+            dsg[0] = dsig * pow2i(es_b);
+#if defined(H3B_WIDE) && defined(H3_WIDE_ENTRY_FENCE)
+            mma_run<NTW, 1, 2, false, ((WIDE_LAYERS >> 8) & 1) == 0 || (NTW < NEFES_H3_WIDE_MIN)>(ring, ring_lane, ArrayIn<1>{dsg}, ZeroInit{}, XA);
+#else
+            mma_run<NTW, 1, 2, false>(ring, ring_lane, ArrayIn<1>{dsg}, ZeroInit{}, XA);
+#endif
+            M += rowb(NEFES_H3B_SIG) * pair_max(fabsf(dsig));
+        } else {
             const int ew = wexp(NEFES_H3B_FINAL), tau = tau_of(M, ew);
             float mx = 0.f;
             es_b = tau + ew;
@@ -464,11 +489,11 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
             mma_run_h3<NTILES, W / 16, T0, true, 2, ((WIDE_LAYERS >> (L)) & 1) != 0>(ring, ring_lane, wrap_store_h3<TRAIN>(MaskedSplitH<NTW + 2, WT, 2>{SRC, bt, pow2i(tau - ES_SRC), mx}, gptr(NEFES_TB_L1 + (L) - 1), pow2i(-(ES_SRC))), ZeroInit{}, DST); \
             M = rowb(NEFES_H3B_L8 + 8 - (L)) * (pair_max(mx) * pow2i(-(ES_SRC)));                                   \
         }
-        NEFES_BWD_LAYER(8, XB, XA, es_b, es_a, NTW, 2)
-        NEFES_BWD_LAYER(7, XA, XB, es_a, es_b, NTW, 2)
-        NEFES_BWD_LAYER(6, XB, XA, es_b, es_a, NTW, 2)
-        NEFES_BWD_LAYER(5, XA, XB, es_a, es_b, NTW + 2, 0)
-        es_e = es_b;                                                         // exponent of the d xyz-embedding tiles XB[0], XB[1]
+        NEFES_BWD_LAYER(8, XP, XQ, es_b, es_a, NTW, 2)
+        NEFES_BWD_LAYER(7, XQ, XP, es_a, es_b, NTW, 2)
+        NEFES_BWD_LAYER(6, XP, XQ, es_b, es_a, NTW, 2)
+        NEFES_BWD_LAYER(5, XQ, XP, es_a, es_b, NTW + 2, 0)
+        es_e = es_b;                                                         // exponent of the d xyz-embedding tiles XP[0], XP[1]
         // the skip connection's share of d xyz-embedding (XB tiles 0, 1), consumed at once (see the d dir-embedding tile above)
         float gx[3] = {0.f, 0.f, 0.f};
         float ge[ENC != NEFES_XYZ_FREQ10 ? NEFES_X_STEPS : 1];
@@ -476,22 +501,22 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
             const float inv = pow2i(-es_e);
             if constexpr (ENC != NEFES_XYZ_FREQ10) {        // kept in registers until layer 1's share exists (see part 1's note below)
 #pragma unroll
-                for (int s_ = 0; s_ < NEFES_X_STEPS; ++s_) ge[s_] = XB[0][s_] * inv;
+                for (int s_ = 0; s_ < NEFES_X_STEPS; ++s_) ge[s_] = XP[0][s_] * inv;
             } else {
                 float dE[32], x3[3];
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) dE[t * 16 + r] = XB[t][r] * inv;
+                    for (int r = 0; r < 16; ++r) dE[t * 16 + r] = XP[t][r] * inv;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) x3[c] = STASH(c);
                 embed_slots_bwd<NEFES_N_FREQ_XYZ>(gx, dE, x3, h);
                 ge[0] = 0.f;
             }
         }
-        NEFES_BWD_LAYER(4, XB, XA, es_b, es_a, NTW, 2)
-        NEFES_BWD_LAYER(3, XA, XB, es_a, es_b, NTW, 2)
-        NEFES_BWD_LAYER(2, XB, XA, es_b, es_a, NTW, 2)
+        NEFES_BWD_LAYER(4, XP, XQ, es_b, es_a, NTW, 2)
+        NEFES_BWD_LAYER(3, XQ, XP, es_a, es_b, NTW, 2)
+        NEFES_BWD_LAYER(2, XP, XQ, es_b, es_a, NTW, 2)
 #undef NEFES_BWD_LAYER
         // ---- xyz_encoding_1^T -> layer 1's share of d xyz-embedding, into fresh tiles (the skip's share is already consumed) ----
         int es_1;
@@ -500,7 +525,7 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
             const int ew = wexp(NEFES_H3B_L1), tau = tau_of(M, ew);
             float mx = 0.f;
             es_1 = tau + ew;
-            mma_run_h3<2, W / 16, 0, true>(ring, ring_lane, wrap_store_h3<TRAIN>(MaskedSplitH<NTW + 2, WT, 2>{XA, bt, pow2i(tau - es_a), mx}, gptr(NEFES_TB_L1), pow2i(-es_a)), ZeroInit{}, XB);
+            mma_run_h3<2, W / 16, 0, true>(ring, ring_lane, wrap_store_h3<TRAIN>(MaskedSplitH<NTW + 2, WT, 2>{XQ, bt, pow2i(tau - es_a), mx}, gptr(NEFES_TB_L1), pow2i(-es_a)), ZeroInit{}, XP);
         }
         // ---- embedding backward (Embedder.embed :257-267): layer 1's share; the other two were taken where they were produced ----
         const float inv1 = pow2i(-es_1);
@@ -509,7 +534,7 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
             // neither written nor re-read by a separate gather launch; both lane halves return their eight levels' share
             float x3[3];
 #pragma unroll
-            for (int s_ = 0; s_ < NEFES_X_STEPS; ++s_) STASH(8 + s_) = ge[s_] + XB[0][s_] * inv1;
+            for (int s_ = 0; s_ < NEFES_X_STEPS; ++s_) STASH(8 + s_) = ge[s_] + XP[0][s_] * inv1;
 #pragma unroll
             for (int c = 0; c < 3; ++c) x3[c] = STASH(c);
             // the position passes through an opaque statement HERE: the cells, indices and table gathers depend on nothing but it, and
@@ -521,7 +546,7 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
             for (int c = 0; c < 3; ++c) gv[c] = STASH(3 + c);
         } else if constexpr (ENC == NEFES_XYZ_EXTERNAL32) {
 #pragma unroll
-            for (int s_ = 0; s_ < NEFES_X_STEPS; ++s_) ge[s_] += XB[0][s_] * inv1;
+            for (int s_ = 0; s_ < NEFES_X_STEPS; ++s_) ge[s_] += XP[0][s_] * inv1;
             if (valid) {
                 float* gp = a.g_enc + m * 32 + h;
 #pragma unroll
@@ -532,7 +557,7 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) dE[t * 16 + r] = XB[t][r] * inv1;
+                for (int r = 0; r < 16; ++r) dE[t * 16 + r] = XP[t][r] * inv1;
 #pragma unroll
             for (int c = 0; c < 3; ++c) x3[c] = STASH(c);
             embed_slots_bwd<NEFES_N_FREQ_XYZ>(g1, dE, x3, h);
@@ -574,8 +599,8 @@ static int launch_bwd_h3(const FieldBwdH3Args& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// Instances spread over nine objects built from this one source (Makefile: -DNEFES_TU_PART=0..8; even parts from 2 on are the
-// Wd = 128 objects): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instance, part 2 = Wd = 128 / class 1,
+// Instances spread over eleven objects built from this one source (Makefile: -DNEFES_TU_PART=0..9, 11; even parts from 2 on are the
+// Wd = 128 objects; parts 9 / 11 = the folded Wd = 256 instances of head class 0 / 1): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instance, part 2 = Wd = 128 / class 1,
 // parts 3 / 4 = their TRAIN instances, parts 5 / 6 = Wd = 256 / class 1 and Wd = 128 / class 0, parts 7 / 8 = their TRAIN instances.
 #ifndef NEFES_TU_PART
 #define NEFES_TU_PART 0
@@ -590,6 +615,8 @@ int nefes_bwd_h3_launch_part5(int which, const FieldBwdH3Args& a, hipStream_t st
 int nefes_bwd_h3_launch_part6(int which, const FieldBwdH3Args& a, hipStream_t st);   // Wd = 128, class 0
 int nefes_bwd_h3_launch_part7(int which, const FieldBwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 256, class 1
 int nefes_bwd_h3_launch_part8(int which, const FieldBwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 128, class 0
+int nefes_bwd_h3_launch_part9(int which, const FieldBwdH3Args& a, hipStream_t st);   // folded (FOLD) instance, Wd = 256, class 0
+int nefes_bwd_h3_launch_part11(int which, const FieldBwdH3Args& a, hipStream_t st);  // folded (FOLD) instance, Wd = 256, class 1
 
 #if NEFES_TU_PART == 1
 int nefes_bwd_h3_launch_part1(int which, const FieldBwdH3Args& a, hipStream_t st) {
@@ -647,6 +674,16 @@ int nefes_bwd_h3_launch_part8(int which, const FieldBwdH3Args& a, hipStream_t st
     if (which == BWD_H3_TRAIN_FULL) return launch_bwd_h3<128, 2, NEFES_XYZ_FREQ10, true, true>(a, st);
     return NEFES_E_UNSUPPORTED;
 }
+#elif NEFES_TU_PART == 9      // (gap-by-gap schedule, like part 0)
+int nefes_bwd_h3_launch_part9(int which, const FieldBwdH3Args& a, hipStream_t st) {
+    if (which == BWD_H3_FULL) return launch_bwd_h3<256, 2 | NEFES_H3B_FOLD, NEFES_XYZ_FREQ10>(a, st);
+    return NEFES_E_UNSUPPORTED;
+}
+#elif NEFES_TU_PART == 11     // (gap-by-gap schedule, like part 0)
+int nefes_bwd_h3_launch_part11(int which, const FieldBwdH3Args& a, hipStream_t st) {
+    if (which == BWD_H3_FULL) return launch_bwd_h3<256, 9 | NEFES_H3B_FOLD, NEFES_XYZ_FREQ10>(a, st);
+    return NEFES_E_UNSUPPORTED;
+}
 #else   // part 0
 
 // The fused dX chain of the train-mode backward on the fp16 pipe: as nefes_field_bwd_train (field_bwd.hip), same `dacts` rows.
@@ -662,6 +699,7 @@ extern "C" int nefes_field_bwd_train_h3(const NefesNetDesc* desc, const void* pa
     if (full && !desc->has_transient) return NEFES_E_UNSUPPORTED;
     const int cls = nefes_head_class(desc->feat_dim);
     if ((desc->width != 256 && desc->width != 128) || cls < 0 || desc->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;
+    if (desc->fold_final) return NEFES_E_UNSUPPORTED;               // (no folded instance reads this stream)
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
     if (rc) return rc;
@@ -695,6 +733,7 @@ extern "C" int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void
     const bool full = mode == NEFES_FIELD_FULL;
     if (full && !desc->has_transient) return NEFES_E_UNSUPPORTED;
     if (desc->width != 256 || nefes_head_class(desc->feat_dim) != 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
+    if (desc->fold_final) return NEFES_E_UNSUPPORTED;
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
     if (rc) return rc;
@@ -725,6 +764,7 @@ extern "C" int nefes_field_bwd_static_h3(const NefesNetDesc* desc, const void* p
     if (!pts && !(rays_o && rays_d && z)) return NEFES_E_BADARG;
     const int cls = nefes_head_class(desc->feat_dim);
     if ((desc->width != 256 && desc->width != 128) || cls < 0 || desc->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;
+    if (desc->fold_final) return NEFES_E_UNSUPPORTED;               // (no folded instance reads this stream)
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
     if (rc) return rc;
@@ -756,11 +796,14 @@ static int field_bwd_h3_impl(const NefesNetDesc* desc, const void* packed, int N
     const bool fused_grid = ext && table != nullptr;            // d pts through the hash grid inside the kernel (hashgrid.h)
     if (fused_grid ? !(g_pts && grid && rays_o && rays_d && z) : (ext ? !g_xyz_enc : (!g_pts || (!pts && !(rays_o && rays_d && z))))) return NEFES_E_BADARG;
     if (!desc->has_transient) return NEFES_E_UNSUPPORTED;
+    // a folded pack (NefesNetDesc.fold_final): folded instances exist at width 256 with the frequency embedding and the network's own head
+    const bool fold = desc->fold_final != 0;
+    if (fold && (desc->width != 256 || ext || fh)) return NEFES_E_UNSUPPORTED;
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
     if (rc) return rc;
     const NefesStreamInfo& si = info.stream[NEFES_STREAM_BWD_FULL_H3];
-    if (si.n_slabs == 0 || si.scale_count < 2 * NEFES_H3B_N) return NEFES_E_UNSUPPORTED;
+    if (si.n_slabs == 0 || si.scale_count < 2 * (uint32_t)(fold ? NEFES_H3BF_N : NEFES_H3B_N)) return NEFES_E_UNSUPPORTED;
     FieldBwdH3Args a;
     a.stream = (const char*)packed + si.slab_off;
     a.tab = (const int*)((const char*)packed + si.bias_off) + si.scale_off;
@@ -790,6 +833,7 @@ static int field_bwd_h3_impl(const NefesNetDesc* desc, const void* packed, int N
     if (fh) return nefes_bwd_h3_launch_part6(BWD_H3_FH, a, st);
     if (desc->width == 256 && fused_grid) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_HG, a, st) : NEFES_E_UNSUPPORTED;
     if (desc->width == 256 && ext) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_EXT, a, st) : NEFES_E_UNSUPPORTED;
+    if (desc->width == 256 && fold) return cls == 0 ? nefes_bwd_h3_launch_part9(BWD_H3_FULL, a, st) : nefes_bwd_h3_launch_part11(BWD_H3_FULL, a, st);
     if (desc->width == 256) return cls == 0 ? launch_bwd_h3<256, 2, NEFES_XYZ_FREQ10>(a, st) : nefes_bwd_h3_launch_part5(BWD_H3_FULL, a, st);
     if (desc->width == 128 && !ext) return cls == 1 ? nefes_bwd_h3_launch_part2(BWD_H3_FULL, a, st) : nefes_bwd_h3_launch_part6(BWD_H3_FULL, a, st);
     return NEFES_E_UNSUPPORTED;

@@ -92,13 +92,23 @@ __device__ __forceinline__ void train_save_h3(float* tile_base, uint32_t voff, i
 // whose head has more channels than g (the reference's default: 3 + 128 against 64) emits g itself -- W/2 channels + a channel of ones
 // (for b_f sum_s w_s) in the feature channels' place, the 3 colour channels from a 3-row head (head class 0) -- and the caller applies
 // W_f once per RAY to the composited g (nefes_amd/render.py).  44 of the head's 60 MFMAs per 32 samples and 63 of 137 raw channels go.
-template <int MODE, int ENC, int W = 256, int NTR = 1, bool TRAIN = false, bool FH = false>
+// FOLD (frozen networks, NefesNetDesc.fold_final): xyz_encoding_final is a Linear with no activation behind it, so the packer has
+// multiplied it into its two consumers (pack.cpp fold_head).  The stream has no FINAL segment; the trunk ends with layer 8 and the
+// stacked head product reads relu(h8) -- the operand static_sigma reads -- through the functor that also records layer 8's mask.
+// Mask words and raw_t are those of the unfolded kernel.  The folded full pass is a MODE value of its own, known to this file only
+// (the instance keeps the kernel's template signature).
+#define NEFES_FIELD_FULL_FOLD 3
+template <int MODEF, int ENC, int W = 256, int NTR = 1, bool TRAIN = false, bool FH = false>
 __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(FieldFwdH3Args a) {
+    constexpr bool FOLD = MODEF == NEFES_FIELD_FULL_FOLD;
+    constexpr int MODE = FOLD ? NEFES_FIELD_FULL : MODEF;
     static_assert(NEFES_SLAB_KIB == (W == 128 ? NEFES_H3_FWD_SLAB_KIB_128 : NEFES_H3_FWD_SLAB_KIB), "ring slab size != the packer's for this width");
+    static_assert(!FOLD || (MODE != NEFES_FIELD_SIGMA && !TRAIN), "the fold serves the head products of frozen networks");
     constexpr int NTW = W / 32, NTH = W / 64;
     constexpr int ES = ENC != NEFES_XYZ_FREQ10 ? NEFES_X_STEPS : NEFES_E_STEPS;
     constexpr int MW = 8 * (W / 64) + 4 * (W / 128), WT = (NTW + 1) / 2, WH = (NTH + 1) / 2;
-    constexpr int NSEG = MODE == NEFES_FIELD_SIGMA ? NEFES_H3F_SIG + 1 : (MODE == NEFES_FIELD_STATIC ? NEFES_H3F_N_STATIC : NEFES_H3F_N);   // segments of the stream
+    constexpr int NSEG = MODE == NEFES_FIELD_SIGMA ? NEFES_H3F_SIG + 1
+                         : (MODE == NEFES_FIELD_STATIC ? NEFES_H3F_N_STATIC : (FOLD ? NEFES_H3FF_N : NEFES_H3F_N));   // segments of the stream
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring_base = smem;
     float* bias_lds = (float*)(smem + NEFES_H3_SLOTS * NEFES_SLAB_BYTES);
@@ -121,12 +131,13 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
     // scale table (layout.h): per segment (weight exponent, row bound), then max |b| per bias block
     const int* tab_i = (const int*)(bias_lds + a.scale_off);
     const float* tab_f = bias_lds + a.scale_off;
-    auto wexp = [&](int seg) { return tab_i[nefes_h3_tab_exp(seg)]; };
-    auto rowb = [&](int seg) { return tab_f[nefes_h3_tab_bound(seg)]; };
-    auto bmax = [&](int blk) { return tab_f[nefes_h3_tab_bias(NSEG, blk)]; };
+    auto wexp = [&](int seg) { return tab_i[nefes_h3_tab_exp(nefes_h3f_seg(FOLD, seg))]; };        // (ordinals of the unfolded stream)
+    auto rowb = [&](int seg) { return tab_f[nefes_h3_tab_bound(nefes_h3f_seg(FOLD, seg))]; };
+    auto bmax = [&](int blk) { return tab_f[nefes_h3_tab_bias(NSEG, nefes_h3f_bias(FOLD, blk))]; };
     ring.prime(ring_lane);                                       // (its barrier also publishes the bias block)
     // bias block offsets (floats), in stream order: L1..L8, SIG, FINAL, DIR, RGB, T0, T1, T2, TH (as in field_fwd.hip)
-    constexpr int B_SIG = 8 * W, B_FINAL = B_SIG + 32, B_DIR = B_FINAL + W, B_RGB = B_DIR + W / 2,
+    // (FOLD: no FINAL block)
+    constexpr int B_SIG = 8 * W, B_FINAL = B_SIG + 32, B_DIR = B_FINAL + (FOLD ? 0 : W), B_RGB = B_DIR + W / 2,
                   B_T0 = B_RGB + 32 * NTR, B_T1 = B_T0 + W / 2, B_T2 = B_T1 + W / 2, B_TH = B_T2 + W / 2;
 #pragma unroll 1
     for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
@@ -275,7 +286,8 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
             save_trunk(L1_, B, es_b);                                                                                          \
         }                                                                                                                      \
         put_masks(bits, WT);                                                                      /* mask of layer l1-1 */
-        constexpr int NPAIRS = MODE == NEFES_FIELD_SIGMA ? 3 : 4;
+        constexpr bool END8 = MODE == NEFES_FIELD_SIGMA || FOLD;    // the trunk ends with layer 8 (tiles B), not with xyz_encoding_final (tiles A)
+        constexpr int NPAIRS = END8 ? 3 : 4;
 #pragma unroll 1
         for (int p = 0; p < NPAIRS; ++p) {
             const int l1 = 2 + 2 * p, l2 = l1 + 1;
@@ -306,7 +318,7 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
             }
             put_masks(bits, WT);                                                                      // mask of layer l1
         }
-        if constexpr (MODE == NEFES_FIELD_SIGMA) { NEFES_FWD_EVEN_LAYER(8, NEFES_H3F_L8) }
+        if constexpr (END8) { NEFES_FWD_EVEN_LAYER(8, NEFES_H3F_L8) }
 #undef NEFES_FWD_EVEN_LAYER
         if constexpr (MODE == NEFES_FIELD_SIGMA) sigma_head(B, es_b, tau_of(M, wexp(NEFES_H3F_SIG)));
         if constexpr (MODE != NEFES_FIELD_SIGMA) {
@@ -344,7 +356,30 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
                 __device__ __forceinline__ f32x16 operator()(int t) const { return t < NTH ? a(t) : b(t - NTH); }
             };
             int es_dt;
-            {
+            if constexpr (FOLD) {
+                sigma_head(B, es_b, tau_of(M, wexp(NEFES_H3F_SIG)));                   // static_sigma on relu(h8), as behind the unfolded layer 8
+                // the stacked head on relu(h8): M bounds h8, the head's first W columns are the packer's W_head[:, :W] W_final
+                const int ew = wexp(NEFES_H3F_DT_H);                                   // = wexp(DT_D): one matrix
+                const float mD = pair_max(array_max(Dv));
+                const int tau = tau_of(fmaxf(M, mD), ew);
+                const float rbh_ = rowb(NEFES_H3F_DT_H), rbd_ = rowb(NEFES_H3F_DT_D);
+                const float bm_ = fmaxf(bmax(NEFES_H3BB_DIR), bmax(NEFES_H3BB_T0));      // (FOLD is a FULL instance: both halves of the stack)
+                float mx = 0.f;
+                es_dt = tau + ew;
+                clear_bits();
+                if constexpr (CB) {
+                    const char* bp8 = bias_half + 7 * W * 4;                            // layer 8's tiles come without its bias
+                    nbias = ReluBiasSplitH<CAP, NTW, WT>::prime(bp8);
+                    const ReluBiasSplitH<CAP, NTW, WT> src8{B, bits, pow2i(tau - es_b), mx, bp8, pow2i(es_b), nbias};
+                    mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, src8, Bias2{bias_at(B_DIR, es_dt), bias_at(B_T0, es_dt)}, dt);
+                } else {
+                    const ReluSplitH<CAP, NTW, WT> src8{B, bits, pow2i(tau - es_b), mx};
+                    mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, src8, Bias2{bias_at(B_DIR, es_dt), bias_at(B_T0, es_dt)}, dt);
+                }
+                mma_run_h3<NDT, 2, 0, false>(ring, ring_lane, ArraySplitH<16>{Dv, pow2i(tau)}, ZeroInit{}, dt);
+                M = rbh_ * (pair_max(mx) * pow2i(-es_b)) + rbd_ * mD + bm_;
+                put_masks(bits, WT);                                                  // mask of layer 8
+            } else {
                 const int ew = wexp(NEFES_H3F_DT_H);                                   // = wexp(DT_D): one matrix
                 const float mD = pair_max(array_max(Dv));                            // direction embedding (<= 1 for unit view dirs)
                 const int tau = tau_of(fmaxf(M, mD), ew);                            // common exponent of both parts
@@ -506,8 +541,8 @@ static int launch_h3(const FieldFwdH3Args& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// Kernel instances spread over nine objects built from this one source (Makefile: -DNEFES_TU_PART=0..8; even parts from 2 on are
-// the Wd = 128 objects): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instances, part 2 = Wd = 128 / class 1,
+// Kernel instances spread over eleven objects built from this one source (Makefile: -DNEFES_TU_PART=0..9, 11; even parts from 2 on
+// are the Wd = 128 objects; parts 9 / 11 = the folded Wd = 256 instances of head class 0 / 1): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instances, part 2 = Wd = 128 / class 1,
 // parts 3 / 4 = their TRAIN instances, parts 5 / 6 = Wd = 256 / class 1 and Wd = 128 / class 0, parts 7 / 8 = their TRAIN instances.
 #ifndef NEFES_TU_PART
 #define NEFES_TU_PART 0
@@ -522,6 +557,8 @@ int nefes_fwd_h3_launch_part5(int which, const FieldFwdH3Args& a, hipStream_t st
 int nefes_fwd_h3_launch_part6(int which, const FieldFwdH3Args& a, hipStream_t st);   // Wd = 128, class 0
 int nefes_fwd_h3_launch_part7(int which, const FieldFwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 256, class 1
 int nefes_fwd_h3_launch_part8(int which, const FieldFwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 128, class 0
+int nefes_fwd_h3_launch_part9(int which, const FieldFwdH3Args& a, hipStream_t st);   // folded (FOLD) instances, Wd = 256, class 0
+int nefes_fwd_h3_launch_part11(int which, const FieldFwdH3Args& a, hipStream_t st);  // folded (FOLD) instances, Wd = 256, class 1
 
 
 #if NEFES_TU_PART == 1
@@ -598,6 +635,16 @@ int nefes_fwd_h3_launch_part8(int which, const FieldFwdH3Args& a, hipStream_t st
     }
     return NEFES_E_UNSUPPORTED;
 }
+#elif NEFES_TU_PART == 9
+int nefes_fwd_h3_launch_part9(int which, const FieldFwdH3Args& a, hipStream_t st) {
+    if (which == H3_FULL) return launch_h3<NEFES_FIELD_FULL_FOLD, NEFES_XYZ_FREQ10, 256, 1>(a, st);
+    return NEFES_E_UNSUPPORTED;
+}
+#elif NEFES_TU_PART == 11
+int nefes_fwd_h3_launch_part11(int which, const FieldFwdH3Args& a, hipStream_t st) {
+    if (which == H3_FULL) return launch_h3<NEFES_FIELD_FULL_FOLD, NEFES_XYZ_FREQ10, 256, 5>(a, st);
+    return NEFES_E_UNSUPPORTED;
+}
 #else   // part 0
 
 // Train-mode forward on the fp16 pipe: as nefes_field_fwd_train (field_fwd.hip), same `acts` rows, same masks, same raw_t.
@@ -610,6 +657,7 @@ extern "C" int nefes_field_fwd_train_h3(const NefesNetDesc* desc, const void* pa
     if (mode == NEFES_FIELD_FULL && !desc->has_transient) return NEFES_E_BADARG;
     const int cls = nefes_head_class(desc->feat_dim);
     if ((desc->width != 256 && desc->width != 128) || cls < 0 || desc->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;
+    if (desc->fold_final) return NEFES_E_UNSUPPORTED;               // (a folded pack is a frozen network's)
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
     if (rc) return rc;
@@ -642,6 +690,7 @@ extern "C" int nefes_field_fwd_train_h3_ext(const NefesNetDesc* desc, const void
     if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_UNSUPPORTED;
     if (mode == NEFES_FIELD_FULL && !desc->has_transient) return NEFES_E_BADARG;
     if (desc->width != 256 || nefes_head_class(desc->feat_dim) != 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
+    if (desc->fold_final) return NEFES_E_UNSUPPORTED;
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
     if (rc) return rc;
@@ -680,6 +729,10 @@ static int field_fwd_h3_impl(const NefesNetDesc* desc, const void* packed, int m
     const int cls = nefes_head_class(desc->feat_dim);
     const bool big = desc->width == 256, small = desc->width == 128 && !ext;
     if (!(big || small) || cls < 0 || (ext && cls != 0) || (desc->xyz_encoding != NEFES_XYZ_FREQ10 && !ext)) return NEFES_E_UNSUPPORTED;
+    // a folded pack (NefesNetDesc.fold_final): folded instances exist for the full pass at width 256 with the frequency embedding;
+    // its sigma-only stream is the unfolded one.  No other kernel may read the folded head segments.
+    const bool fold = desc->fold_final != 0;
+    if (fold && mode != NEFES_FIELD_SIGMA && !(mode == NEFES_FIELD_FULL && big && !ext && !fh)) return NEFES_E_UNSUPPORTED;
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
     if (rc) return rc;
@@ -728,6 +781,7 @@ static int field_fwd_h3_impl(const NefesNetDesc* desc, const void* packed, int m
         return cls == 1 ? nefes_fwd_h3_launch_part2(H3_FULL, a, st) : nefes_fwd_h3_launch_part6(H3_FULL, a, st);
     }
     if (mode == NEFES_FIELD_SIGMA) return launch_h3<NEFES_FIELD_SIGMA, NEFES_XYZ_FREQ10>(a, st);
+    if (fold) return cls == 0 ? nefes_fwd_h3_launch_part9(H3_FULL, a, st) : nefes_fwd_h3_launch_part11(H3_FULL, a, st);
     return cls == 0 ? launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10>(a, st) : nefes_fwd_h3_launch_part5(H3_FULL, a, st);
 }
 

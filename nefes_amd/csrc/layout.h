@@ -131,6 +131,22 @@ enum { NEFES_H3B_RGB = 0, NEFES_H3B_TH, NEFES_H3B_T2, NEFES_H3B_T1, NEFES_H3B_T0
 #define NEFES_H3F_N_STATIC (NEFES_H3F_RGB + 1)
 #define NEFES_H3B_N_STATIC (NEFES_H3B_N - 4)
 NEFES_HD int nefes_h3b_seg(int has_transient, int seg) { return (has_transient || seg == NEFES_H3B_RGB) ? seg : seg - 4; }
+/* Folded streams (NefesNetDesc.fold_final: xyz_encoding_final multiplied into the head matrices by the packer): the same segments
+ * and bias blocks without FINAL; DT_H then holds [W_dir[:, :W] ; W_t0[:, :W]] W_final, the DIR / T0 bias blocks W_head[:, :W] b_final
+ * + b_head.  The kernels address both kinds with the unfolded ordinals through nefes_h3f_seg / nefes_h3f_bias / nefes_h3b_fold_seg. */
+enum { NEFES_H3FF_SIG = NEFES_H3F_SIG, NEFES_H3FF_DT_H, NEFES_H3FF_DT_D, NEFES_H3FF_RGB, NEFES_H3FF_T1, NEFES_H3FF_T2, NEFES_H3FF_TH,
+       NEFES_H3FF_N };
+enum { NEFES_H3FBB_SIG = NEFES_H3BB_SIG, NEFES_H3FBB_DIR, NEFES_H3FBB_RGB, NEFES_H3FBB_T0, NEFES_H3FBB_T1, NEFES_H3FBB_T2, NEFES_H3FBB_TH };
+enum { NEFES_H3BF_RGB = 0, NEFES_H3BF_TH, NEFES_H3BF_T2, NEFES_H3BF_T1, NEFES_H3BF_T0, NEFES_H3BF_DIR, NEFES_H3BF_SIG, NEFES_H3BF_L8,
+       NEFES_H3BF_L7, NEFES_H3BF_L6, NEFES_H3BF_L5, NEFES_H3BF_L4, NEFES_H3BF_L3, NEFES_H3BF_L2, NEFES_H3BF_L1, NEFES_H3BF_N };
+#define NEFES_H3FF_N_STATIC (NEFES_H3FF_RGB + 1)
+#define NEFES_H3BF_N_STATIC (NEFES_H3BF_N - 4)
+NEFES_HD int nefes_h3f_seg(int fold, int seg) { return (fold && seg > NEFES_H3F_FINAL) ? seg - 1 : seg; }
+NEFES_HD int nefes_h3f_bias(int fold, int block) { return (fold && block > NEFES_H3BB_FINAL) ? block - 1 : block; }
+NEFES_HD int nefes_h3b_fold_seg(int fold, int seg) { return (fold && seg > NEFES_H3B_FINAL) ? seg - 1 : seg; }   /* before nefes_h3b_seg */
+static_assert(NEFES_H3FF_DT_H == NEFES_H3F_DT_H - 1 && NEFES_H3FF_TH == NEFES_H3F_TH - 1 && NEFES_H3FBB_DIR == NEFES_H3BB_DIR - 1 &&
+              NEFES_H3FBB_TH == NEFES_H3BB_TH - 1 && NEFES_H3BF_SIG == NEFES_H3B_SIG - 1 && NEFES_H3BF_L1 == NEFES_H3B_L1 - 1,
+              "folded ordinals = the unfolded ones with FINAL taken out");
 
 // ReLU-mask words (32 bit) written per lane per 32-sample tile by the full forward pass:
 // 8 trunk layers (W/64 words each) + dir + 3 transient layers (W/128 words each)

@@ -126,6 +126,7 @@ static int scale_exp(float amax) {
 struct BiasBlk {
     const float* b;
     std::vector<int> ridx;  // [nt*32] index into b or -1
+    bool folded = false;    // a fold_final bias (rounded from a double): its max |b| in the scale table is rounded up one ulp
 };
 
 struct Stream {
@@ -194,6 +195,15 @@ struct Net {
     const float* const* t;
     std::vector<float> th_w, th_b;  // virtual transient-head matrix [5][W2]: rgb(3), sigma, beta
     std::vector<float> dt_w;        // virtual stacked [dir_encoding ; transient_encoding.0] matrix [2 W2][W + 27] (x6 streams)
+    // NefesNetDesc.fold_final: xyz_encoding_final multiplied into its two consumers (fold_head below) -- dir_encoding, transient_
+    // encoding.0 and their stack with the first W columns replaced by W_head[:, :W] W_final, biases W_head[:, :W] b_final + b_head
+    bool fold = false;
+    std::vector<float> fd_w, ft_w, fdt_w, fd_b, ft_b;
+    const float* w_dir(bool h3) const { return fold && h3 ? fd_w.data() : w(L_DIR); }
+    const float* w_t0(bool h3) const { return fold && h3 ? ft_w.data() : w(L_T0); }
+    const float* w_dt(bool h3) const { return fold && h3 ? fdt_w.data() : dt_w.data(); }
+    const float* b_dir(bool h3) const { return fold && h3 ? fd_b.data() : b(L_DIR); }
+    const float* b_t0(bool h3) const { return fold && h3 ? ft_b.data() : b(L_T0); }
     const float* w(int l) const { return t[2 * l]; }
     const float* b(int l) const { return t[2 * l + 1]; }
 };
@@ -265,14 +275,16 @@ void add_static_head(const Net& n, Stream& st, int x6 = 0) {
 // first NEFES_H3F_N_STATIC segments of the full fp16 stream, with dir_encoding alone where that one stacks [dir ; t0]
 void add_static_head_h3(const Net& n, Stream& st) {
     const int W = n.W, W2 = n.W2;
-    st.segs.push_back(seg(n.NTW, W / 2, k_natural(W / 2, 0), rows_natural(n.NTW, W), n.w(L_FINAL), W));
+    if (!n.fold) {
+        st.segs.push_back(seg(n.NTW, W / 2, k_natural(W / 2, 0), rows_natural(n.NTW, W), n.w(L_FINAL), W));
+        mark(st.segs.back(), 2);
+        st.bias.push_back({n.b(L_FINAL), rows_natural(n.NTW, W)});
+    }
+    st.segs.push_back(seg(n.NTH, W / 2, k_natural(W / 2, 0), rows_natural(n.NTH, W2), n.w_dir(true), W + 27));
     mark(st.segs.back(), 2);
-    st.bias.push_back({n.b(L_FINAL), rows_natural(n.NTW, W)});
-    st.segs.push_back(seg(n.NTH, W / 2, k_natural(W / 2, 0), rows_natural(n.NTH, W2), n.w(L_DIR), W + 27));
+    st.segs.push_back(seg(n.NTH, 16, k_emb(4, 16, W), rows_natural(n.NTH, W2), n.w_dir(true), W + 27));   // 14 k-steps padded to 16
     mark(st.segs.back(), 2);
-    st.segs.push_back(seg(n.NTH, 16, k_emb(4, 16, W), rows_natural(n.NTH, W2), n.w(L_DIR), W + 27));   // 14 k-steps padded to 16
-    mark(st.segs.back(), 2);
-    st.bias.push_back({n.b(L_DIR), rows_natural(n.NTH, W2)});
+    st.bias.push_back({n.b_dir(true), rows_natural(n.NTH, W2), n.fold});
     st.segs.push_back(seg(n.NTR, W2 / 2, k_natural(W2 / 2, 0), rows_natural(n.NTR, 3 + n.C), n.w(L_RGB), W2));
     mark(st.segs.back(), 2);
     st.bias.push_back({n.b(L_RGB), rows_natural(n.NTR, 3 + n.C)});
@@ -284,19 +296,22 @@ void add_static_head_h3(const Net& n, Stream& st) {
 // order of the fp32 streams (FINAL, DIR, RGB, T0, T1, T2, TH).
 void add_heads_x6(const Net& n, Stream& st, int kind = 1) {
     const int W = n.W, W2 = n.W2;
-    st.segs.push_back(seg(n.NTW, W / 2, k_natural(W / 2, 0), rows_natural(n.NTW, W), n.w(L_FINAL), W));
-    mark(st.segs.back(), kind);
-    st.bias.push_back({n.b(L_FINAL), rows_natural(n.NTW, W)});
-    st.segs.push_back(seg(2 * n.NTH, W / 2, k_natural(W / 2, 0), rows_natural(2 * n.NTH, 2 * W2), n.dt_w.data(), W + 27));
+    const bool h3 = kind == 2, fold = n.fold && h3;                     // (the fold is the fp16 streams' alone)
+    if (!fold) {
+        st.segs.push_back(seg(n.NTW, W / 2, k_natural(W / 2, 0), rows_natural(n.NTW, W), n.w(L_FINAL), W));
+        mark(st.segs.back(), kind);
+        st.bias.push_back({n.b(L_FINAL), rows_natural(n.NTW, W)});
+    }
+    st.segs.push_back(seg(2 * n.NTH, W / 2, k_natural(W / 2, 0), rows_natural(2 * n.NTH, 2 * W2), n.w_dt(h3), W + 27));
     mark(st.segs.back(), kind);
     // direction part: 14 k-steps padded to 16 (= two 16-k steps; slots 14, 15 are padding)
-    st.segs.push_back(seg(2 * n.NTH, 16, k_emb(4, 16, W), rows_natural(2 * n.NTH, 2 * W2), n.dt_w.data(), W + 27));
+    st.segs.push_back(seg(2 * n.NTH, 16, k_emb(4, 16, W), rows_natural(2 * n.NTH, 2 * W2), n.w_dt(h3), W + 27));
     mark(st.segs.back(), kind);
-    st.bias.push_back({n.b(L_DIR), rows_natural(n.NTH, W2)});
+    st.bias.push_back({n.b_dir(h3), rows_natural(n.NTH, W2), fold});
     st.segs.push_back(seg(n.NTR, W2 / 2, k_natural(W2 / 2, 0), rows_natural(n.NTR, 3 + n.C), n.w(L_RGB), W2));
     mark(st.segs.back(), kind);
     st.bias.push_back({n.b(L_RGB), rows_natural(n.NTR, 3 + n.C)});
-    st.bias.push_back({n.b(L_T0), rows_natural(n.NTH, W2)});
+    st.bias.push_back({n.b_t0(h3), rows_natural(n.NTH, W2), fold});
     for (int l = L_T1; l <= L_T2; ++l) {
         st.segs.push_back(seg(n.NTH, W2 / 2, k_natural(W2 / 2, 0), rows_natural(n.NTH, W2), n.w(l), W2));
         mark(st.segs.back(), kind);
@@ -347,15 +362,18 @@ void add_backward(const Net& n, Stream& st, int x6 = 0, bool transient = true) {
     }
     // [transient_encoding.0 ; dir_encoding]^T: out rows = dir-embedding slots (1 tile) then final features (NTW tiles)
     std::vector<int> rows_fd = concat(rows_emb(4, 1, W), rows_natural(NTW, W));
+    // (fold_final, fp16 streams: the folded matrices -- their rows past the embedding tile are d h8 itself)
     if (transient) {
-        st.segs.push_back(seg(NTW + 1, W2 / 2, k_natural(W2 / 2, 0), rows_fd, n.w(L_T0), W + 27, true));
+        st.segs.push_back(seg(NTW + 1, W2 / 2, k_natural(W2 / 2, 0), rows_fd, n.w_t0(x6 == 2), W + 27, true));
         mark(st.segs.back(), x6);
     }
-    st.segs.push_back(seg(NTW + 1, W2 / 2, k_natural(W2 / 2, 0), rows_fd, n.w(L_DIR), W + 27, true));
+    st.segs.push_back(seg(NTW + 1, W2 / 2, k_natural(W2 / 2, 0), rows_fd, n.w_dir(x6 == 2), W + 27, true));
     mark(st.segs.back(), x6);
     // xyz_encoding_final^T, plus the static-sigma head as one extra k-step
-    st.segs.push_back(seg(NTW, W / 2, k_natural(W / 2, 0), rows_natural(NTW, W), n.w(L_FINAL), W, true));
-    mark(st.segs.back(), x6);
+    if (!(n.fold && x6 == 2)) {
+        st.segs.push_back(seg(NTW, W / 2, k_natural(W / 2, 0), rows_natural(NTW, W), n.w(L_FINAL), W, true));
+        mark(st.segs.back(), x6);
+    }
     st.segs.push_back(seg(NTW, 1, k_compact(1, 1), rows_natural(NTW, W), n.w(L_SIGMA), W, true));
     for (int l = 7; l >= 0; --l) {
         if (l == 4) {
@@ -379,6 +397,8 @@ void add_backward(const Net& n, Stream& st, int x6 = 0, bool transient = true) {
 // Elements of the weight matrix a segment reads (the whole torch tensor, or one of the virtual stacked matrices).
 static size_t matrix_elems(const Net& n, const float* Wm) {
     if (Wm == n.th_w.data()) return n.th_w.size();
+    if (n.fold && Wm == n.fdt_w.data()) return n.fdt_w.size();
+    if (n.fold && (Wm == n.fd_w.data() || Wm == n.ft_w.data())) return n.fd_w.size();
     if (Wm == n.dt_w.data()) return n.dt_w.size();
     const int W = n.W, W2 = n.W2;
     for (int l = 0; l < 18; ++l) {
@@ -407,9 +427,13 @@ static float abs_max(const float* p, size_t cnt) {
 // products share accumulators in both directions).
 static void assign_weight_exponents(const Net& n, Stream (&st)[NEFES_N_STREAMS]) {
     const int e_dt = n.transient ? scale_exp(abs_max(n.dt_w.data(), n.dt_w.size())) : 0;
+    // the folded head matrices: ONE exponent for the folded columns and the direction columns, which accumulate into the same
+    // tiles (fp16 subnormals keep a column group that lies up to 16 binades below the other at its full 22 bits: DESIGN.md 4.1d)
+    const int e_fdt = n.fold ? scale_exp(abs_max(n.fdt_w.data(), n.fdt_w.size())) : 0;
     for (auto& stream : st)
         for (auto& sg : stream.segs) {
             if (!sg.h3 || !sg.W) continue;
+            if (n.fold && (sg.W == n.fdt_w.data() || sg.W == n.fd_w.data() || sg.W == n.ft_w.data())) { sg.wexp = e_fdt; continue; }
             const bool dt = sg.W == n.dt_w.data() || (n.transient && (sg.W == n.w(L_DIR) || sg.W == n.w(L_T0)));
             sg.wexp = dt ? e_dt : scale_exp(abs_max(sg.W, matrix_elems(n, sg.W)));
         }
@@ -426,8 +450,30 @@ static int group_of(const Net& n, const float* Wm) {
     return -1;
 }
 
+// fold_final: out [W2][W + 27] = [W_head[:, :W] W_final | W_head[:, W:]], out_b = W_head[:, :W] b_final + b_head, in double from the
+// fp32 tensors, rounded ONCE to fp32 (the scaling and the fp16 split then treat it like any other matrix)
+static void fold_head(const Net& n, const float* Wh, const float* bh, float* out, float* out_b) {
+    const int W = n.W, W2 = n.W2, K = n.W + 27;
+    const float *Wf = n.w(L_FINAL), *bf = n.b(L_FINAL);
+    std::vector<double> row((size_t)W);
+    for (int r = 0; r < W2; ++r) {
+        for (int c = 0; c < W; ++c) row[c] = 0.0;
+        double bsum = (double)bh[r];
+        for (int k = 0; k < W; ++k) {
+            const double a = (double)Wh[(size_t)r * K + k];
+            const float* wf = Wf + (size_t)k * W;
+            for (int c = 0; c < W; ++c) row[c] += a * (double)wf[c];
+            bsum += a * (double)bf[k];
+        }
+        for (int c = 0; c < W; ++c) out[(size_t)r * K + c] = (float)row[c];
+        for (int c = W; c < K; ++c) out[(size_t)r * K + c] = Wh[(size_t)r * K + c];
+        out_b[r] = (float)bsum;
+    }
+}
+
 bool build(const NefesNetDesc* d, const float* const* tensors, Net& n, Stream (&st)[NEFES_N_STREAMS]) {
     if (!d) return false;
+    if (d->fold_final != 0 && d->fold_final != 1) return false;
     if (d->width != 128 && d->width != 256) return false;
     if (nefes_head_class(d->feat_dim) < 0) return false;          // 0 <= C <= NEFES_HEAD_MAX_C (layout.h: head classes)
     n.W = d->width; n.W2 = n.W / 2; n.C = d->feat_dim;
@@ -454,6 +500,19 @@ bool build(const NefesNetDesc* d, const float* const* tensors, Net& n, Stream (&
         n.dt_w.assign((size_t)2 * n.W2 * (n.W + 27), 0.f);
         n.th_w.assign((size_t)5 * n.W2, 0.f);
         n.th_b.assign(5, 0.f);
+    }
+    n.fold = d->fold_final != 0;
+    if (n.fold) {
+        if (n.ext && !(n.W == 256 && nefes_head_class(n.C) == 0)) return false;       // no fp16 streams to fold (h3_shape below)
+        const size_t me = (size_t)n.W2 * (n.W + 27);
+        n.fd_w.assign(me, 0.f); n.ft_w.assign(me, 0.f); n.fdt_w.assign(2 * me, 0.f);
+        n.fd_b.assign(n.W2, 0.f); n.ft_b.assign(n.W2, 0.f);
+        if (tensors) {
+            fold_head(n, n.w(L_DIR), n.b(L_DIR), n.fd_w.data(), n.fd_b.data());
+            if (n.transient) fold_head(n, n.w(L_T0), n.b(L_T0), n.ft_w.data(), n.ft_b.data());
+            memcpy(&n.fdt_w[0], n.fd_w.data(), sizeof(float) * me);
+            memcpy(&n.fdt_w[me], n.ft_w.data(), sizeof(float) * me);
+        }
     }
     // a null `tensors` is allowed for geometry queries: substitute a dummy table
     static const float* dummy[36] = {nullptr};
@@ -587,6 +646,7 @@ static int pack_walk(const NefesNetDesc* desc, const Net& n, char* base, uint32_
                     float m = 0.f;
                     for (int r : bb.ridx)
                         if (r >= 0 && fabsf(bb.b[r]) > m) m = fabsf(bb.b[r]);
+                    if (bb.folded) m = nextafterf(m, INFINITY);
                     memcpy(&word, &m, 4);
                 }
                 if (base) memcpy(base + boff, &word, 4);
@@ -705,6 +765,8 @@ struct Indexed {
     NefesBlobInfo info;
 };
 static int build_indexed(const NefesNetDesc* desc, Indexed& x, int64_t* tensor_elems_out) {
+    // a folded blob holds products of parameters: no slot map / reduction plan exists for it, the device re-pack does not serve it
+    if (desc && desc->fold_final) return NEFES_E_UNSUPPORTED;
     {   // geometry first (tensor sizes depend on it)
         Stream tmp[NEFES_N_STREAMS];
         if (!build(desc, nullptr, x.n, tmp)) return NEFES_E_UNSUPPORTED;

@@ -204,6 +204,8 @@ class NeRFH_NFF(nn.Module):
         self._pk_key = None
         self._pk_gen = None
         self._pk_gen_key = None
+        self._pk_fold = None
+        self._pk_fold_key = None
 
     # -- the HIP path ---------------------------------------------------------------------------
     def _supported(self):
@@ -310,6 +312,7 @@ class NeRFH_NFF(nn.Module):
         such an edit (a captured PoseRefiner graph must be re-captured as well)."""
         self._pk_key = None
         self._pk_gen_key = None
+        self._pk_fold_key = None
 
     def packed(self) -> ops.PackedField:
         """Fragment streams for the fused kernels; re-packed when any path parameter changes (see invalidate_packed for
@@ -345,13 +348,38 @@ class NeRFH_NFF(nn.Module):
             self._pk_key = key
         return self._pk
 
+    def _field_frozen(self):
+        """No parameter of the field path asks for a gradient (the FusionNet / exposure sub-modules are not part of the field)."""
+        return not any(p.requires_grad for n, p in self.named_parameters()
+                       if not n.startswith(("fusion_net", "exposure_embedding")))
+
+    def fold_ok(self):
+        """The folded kernels apply to this network's full pass (csrc/field_fwd_h3.hip FOLD): a FROZEN fine network of a shape with folded
+        instances, on the fp16 two-part pipe.  Evaluated per render: a network made trainable afterwards takes the unfolded kernels."""
+        return (ops.FOLD_FINAL and ops.SPLIT == "h3" and ops.USE_X6 and not ops.FIELD_GENERIC and self.encode_transient and self._supported()
+                and ops.fold_shape(self.W, self.W_features, L.XYZ_EXTERNAL32 if self.in_channels_xyz == 32 else L.XYZ_FREQ10)
+                and self._field_frozen())
+
+    def packed_folded(self) -> ops.PackedField:
+        """packed() with xyz_encoding_final multiplied into dir_encoding / transient_encoding.0 by the packer (NefesNetDesc.fold_final):
+        what the fine pass of a frozen network runs on.  Cached and invalidated like packed(); always packed on the host (the fold is a
+        product of parameters in double)."""
+        names = ops.PackedField.LAYERS_FINE
+        sd = dict(self.named_parameters())
+        prm = [sd[n + s] for n in names for s in (".weight", ".bias")]
+        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in prm)
+        if self._pk_fold is None or key != self._pk_fold_key:
+            dev = prm[0].device if prm[0].is_cuda else torch.device("cuda")
+            self._pk_fold = ops.PackedField(self._kernel_params({n: p.detach() for n, p in sd.items()}), self.W, self.W_features,
+                                            True, dev, L.XYZ_FREQ10, fold_final=True)
+            self._pk_fold_key = key
+        return self._pk_fold
+
     def factored_head_ok(self):
         """The factored-head kernels apply (csrc/field_fwd_h3.hip FH): a FROZEN fine network of width 128 on the frequency embedding whose
         rgb+feature head has more channels than g = relu(dir_encoding) has features (+ the ones channel), on the fp16 two-part pipe."""
         return (ops.FACTORED_HEAD and not ops.FIELD_GENERIC and self.encode_transient and self.W == 128 and self.in_channels_xyz != 32 and self._supported()
-                and 3 + self.W_features > 3 + self.W // 2 + 1 and ops.SPLIT == "h3"
-                and not any(p.requires_grad for n, p in self.named_parameters()
-                            if not n.startswith(("fusion_net", "exposure_embedding"))))
+                and 3 + self.W_features > 3 + self.W // 2 + 1 and ops.SPLIT == "h3" and self._field_frozen())
 
     def packed_fh(self):
         """(PackedField of the network WITHOUT its feature rows -- static_rgb = its three colour rows, f_dim 0 --, W_f [C, W/2], W_f^T, b_f [C]):

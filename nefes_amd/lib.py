@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("NEFES_HIP_LIB") or os.path.join(_HERE, "libnefes_hip.
 
 
 class NefesNetDesc(C.Structure):
-    _fields_ = [("width", C.c_int32), ("feat_dim", C.c_int32), ("has_transient", C.c_int32), ("xyz_encoding", C.c_int32)]
+    _fields_ = [("width", C.c_int32), ("feat_dim", C.c_int32), ("has_transient", C.c_int32), ("xyz_encoding", C.c_int32),
+                ("fold_final", C.c_int32)]
 
 
 class NefesGenericNetDesc(C.Structure):
@@ -36,7 +37,7 @@ class NefesHashGridDesc(C.Structure):
                 ("base_resolution", C.c_int32), ("per_level_scale", C.c_float), ("bound", C.c_float)]
 
 
-ABI_VERSION = 16       # NEFES_ABI_VERSION of include/nefes_hip.h
+ABI_VERSION = 17       # NEFES_ABI_VERSION of include/nefes_hip.h
 STREAM_FWD_SIGMA, STREAM_FWD_STATIC, STREAM_FWD_FULL, STREAM_BWD_FULL, STREAM_FWD_SIGMA_X6, STREAM_FWD_FULL_X6, STREAM_BWD_FULL_X6, STREAM_BWD_STATIC = 0, 1, 2, 3, 4, 5, 6, 7
 STREAM_FWD_SIGMA_H3, STREAM_FWD_FULL_H3, STREAM_BWD_FULL_H3, STREAM_FWD_STATIC_H3, STREAM_BWD_STATIC_H3 = 8, 9, 10, 11, 12
 FIELD_SIGMA, FIELD_STATIC, FIELD_FULL = 0, 1, 2

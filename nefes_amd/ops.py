@@ -263,9 +263,10 @@ class PackedField:
     LAYERS_FINE = LAYERS_COARSE + ["transient_encoding.0", "transient_encoding.2", "transient_encoding.4",
                                    "transient_sigma.0", "transient_rgb.0", "transient_beta.0"]
 
-    def __init__(self, state_dict, width, feat_dim, has_transient, device, xyz_encoding=0):
+    def __init__(self, state_dict, width, feat_dim, has_transient, device, xyz_encoding=0, fold_final=False):
         lib = L.load()
-        self.desc = L.NefesNetDesc(int(width), int(feat_dim), 1 if has_transient else 0, int(xyz_encoding))
+        self.desc = L.NefesNetDesc(int(width), int(feat_dim), 1 if has_transient else 0, int(xyz_encoding), 1 if fold_final else 0)
+        self.fold = bool(fold_final)  # xyz_encoding_final multiplied into the head matrices of the fp16 streams (frozen networks; fold_shape)
         self.xyz_encoding = int(xyz_encoding)
         self.width, self.feat_dim, self.has_transient = int(width), int(feat_dim), bool(has_transient)
         info = L.NefesBlobInfo()
@@ -289,6 +290,9 @@ class PackedField:
         """Re-pack every stream on the device from the current parameter values (`params`: (weight, bias) per layer in
         LAYERS order, CUDA tensors): one concatenation + one launch (nefes_pack_device), no host copy, no sync."""
         lib = L.load()
+        if self.fold:
+            raise RuntimeError("nefes_amd: a folded pack (fold_final) holds products of parameters and is not re-packed on the device; "
+                               "trainable networks take NeRFH_NFF.packed()")
         if self._map is None:
             n = self.info.total_bytes // 2
             host_map = torch.zeros(n, dtype=torch.int32)
@@ -398,6 +402,17 @@ def h3_shape(pk: PackedField):
     return True if pk.xyz_encoding == L.XYZ_FREQ10 else (pk.width == 256 and cls == 0)
 
 
+# Frozen networks on the fp16 pipe: xyz_encoding_final (a Linear with no activation behind it) is multiplied into dir_encoding /
+# transient_encoding.0 by the packer and its W x W product leaves the fine pass's forward and backward kernels (csrc/field_fwd_h3.hip
+# FOLD; NeRFH_NFF.packed_folded).  "0": the unfolded kernels for every network.
+FOLD_FINAL = os.environ.get("NEFES_FOLD_FINAL", "1") != "0"
+
+
+def fold_shape(width, feat_dim, xyz_encoding=L.XYZ_FREQ10):
+    """Shapes with folded instances (csrc/field_fwd_h3.hip parts 9 / 11): width 256, both head classes, frequency embedding, full pass."""
+    return width == 256 and head_class(feat_dim) >= 0 and xyz_encoding == L.XYZ_FREQ10
+
+
 def x6_supported(pk: PackedField, mode, forward=True):
     """A split-product instance (fp16 two-part or bf16x6) serves this network and mode: sigma-only or full, forward and backward --
     and, on the fp16 two-part instances with the frequency embedding, the static head alone (round 5: a frozen coarse network with
@@ -442,8 +457,11 @@ def field_fwd_x6(pk: PackedField, mode, N, S, rays_o=None, rays_d=None, z=None, 
     if not h3 and not canonical_shape(pk):
         raise RuntimeError(f"nefes_amd: {N * S} samples in one launch exceed the fp16 two-part kernels' 32-bit sample index and "
                            f"W={pk.width}, f_dim={pk.feat_dim} has no other instance; render fewer rays per launch")
+    fold = getattr(pk, "fold", False)
+    if fold and not (h3 and mode == L.FIELD_FULL):
+        raise RuntimeError("nefes_amd: a folded pack serves the full pass on the fp16 two-part kernels only")
     fn = L.load().nefes_field_fwd_h3 if h3 else L.load().nefes_field_fwd_x6
-    with _timed(f"field_fwd[{('sigma', 'static', 'full')[mode]},{'h3' if h3 else 'x6'}]"):
+    with _timed(f"field_fwd[{('sigma', 'static', 'full')[mode]},{'h3' if h3 else 'x6'}{',fold' if fold else ''}]"):
         L.check(fn(pk.desc, _chk(pk.blob, "blob", torch.uint8), mode, N, S, _chk(rays_o, "rays_o"),
                                             _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(xyz_enc, "xyz_enc"),
                                             _chk(viewdirs, "viewdirs"),
@@ -482,8 +500,13 @@ def field_bwd(pk: PackedField, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=
     g_vs = torch.empty(N * S, 3, device=dev)
     if USE_X6 and SPLIT != "f32" and x6_supported(pk, L.FIELD_FULL, forward=False):
         h3 = _h3(pk)
+        # (a folded pack with SPLIT switched to "f32" between forward and backward -- tests do that -- lands in the strict-fp32 call
+        # at the end of this function: that stream of a folded blob is the unfolded one and the masks / raw_t are the same)
+        fold = getattr(pk, "fold", False)
+        if fold and not h3:
+            raise RuntimeError("nefes_amd: a folded pack serves the fp16 two-part kernels only")
         fn = L.load().nefes_field_bwd_h3 if h3 else L.load().nefes_field_bwd_x6
-        with _timed("field_bwd[h3]" if h3 else "field_bwd[x6]"):
+        with _timed(("field_bwd[h3,fold]" if fold else "field_bwd[h3]") if h3 else "field_bwd[x6]"):
             L.check(fn(pk.desc, _chk(pk.blob, "blob", torch.uint8), N, S, _chk(rays_o, "rays_o"),
                                                 _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
                                                 _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32),

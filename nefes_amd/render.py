@@ -229,8 +229,14 @@ def _fine_pass(rays_o, rays_d, viewdirs, z_fine, z_samples, network_fine, cfg, C
         if cfg.feat_as_gmap:
             ret["feat_is_gmap"] = True
         return ret
-    pk_f = network_fine.packed_any()
     mode = L.FIELD_FULL if cfg.NeRFW else L.FIELD_STATIC
+    if (mode == L.FIELD_FULL and cfg.xyz_encoder is None and z_f.shape[0] * z_f.shape[1] < (1 << 31) - 256
+            and network_fine.fold_ok()):
+        # a frozen network on the fp16 pipe: the pack with xyz_encoding_final folded into the head matrices (decided per render;
+        # forward and backward of the autograd node use this one pack)
+        pk_f = network_fine.packed_folded()
+    else:
+        pk_f = network_fine.packed_any()
     raw_f = field(network_fine, pk_f, mode, z_f)
     if cfg.raw_noise_std > 0. and not cfg.NeRFW:
         # the reference draws the noise in every composite WITHOUT the transient head (nerfh_nff.py:66-68) -- the coarse pass above and a
