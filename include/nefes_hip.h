@@ -239,7 +239,8 @@ int nefes_field_bwd_x6(const NefesNetDesc* desc, const void* packed, int N, int 
  * Weights are scaled per matrix by the packer (exponent table in the NEFES_STREAM_*_H3 streams), activations / gradient vectors
  * per sample and product inside the kernels.  Shapes (round 4): widths 128 / 256 x the two head CLASSES of csrc/layout.h --
  * nefes_head_class: C <= 29 (e.g. BASELINE's 16 channels) and 30 <= C <= 141 (the reference's FEATURE_DIM = 128, nerfh_nff.py:21) --
- * with the frequency embedding, C itself a run-time value (desc->feat_dim); width 256 / C <= 29 with an external embedding.
+ * with the frequency embedding, C itself a run-time value (desc->feat_dim); width 256 x both classes with an external embedding
+ * (sigma-only and full; the static head alone at inference stays the frequency embedding's).
  * NEFES_E_UNSUPPORTED otherwise (nefes_blob_info refuses C > 141 and widths other than 128 / 256 up front).
  * Same arguments, outputs and ReLU-mask words as the calls above, so forward and backward kernels of every kind combine.
  * nefes_pack_device refreshes the fp16 streams when it is given the plan of nefes_pack_h3_plan. */
@@ -261,7 +262,8 @@ int nefes_field_bwd_h3(const NefesNetDesc* desc, const void* packed, int N, int 
  * d loss / d pts through the MLP and the grid (frozen table) -- nefes_hashgrid_fwd + nefes_field_fwd_h3(xyz_enc) and
  * nefes_field_bwd_h3(g_xyz_enc) + nefes_hashgrid_bwd_x without the two [M, 32] tensors (10 GB each per fine pass at 854x480).
  * Forward outputs are bit-identical to that sequence.  z: [N, S], or (forward, z_is_row != 0) one row [S] shared by every ray.
- * Width 256, C <= 29.  PARITY UNPINNED like nefes_hashgrid_fwd. */
+ * Width 256, C <= 29; the sigma-only forward (no rgb head) also for 30 <= C <= 141, whose full pass returns NEFES_E_UNSUPPORTED here and
+ * takes the separate calls above.  PARITY UNPINNED like nefes_hashgrid_fwd. */
 int nefes_field_fwd_h3_hashgrid(const NefesNetDesc* desc, const void* packed, const NefesHashGridDesc* grid, const float* table,
                                 int mode, int N, int S, const float* rays_o, const float* rays_d, const float* z, int z_is_row,
                                 const float* viewdirs, float* raw_t, uint32_t* masks, void* stream);
@@ -360,7 +362,7 @@ int nefes_field_bwd_train_h3(const NefesNetDesc* desc, const void* packed, int m
 /* Train mode of a NEFES_XYZ_EXTERNAL32 network (a trainable hash grid in front of the MLP): the forward reads the caller's encoding
  * xyz_enc [N*S, 32] and stores it into rows 0..31 of the E block of `acts` in natural feature order; the backward writes `dacts` as
  * nefes_field_bwd_train_h3 does plus g_xyz_enc [N*S, 32] = d loss / d xyz_enc (no ray gradients: those pass through the encoding).
- * fp16 two-part pipe, width 256, head class 0 (3 + C <= 32) only; mode NEFES_FIELD_STATIC or NEFES_FIELD_FULL. */
+ * fp16 two-part pipe, width 256, both head classes (3 + C <= 144); mode NEFES_FIELD_STATIC or NEFES_FIELD_FULL. */
 int nefes_field_fwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* xyz_enc,
                                  const float* viewdirs, float* raw_t, float* acts, uint32_t* masks, void* stream);
 int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* viewdirs,

@@ -17,7 +17,8 @@
 // runs -- behind an MFMA that has not written them yet.  So the three embedding-gradient tiles are consumed
 // where they are produced (below), layer 5's two extra output tiles live in VGPRs for the length of that run, and
 // tests/test_pack_stream.py disassembles the library and fails if a v_accvgpr_mov shows up in these kernels.
-#if !defined(NEFES_TU_PART) || NEFES_TU_PART == 0 || NEFES_TU_PART == 1 || NEFES_TU_PART == 5 || NEFES_TU_PART == 9 || NEFES_TU_PART == 11
+#if !defined(NEFES_TU_PART) || NEFES_TU_PART == 0 || NEFES_TU_PART == 1 || NEFES_TU_PART == 5 || NEFES_TU_PART == 9 || NEFES_TU_PART == 11 || \
+    NEFES_TU_PART == 13
 #define H3B_WIDE
 #define H3_ACC_READ_ASM        // source tiles are read out of their AGPRs inside the MFMA gaps (field_h3.h acc_read)
 #define NEFES_ASM_READS_ACC    // ... by asm statements: compiler-placed runs end with field_common.h mfma_results_fence_tiles
@@ -141,7 +142,8 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
     // v_accvgpr_mov one wait state behind the asm MFMA that writes the tile, where hipcc would put twelve behind an MFMA of its own
     // (tools/hazard_lint.py rule B1; tests/test_pack_stream.py finds the move itself; round 3 saw wrong gradients from such a move).  With compiler-placed MFMAs a moved tile is
     // the compiler's to pad.  Costs configs[3] ~4 ms of 590 per frame.
-    constexpr int WIDE_LAYERS = ENC == NEFES_XYZ_HASHGRID_FUSED ? 0 : H3B_WIDE_LAYERS;
+    // (KR16 = 9 with the hash grid exists in NEFES_H3_HG_CLASS1 builds only, on the schedule: part 13's note)
+    constexpr int WIDE_LAYERS = (ENC == NEFES_XYZ_HASHGRID_FUSED && KR16 == 2) ? 0 : H3B_WIDE_LAYERS;
     static_assert(KR16 == 2 || KR16 == 9, "head classes of layout.h (nefes_head_kr16 / nefes_head_ntr)");
     const int C3 = 3 + a.C;                                         // static rgb/feature head^T: 3+C upstream channels as fp16 k-steps
     static_assert(MW % 4 == 0, "mask words are staged as 16-byte groups");
@@ -599,8 +601,9 @@ static int launch_bwd_h3(const FieldBwdH3Args& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// Instances spread over eleven objects built from this one source (Makefile: -DNEFES_TU_PART=0..9, 11; even parts from 2 on are the
-// Wd = 128 objects; parts 9 / 11 = the folded Wd = 256 instances of head class 0 / 1): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instance, part 2 = Wd = 128 / class 1,
+// Instances spread over thirteen objects built from this one source (Makefile: -DNEFES_TU_PART=0..9, 11, 13, 15; even parts from 2 on are the
+// Wd = 128 objects; parts 9 / 11 = the folded Wd = 256 instances of head class 0 / 1; parts 13 / 15 = the external-encoding (hash-grid)
+// instances of Wd = 256 / head class 1 and their TRAIN instances): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instance, part 2 = Wd = 128 / class 1,
 // parts 3 / 4 = their TRAIN instances, parts 5 / 6 = Wd = 256 / class 1 and Wd = 128 / class 0, parts 7 / 8 = their TRAIN instances.
 #ifndef NEFES_TU_PART
 #define NEFES_TU_PART 0
@@ -617,6 +620,8 @@ int nefes_bwd_h3_launch_part7(int which, const FieldBwdH3Args& a, hipStream_t st
 int nefes_bwd_h3_launch_part8(int which, const FieldBwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 128, class 0
 int nefes_bwd_h3_launch_part9(int which, const FieldBwdH3Args& a, hipStream_t st);   // folded (FOLD) instance, Wd = 256, class 0
 int nefes_bwd_h3_launch_part11(int which, const FieldBwdH3Args& a, hipStream_t st);  // folded (FOLD) instance, Wd = 256, class 1
+int nefes_bwd_h3_launch_part13(int which, const FieldBwdH3Args& a, hipStream_t st);  // external encoding / hash grid, Wd = 256, class 1
+int nefes_bwd_h3_launch_part15(int which, const FieldBwdH3Args& a, hipStream_t st);  // ... their TRAIN instances
 
 #if NEFES_TU_PART == 1
 int nefes_bwd_h3_launch_part1(int which, const FieldBwdH3Args& a, hipStream_t st) {
@@ -684,6 +689,26 @@ int nefes_bwd_h3_launch_part11(int which, const FieldBwdH3Args& a, hipStream_t s
     if (which == BWD_H3_FULL) return launch_bwd_h3<256, 9 | NEFES_H3B_FOLD, NEFES_XYZ_FREQ10>(a, st);
     return NEFES_E_UNSUPPORTED;
 }
+#elif NEFES_TU_PART == 13     // (gap-by-gap schedule, like part 0)
+// Head class 1 on a SUPPLIED encoding.  The instance with the hash grid in its epilogue, <256, 9, NEFES_XYZ_HASHGRID_FUSED>, is not
+// built: on the gap-by-gap schedule hipcc relocates accumulator tiles inside the asm-scheduled runs (v_accvgpr_mov one to six wait
+// states behind the asm MFMA that writes the tile: tools/hazard_lint.py rule B1 -- 512 registers, no scratch), the failure the class-0
+// instance avoids by leaving the schedule, and the seventy-two upstream values of this class leave it less room, not more.  Such
+// networks take nefes_hashgrid_fwd / _bwd_x around the EXT instance (ops.hashgrid_fused_ok).
+// make EXTRA_H3=-DNEFES_H3_HG_CLASS1 builds it (experiments: the linter and tests/test_pack_stream.py are red on that library).
+int nefes_bwd_h3_launch_part13(int which, const FieldBwdH3Args& a, hipStream_t st) {
+    if (which == BWD_H3_EXT) return launch_bwd_h3<256, 9, NEFES_XYZ_EXTERNAL32>(a, st);
+#ifdef NEFES_H3_HG_CLASS1
+    if (which == BWD_H3_HG) return launch_bwd_h3<256, 9, NEFES_XYZ_HASHGRID_FUSED>(a, st);
+#endif
+    return NEFES_E_UNSUPPORTED;
+}
+#elif NEFES_TU_PART == 15
+int nefes_bwd_h3_launch_part15(int which, const FieldBwdH3Args& a, hipStream_t st) {
+    if (which == BWD_H3_TRAIN_EXT_STATIC) return launch_bwd_h3<256, 9, NEFES_XYZ_EXTERNAL32, false, true>(a, st);
+    if (which == BWD_H3_TRAIN_EXT_FULL) return launch_bwd_h3<256, 9, NEFES_XYZ_EXTERNAL32, true, true>(a, st);
+    return NEFES_E_UNSUPPORTED;
+}
 #else   // part 0
 
 // The fused dX chain of the train-mode backward on the fp16 pipe: as nefes_field_bwd_train (field_bwd.hip), same `dacts` rows.
@@ -723,7 +748,7 @@ extern "C" int nefes_field_bwd_train_h3(const NefesNetDesc* desc, const void* pa
 }
 
 // The same for a NEFES_XYZ_EXTERNAL32 network (nefes_field_fwd_train_h3_ext): `dacts` as above, g_xyz_enc [N*S, 32] = d loss / d its
-// encoding (what the hash grid's table gradient consumes), g_viewdirs_s per sample.  Width 256, head class 0.
+// encoding (what the hash grid's table gradient consumes), g_viewdirs_s per sample.  Width 256, both head classes.
 extern "C" int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* viewdirs,
                                             const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* dacts,
                                             float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
@@ -732,7 +757,8 @@ extern "C" int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void
     if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
     const bool full = mode == NEFES_FIELD_FULL;
     if (full && !desc->has_transient) return NEFES_E_UNSUPPORTED;
-    if (desc->width != 256 || nefes_head_class(desc->feat_dim) != 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
+    const int cls = nefes_head_class(desc->feat_dim);
+    if (desc->width != 256 || cls < 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
     if (desc->fold_final) return NEFES_E_UNSUPPORTED;
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
@@ -750,7 +776,8 @@ extern "C" int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void
     a.n_tiles = (int)((a.M + 127) / 128);
     a.dacts = dacts; a.gout = 0; a.hg_table = nullptr; a.g_gmap = nullptr;
     a.rows = nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END);
-    return nefes_bwd_h3_launch_part3(full ? BWD_H3_TRAIN_EXT_FULL : BWD_H3_TRAIN_EXT_STATIC, a, (hipStream_t)stream);
+    const int which = full ? BWD_H3_TRAIN_EXT_FULL : BWD_H3_TRAIN_EXT_STATIC;
+    return cls == 0 ? nefes_bwd_h3_launch_part3(which, a, (hipStream_t)stream) : nefes_bwd_h3_launch_part15(which, a, (hipStream_t)stream);
 }
 
 // nefes_field_bwd_static on the fp16 pipe: backward-to-inputs of a NEFES_FIELD_STATIC forward with frozen weights (round 5: every
@@ -831,8 +858,8 @@ static int field_bwd_h3_impl(const NefesNetDesc* desc, const void* packed, int N
     const int cls = nefes_head_class(desc->feat_dim);          // compiled set: as nefes_field_fwd_h3
     if (cls < 0) return NEFES_E_UNSUPPORTED;
     if (fh) return nefes_bwd_h3_launch_part6(BWD_H3_FH, a, st);
-    if (desc->width == 256 && fused_grid) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_HG, a, st) : NEFES_E_UNSUPPORTED;
-    if (desc->width == 256 && ext) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_EXT, a, st) : NEFES_E_UNSUPPORTED;
+    if (desc->width == 256 && fused_grid) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_HG, a, st) : nefes_bwd_h3_launch_part13(BWD_H3_HG, a, st);
+    if (desc->width == 256 && ext) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_EXT, a, st) : nefes_bwd_h3_launch_part13(BWD_H3_EXT, a, st);
     if (desc->width == 256 && fold) return cls == 0 ? nefes_bwd_h3_launch_part9(BWD_H3_FULL, a, st) : nefes_bwd_h3_launch_part11(BWD_H3_FULL, a, st);
     if (desc->width == 256) return cls == 0 ? launch_bwd_h3<256, 2, NEFES_XYZ_FREQ10>(a, st) : nefes_bwd_h3_launch_part5(BWD_H3_FULL, a, st);
     if (desc->width == 128 && !ext) return cls == 1 ? nefes_bwd_h3_launch_part2(BWD_H3_FULL, a, st) : nefes_bwd_h3_launch_part6(BWD_H3_FULL, a, st);

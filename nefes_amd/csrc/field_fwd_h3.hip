@@ -541,8 +541,9 @@ static int launch_h3(const FieldFwdH3Args& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// Kernel instances spread over eleven objects built from this one source (Makefile: -DNEFES_TU_PART=0..9, 11; even parts from 2 on
-// are the Wd = 128 objects; parts 9 / 11 = the folded Wd = 256 instances of head class 0 / 1): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instances, part 2 = Wd = 128 / class 1,
+// Kernel instances spread over thirteen objects built from this one source (Makefile: -DNEFES_TU_PART=0..9, 11, 13, 15; even parts from 2 on
+// are the Wd = 128 objects; parts 9 / 11 = the folded Wd = 256 instances of head class 0 / 1; parts 13 / 15 = the external-encoding
+// (hash-grid) instances of Wd = 256 / head class 1 and their TRAIN instances): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instances, part 2 = Wd = 128 / class 1,
 // parts 3 / 4 = their TRAIN instances, parts 5 / 6 = Wd = 256 / class 1 and Wd = 128 / class 0, parts 7 / 8 = their TRAIN instances.
 #ifndef NEFES_TU_PART
 #define NEFES_TU_PART 0
@@ -559,6 +560,8 @@ int nefes_fwd_h3_launch_part7(int which, const FieldFwdH3Args& a, hipStream_t st
 int nefes_fwd_h3_launch_part8(int which, const FieldFwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 128, class 0
 int nefes_fwd_h3_launch_part9(int which, const FieldFwdH3Args& a, hipStream_t st);   // folded (FOLD) instances, Wd = 256, class 0
 int nefes_fwd_h3_launch_part11(int which, const FieldFwdH3Args& a, hipStream_t st);  // folded (FOLD) instances, Wd = 256, class 1
+int nefes_fwd_h3_launch_part13(int which, const FieldFwdH3Args& a, hipStream_t st);  // external encoding / hash grid, Wd = 256, class 1
+int nefes_fwd_h3_launch_part15(int which, const FieldFwdH3Args& a, hipStream_t st);  // ... their TRAIN instances
 
 
 #if NEFES_TU_PART == 1
@@ -645,6 +648,26 @@ int nefes_fwd_h3_launch_part11(int which, const FieldFwdH3Args& a, hipStream_t s
     if (which == H3_FULL) return launch_h3<NEFES_FIELD_FULL_FOLD, NEFES_XYZ_FREQ10, 256, 5>(a, st);
     return NEFES_E_UNSUPPORTED;
 }
+#elif NEFES_TU_PART == 13
+// The reference's FEATURE_DIM = 128 on a hash grid: the full pass with the five-tile rgb+feature head on a SUPPLIED encoding.  (The
+// sigma-only pass has no rgb head: part 1's H3_EXT_SIGMA / H3_HG_SIGMA serve both classes.)  No fused-gather instance of this class:
+// its forward <FULL, HASHGRID_FUSED, 256, 5> builds clean (256 + 256 registers, no scratch), its backward does not keep the house rules
+// (field_bwd_h3.hip part 13), and a forward alone would leave the pair's masks without a consumer -- DESIGN.md 4.8.
+// Experiments: make EXTRA_H3=-DNEFES_H3_HG_CLASS1 builds the pair and routes the class-1 full pass of the _hashgrid entry points to it
+// (re-check the registers with tools/kernel_resources.py and the moves with tools/hazard_lint.py after a compiler update).
+int nefes_fwd_h3_launch_part13(int which, const FieldFwdH3Args& a, hipStream_t st) {
+    if (which == H3_EXT_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_EXTERNAL32, 256, 5>(a, st);
+#ifdef NEFES_H3_HG_CLASS1
+    if (which == H3_HG_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_HASHGRID_FUSED, 256, 5>(a, st);
+#endif
+    return NEFES_E_UNSUPPORTED;
+}
+#elif NEFES_TU_PART == 15
+int nefes_fwd_h3_launch_part15(int which, const FieldFwdH3Args& a, hipStream_t st) {
+    if (which == H3_TRAIN_EXT_STATIC) return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_EXTERNAL32, 256, 5, true>(a, st);
+    if (which == H3_TRAIN_EXT_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_EXTERNAL32, 256, 5, true>(a, st);
+    return NEFES_E_UNSUPPORTED;
+}
 #else   // part 0
 
 // Train-mode forward on the fp16 pipe: as nefes_field_fwd_train (field_fwd.hip), same `acts` rows, same masks, same raw_t.
@@ -683,13 +706,14 @@ extern "C" int nefes_field_fwd_train_h3(const NefesNetDesc* desc, const void* pa
 }
 
 // Train-mode forward of a NEFES_XYZ_EXTERNAL32 network on its caller-supplied encoding xyz_enc [N*S, 32] (a trainable hash grid):
-// as nefes_field_fwd_train_h3, with the 32 features in rows 0..31 of the E block, natural order.  Width 256, head class 0.
+// as nefes_field_fwd_train_h3, with the 32 features in rows 0..31 of the E block, natural order.  Width 256, both head classes.
 extern "C" int nefes_field_fwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* xyz_enc,
                                             const float* viewdirs, float* raw_t, float* acts, uint32_t* masks, void* stream) {
     if (!desc || !packed || !xyz_enc || !raw_t || !acts || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
     if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_UNSUPPORTED;
     if (mode == NEFES_FIELD_FULL && !desc->has_transient) return NEFES_E_BADARG;
-    if (desc->width != 256 || nefes_head_class(desc->feat_dim) != 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
+    const int cls = nefes_head_class(desc->feat_dim);
+    if (desc->width != 256 || cls < 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
     if (desc->fold_final) return NEFES_E_UNSUPPORTED;
     NefesBlobInfo info;
     int rc = nefes_blob_info(desc, &info);
@@ -710,7 +734,8 @@ extern "C" int nefes_field_fwd_train_h3_ext(const NefesNetDesc* desc, const void
     a.rows = nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END);
     a.z_row = 0; a.gout = 0; a.hg_table = nullptr;
     magic_div((uint32_t)S, a.s_magic, a.s_shift);
-    return nefes_fwd_h3_launch_part3(mode == NEFES_FIELD_STATIC ? H3_TRAIN_EXT_STATIC : H3_TRAIN_EXT_FULL, a, (hipStream_t)stream);
+    const int which = mode == NEFES_FIELD_STATIC ? H3_TRAIN_EXT_STATIC : H3_TRAIN_EXT_FULL;
+    return cls == 0 ? nefes_fwd_h3_launch_part3(which, a, (hipStream_t)stream) : nefes_fwd_h3_launch_part15(which, a, (hipStream_t)stream);
 }
 
 static int field_fwd_h3_impl(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
@@ -724,11 +749,11 @@ static int field_fwd_h3_impl(const NefesNetDesc* desc, const void* packed, int m
     if (mode != NEFES_FIELD_SIGMA && mode != NEFES_FIELD_FULL && mode != NEFES_FIELD_STATIC) return NEFES_E_UNSUPPORTED;
     if (mode == NEFES_FIELD_FULL && (!viewdirs || !desc->has_transient)) return NEFES_E_BADARG;
     if (mode == NEFES_FIELD_STATIC && (!viewdirs || ext)) return ext ? NEFES_E_UNSUPPORTED : NEFES_E_BADARG;   // (frequency embedding only)
-    // compiled set: widths 128 / 256 x head classes 0 / 1 (layout.h) with the frequency embedding; width 256 / class 0 with an
-    // external 32-feature embedding
+    // compiled set: widths 128 / 256 x head classes 0 / 1 (layout.h) with the frequency embedding; width 256 x head classes 0 / 1 with
+    // an external 32-feature embedding (the hash grid gathered by the kernel itself: class 0, and the sigma-only pass of either class)
     const int cls = nefes_head_class(desc->feat_dim);
     const bool big = desc->width == 256, small = desc->width == 128 && !ext;
-    if (!(big || small) || cls < 0 || (ext && cls != 0) || (desc->xyz_encoding != NEFES_XYZ_FREQ10 && !ext)) return NEFES_E_UNSUPPORTED;
+    if (!(big || small) || cls < 0 || (desc->xyz_encoding != NEFES_XYZ_FREQ10 && !ext)) return NEFES_E_UNSUPPORTED;
     // a folded pack (NefesNetDesc.fold_final): folded instances exist for the full pass at width 256 with the frequency embedding;
     // its sigma-only stream is the unfolded one.  No other kernel may read the folded head segments.
     const bool fold = desc->fold_final != 0;
@@ -774,8 +799,12 @@ static int field_fwd_h3_impl(const NefesNetDesc* desc, const void* packed, int m
         if (big) return cls == 0 ? nefes_fwd_h3_launch_part1(H3_STATIC, a, st) : nefes_fwd_h3_launch_part5(H3_STATIC, a, st);
         return cls == 1 ? nefes_fwd_h3_launch_part2(H3_STATIC, a, st) : nefes_fwd_h3_launch_part6(H3_STATIC, a, st);
     }
-    if (fused_grid) return nefes_fwd_h3_launch_part1(mode == NEFES_FIELD_SIGMA ? H3_HG_SIGMA : H3_HG_FULL, a, st);
-    if (ext) return nefes_fwd_h3_launch_part1(mode == NEFES_FIELD_SIGMA ? H3_EXT_SIGMA : H3_EXT_FULL, a, st);
+    // (the sigma-only instances have no rgb head: one per encoding serves both head classes)
+    if (fused_grid && mode == NEFES_FIELD_SIGMA) return nefes_fwd_h3_launch_part1(H3_HG_SIGMA, a, st);
+    // (class 1: the separate launches -- part 13 answers NEFES_E_UNSUPPORTED unless built with NEFES_H3_HG_CLASS1)
+    if (fused_grid) return cls == 0 ? nefes_fwd_h3_launch_part1(H3_HG_FULL, a, st) : nefes_fwd_h3_launch_part13(H3_HG_FULL, a, st);
+    if (ext && mode == NEFES_FIELD_SIGMA) return nefes_fwd_h3_launch_part1(H3_EXT_SIGMA, a, st);
+    if (ext) return cls == 0 ? nefes_fwd_h3_launch_part1(H3_EXT_FULL, a, st) : nefes_fwd_h3_launch_part13(H3_EXT_FULL, a, st);
     if (small) {
         if (mode == NEFES_FIELD_SIGMA) return nefes_fwd_h3_launch_part2(H3_SIGMA, a, st);
         return cls == 1 ? nefes_fwd_h3_launch_part2(H3_FULL, a, st) : nefes_fwd_h3_launch_part6(H3_FULL, a, st);

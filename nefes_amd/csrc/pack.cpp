@@ -503,7 +503,7 @@ bool build(const NefesNetDesc* d, const float* const* tensors, Net& n, Stream (&
     }
     n.fold = d->fold_final != 0;
     if (n.fold) {
-        if (n.ext && !(n.W == 256 && nefes_head_class(n.C) == 0)) return false;       // no fp16 streams to fold (h3_shape below)
+        if (n.ext && !(n.W == 256 && nefes_head_class(n.C) == 0)) return false;       // (no folded instance serves an external encoding; class 1 keeps the refusal)
         const size_t me = (size_t)n.W2 * (n.W + 27);
         n.fd_w.assign(me, 0.f); n.ft_w.assign(me, 0.f); n.fdt_w.assign(2 * me, 0.f);
         n.fd_b.assign(n.W2, 0.f); n.ft_b.assign(n.W2, 0.f);
@@ -528,9 +528,10 @@ bool build(const NefesNetDesc* d, const float* const* tensors, Net& n, Stream (&
         add_backward(n, st[NEFES_STREAM_BWD_FULL]);
     }
     // bf16x6 instances exist for the two canonical shapes only (and the sigma-only pass at every Wd = 256 network); the fp16 two-part
-    // instances for both widths x both head classes (frequency embedding), and for Wd = 256 / class 0 with an external embedding
+    // instances for both widths x both head classes (frequency embedding), and for Wd = 256 x both head classes with an external
+    // embedding (the head padded to the class exactly as for the frequency networks: n.NTR tiles, nefes_head_kr16 k-steps)
     const bool big = n.W == 256, small = n.W == 128 && n.C == 128 && !n.ext;
-    const bool h3_shape = !n.ext || (n.W == 256 && nefes_head_class(n.C) == 0);
+    const bool h3_shape = !n.ext || n.W == 256;
     if (big || small) add_trunk(n, st[NEFES_STREAM_FWD_SIGMA_X6], 1);
     if (n.transient && (big || small) && (small || n.C == 16)) {
         add_trunk(n, st[NEFES_STREAM_FWD_FULL_X6], 1);

@@ -216,7 +216,7 @@ class NeRFH_NFF(nn.Module):
         freq_xyz = self.in_channels_xyz in range(3, 64, 6)
         return (self.D == 8 and self.skips == [4] and (freq_xyz or self.in_channels_xyz == 32) and self.in_channels_dir in range(3, 28, 6)
                 and self.W in (128, 256) and self.out_ch_size != 3 and 0 < self.W_features <= ops.HEAD_MAX_C
-                and (freq_xyz or (self.W == 256 and ops.head_class(self.W_features) == 0)))
+                and (freq_xyz or self.W == 256))
 
     # layers whose input holds an embedding: (name, column where the embedding starts, its width here, its width in the kernels)
     def _embedding_columns(self):

@@ -167,7 +167,7 @@ def load():
 
 
 COMPILED_SET = ("fp16 two-part instances (default): widths 128 / 256 x feature heads of 0..29 or 30..141 channels with the frequency "
-                "embedding, width 256 x 0..29 channels with an external 32-feature embedding; bf16x6 and fp32-MFMA instances "
+                "embedding, width 256 x 0..29 or 30..141 channels with an external 32-feature embedding (hash grid); bf16x6 and fp32-MFMA instances "
                 "(NEFES_SPLIT=x6 / f32): width 256 x 16 channels and width 128 x 128 channels only")
 GENERIC_SET = ("generic fp32-MFMA kernels (frozen weights, frequency embedding): any width that is a multiple of 32 from 32 to 512, "
                "depth 1..8 with skips=[4] (or none when depth <= 4), feature heads of 1..141 channels")

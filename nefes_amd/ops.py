@@ -395,11 +395,11 @@ def canonical_shape(pk: PackedField):
 
 def h3_shape(pk: PackedField):
     """Shapes with fp16 two-part instances (csrc/field_fwd_h3.hip nefes_field_fwd_h3): both widths x both head classes with the
-    frequency embedding; width 256 / class 0 with an external embedding."""
+    frequency embedding; width 256 x both head classes with an external embedding."""
     cls = head_class(pk.feat_dim)
     if pk.width not in (128, 256) or cls < 0:
         return False
-    return True if pk.xyz_encoding == L.XYZ_FREQ10 else (pk.width == 256 and cls == 0)
+    return True if pk.xyz_encoding == L.XYZ_FREQ10 else pk.width == 256
 
 
 # Frozen networks on the fp16 pipe: xyz_encoding_final (a Linear with no activation behind it) is multiplied into dir_encoding /
@@ -1073,7 +1073,9 @@ FUSED_HASHGRID = os.environ.get("NEFES_FUSED_HASHGRID", "1") != "0"
 
 
 def hashgrid_fused_ok(pk, grid):
-    """The fp16 two-part field kernels can gather this hash grid themselves: width 256, head class 0, sixteen levels x two features."""
+    """The fp16 two-part field kernels can gather this hash grid themselves: width 256, head class 0, sixteen levels x two features.
+    (Head class 1 -- the 128-channel feature head -- has instances on a SUPPLIED encoding only, csrc/field_bwd_h3.hip part 13: its
+    renders take HashGridEncode + FieldFromEncoding, and with them the four-launch coarse pass.)"""
     return (FUSED_HASHGRID and isinstance(grid, HashGrid) and _h3(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32 and pk.width == 256
             and head_class(pk.feat_dim) == 0 and grid.desc.n_levels == 16 and grid.desc.n_features == 2)
 

@@ -151,9 +151,9 @@ def fp16_pipe(pk):
 
 
 def ext_pipe(pk):
-    """The train-mode instances of a network on an external 32-feature encoding (a hash grid): fp16 two-part pipe, width 256, head
-    class 0 (csrc/field_fwd_h3.hip H3_TRAIN_EXT_*)."""
-    return ops._h3(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32 and pk.width == 256 and ops.head_class(pk.feat_dim) == 0
+    """The train-mode instances of a network on an external 32-feature encoding (a hash grid): fp16 two-part pipe, width 256, either
+    head class (csrc/field_fwd_h3.hip H3_TRAIN_EXT_*, parts 3 / 15)."""
+    return ops._h3(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32 and pk.width == 256 and ops.head_class(pk.feat_dim) >= 0
 
 
 FUSED_DX = True       # one fused backward launch (nefes_field_bwd_train) instead of the layer-by-layer nefes_train_dx chain
@@ -339,7 +339,7 @@ def field_train(net, mode, rays_o, rays_d, viewdirs, z):
 class FieldTrainEncoded(torch.autograd.Function):
     """FieldTrain for a network on an external 32-feature xyz encoding (a hash grid, BASELINE configs[3]): raw_t [N,R,S] from
     enc [N,S,32] and viewdirs [N,3], differentiable w.r.t. enc (-> the grid's table and the sample positions, HashGridEncode),
-    viewdirs and the network parameters (*params in `param_names` order).  fp16 two-part train instances, width 256, head class 0."""
+    viewdirs and the network parameters (*params in `param_names` order).  fp16 two-part train instances, width 256, both head classes."""
 
     @staticmethod
     def forward(ctx, enc, viewdirs, net, mode, *params):
@@ -348,7 +348,7 @@ class FieldTrainEncoded(torch.autograd.Function):
         if mode not in (L.FIELD_STATIC, L.FIELD_FULL):
             raise ValueError("nefes_amd: train mode evaluates the static or the full head")
         if not ext_pipe(pk):
-            raise NotImplementedError(f"nefes_amd: train mode on an external (hash-grid) encoding is built for width 256 with 3 + f_dim <= 32 "
+            raise NotImplementedError(f"nefes_amd: train mode on an external (hash-grid) encoding is built for width 256 with 3 + f_dim <= 144 "
                                       f"on the fp16 two-part instances (NEFES_SPLIT=h3); got W={pk.width}, f_dim={pk.feat_dim}, "
                                       f"NEFES_SPLIT={ops.SPLIT}.  Compiled: {ops.COMPILED_SET}")
         N, S = enc.shape[0], enc.shape[1]
