@@ -26,7 +26,9 @@
 extern "C" {
 #endif
 
-#define NEFES_ABI_VERSION 17
+#define NEFES_ABI_VERSION 18
+/* layout version of the blob nefes_pack_weights writes (second header word): moves when that layout does, not with every new call */
+#define NEFES_BLOB_FORMAT 17
 
 #define NEFES_E_BADARG (-1)     /* null pointer / non-positive size */
 #define NEFES_E_UNSUPPORTED (-2) /* width / feat_dim / sample count outside the compiled set */
@@ -330,6 +332,26 @@ int nefes_field_fwd_generic(const NefesGenericNetDesc* desc, const void* packed,
 int nefes_field_bwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
                             const float* rays_d, const float* z, const float* pts, const float* viewdirs, const float* raw_t,
                             const float* g_raw_t, const uint32_t* masks, float* g_pts, float* g_viewdirs_s, void* stream);
+/* The same scatter as nefes_generic_pack from DEVICE tensors (`tensors`: a host array of device pointers, same order and shapes) into
+ * a device blob that was zeroed once: plain stores, the padding is never written.  One small launch per tensor pair. */
+int nefes_generic_pack_device(const NefesGenericNetDesc* desc, const float* const* tensors, int n_tensors, void* blob,
+                              size_t blob_bytes, void* stream);
+/* Train mode of the generic kernels (weight gradients for any width / depth).  `acts` / `dacts`: the train layout below
+ * ([ceil(N*S/128)][rows][128], nefes_train_off), rows = nefes_generic_train_rows(desc), first row of block b (the NEFES_TB_* enumeration
+ * of nefes_amd/csrc/layout.h: E = 0, DV = 1, L1..L8 = 2..9, FINAL = 10, DIR = 11, T0..T2 = 12..14, RGB = 15, SIG = 16, TH = 17, END = 18)
+ * = nefes_generic_train_row_offset(desc, b).  Blocks a network does not have (layers above its depth, T0..T2 / TH without the
+ * transient head) are empty; every block is a multiple of 32 rows (W/2 and the heads padded with zero rows).  Unlike the tuned train
+ * kernels, E / DV are in the reference's feature order and `acts` holds layer OUTPUTS (after ReLU): run nefes_train_dw_bias with
+ * x_relu = 0.  `dacts` holds the gradient w.r.t. every layer's pre-activation.  Columns of samples >= N*S are written as zeros. */
+size_t nefes_generic_train_rows(const NefesGenericNetDesc* desc);
+int nefes_generic_train_row_offset(const NefesGenericNetDesc* desc, int block);
+/* mode NEFES_FIELD_STATIC or NEFES_FIELD_FULL (NEFES_E_BADARG otherwise, and for any null buffer); masks as nefes_field_fwd_generic */
+int nefes_field_fwd_train_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
+                                  const float* rays_d, const float* z, const float* viewdirs, float* raw_t, float* acts, uint32_t* masks,
+                                  void* stream);
+int nefes_field_bwd_train_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
+                                  const float* rays_d, const float* z, const float* viewdirs, const float* raw_t, const float* g_raw_t,
+                                  const uint32_t* masks, float* dacts, float* g_pts, float* g_viewdirs_s, void* stream);
 
 /* ---- train mode: weight gradients (script/run_nefes.py:42-108 `loss.backward()` through models/nerfh_nff.py:525-576) ----
  * Buffers `acts` / `dacts`: fp32 [n_tiles = ceil(N*S/128)][rows x 128 samples], rows = nefes_train_rows(desc); inside a tile

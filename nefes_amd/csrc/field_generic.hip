@@ -16,10 +16,17 @@
 // ReLU masks: one word per (tile, hidden layer, row block, lane): bit 16 c + r = accumulator r of column block c was > 0.  The
 // backward's transposed product leaves the gradient of a layer's output in exactly the accumulator that produced it, so it tests the
 // same bit -- no recomputation of the forward (which would double the backward's matrix work) and 1 bit per activation of traffic.
+//
+// Train mode (nefes_field_fwd_train_generic / nefes_field_bwd_train_generic): the same two bodies with TRAIN set also copy, from the
+// LDS buffers they sit in anyway, every weight-gradient operand to the train-layout buffers of csrc/train.hip (layout.h
+// nefes_train_off): the forward the embeddings and every hidden layer's OUTPUT (after ReLU) to `acts`, the backward the gradient
+// with respect to every layer's pre-activation to `dacts`.  nefes_train_dw_bias then forms dW = G X^T unchanged; the block ->
+// first-row map is gen_train_rows (nefes_generic_train_row_offset).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/nefes_hip.h"
+#include "layout.h"
 
 #include <string.h>
 
@@ -133,6 +140,33 @@ extern "C" size_t nefes_generic_mask_bytes(const NefesGenericNetDesc* desc, int6
     return (size_t)((M + TS - 1) / TS) * g.mask_words * 64 * 4;
 }
 
+// The packers' table: tensor pair t (weight, bias; torch layout [rows][src_cols]) fills rows [m0, m0 + rows) of layer li; source
+// columns [emb_at, emb_at + emb) are an embedding padded to emb_pad in the kernels' K order, so column c -> k = gen_put_k.
+struct GenPut { int li, m0, rows, t, src_cols, emb, emb_at, emb_pad; };
+__host__ __device__ static inline int gen_put_k(const GenPut& p, int c) { return c < p.emb_at + p.emb ? c : c + (p.emb_pad - p.emb); }
+template <class F>
+static void gen_for_each_put(const GenLayout& g, F f) {
+    const int W = g.W, D = g.D, H = W / 2;
+    int t = 0;
+    for (int i = 0; i < D; ++i, t += 2) {
+        if (i == 0) f(GenPut{i, 0, W, t, 63, 63, 0, GEN_E_ROWS});
+        else if (i == g.skip) f(GenPut{i, 0, W, t, 63 + W, 63, 0, GEN_E_ROWS});
+        else f(GenPut{i, 0, W, t, W, 0, 0, 0});
+    }
+    f(GenPut{g.iFINAL, 0, W, t, W, 0, 0, 0}); t += 2;
+    f(GenPut{g.iDIR, 0, H, t, W + 27, 27, W, GEN_DV_ROWS}); t += 2;
+    f(GenPut{g.iSIGMA, 0, 1, t, W, 0, 0, 0}); t += 2;
+    f(GenPut{g.iRGB, 0, 3 + g.C, t, H, 0, 0, 0}); t += 2;
+    if (g.fine) {
+        f(GenPut{g.iT0, 0, H, t, W + 27, 27, W, GEN_DV_ROWS}); t += 2;
+        f(GenPut{g.iT1, 0, H, t, H, 0, 0, 0}); t += 2;
+        f(GenPut{g.iT2, 0, H, t, H, 0, 0, 0}); t += 2;
+        f(GenPut{g.iTH, 3, 1, t, H, 0, 0, 0}); t += 2;      // transient sigma
+        f(GenPut{g.iTH, 0, 3, t, H, 0, 0, 0}); t += 2;      // transient rgb
+        f(GenPut{g.iTH, 4, 1, t, H, 0, 0, 0}); t += 2;      // transient beta
+    }
+}
+
 // tensors: (weight, bias) per layer: xyz_encoding_1..D, xyz_encoding_final, dir_encoding.0, static_sigma.0, static_rgb.0
 // [, transient_encoding.0/.2/.4, transient_sigma.0, transient_rgb.0, transient_beta.0]; torch layout [out, in], embeddings at their
 // full 63 / 27 features.
@@ -142,49 +176,100 @@ extern "C" int nefes_generic_pack(const NefesGenericNetDesc* desc, const float* 
     int rc = gen_layout(desc, &g);
     if (rc) return rc;
     if (!tensors || !blob) return NEFES_E_BADARG;
-    const int W = g.W, D = g.D, H = W / 2;
-    if (n_tensors != 2 * (D + (g.fine ? 10 : 4)) || blob_bytes < (size_t)g.total_floats * 4) return NEFES_E_BADARG;
+    if (n_tensors != 2 * (g.D + (g.fine ? 10 : 4)) || blob_bytes < (size_t)g.total_floats * 4) return NEFES_E_BADARG;
     for (int i = 0; i < n_tensors; ++i)
         if (!tensors[i]) return NEFES_E_BADARG;
     float* out = (float*)blob;
     memset(out, 0, (size_t)g.total_floats * 4);
-    // put rows [m0, m0 + rows) of layer li from a [rows][src_ld] matrix: source column c -> k = kmap(c)
-    auto put = [&](int li, int m0, int rows, const float* w, const float* b, int src_cols, int emb, int emb_at, int emb_pad) {
-        const GenLayer& l = g.L[li];
-        for (int m = 0; m < rows; ++m) {
-            for (int c = 0; c < src_cols; ++c) {
-                // columns [emb_at, emb_at + emb) are an embedding padded to emb_pad in the kernel's K order
-                const int k = c < emb_at + emb ? c : c + (emb_pad - emb);
-                const float v = w[(size_t)m * src_cols + c];
-                out[l.wt + (long long)k * l.Mp + (m0 + m)] = v;
-                out[l.wb + (long long)(m0 + m) * l.Kp + k] = v;
+    gen_for_each_put(g, [&](const GenPut& p) {
+        const GenLayer& l = g.L[p.li];
+        const float *w = tensors[p.t], *b = tensors[p.t + 1];
+        for (int m = 0; m < p.rows; ++m) {
+            for (int c = 0; c < p.src_cols; ++c) {
+                const int k = gen_put_k(p, c);
+                const float v = w[(size_t)m * p.src_cols + c];
+                out[l.wt + (long long)k * l.Mp + (p.m0 + m)] = v;
+                out[l.wb + (long long)(p.m0 + m) * l.Kp + k] = v;
             }
-            out[l.bias + m0 + m] = b[m];
+            out[l.bias + p.m0 + m] = b[m];
         }
-    };
-    int t = 0;
-    for (int i = 0; i < D; ++i, t += 2) {
-        if (i == 0) put(i, 0, W, tensors[t], tensors[t + 1], 63, 63, 0, GEN_E_ROWS);
-        else if (i == g.skip) put(i, 0, W, tensors[t], tensors[t + 1], 63 + W, 63, 0, GEN_E_ROWS);
-        else put(i, 0, W, tensors[t], tensors[t + 1], W, 0, 0, 0);
-    }
-    put(g.iFINAL, 0, W, tensors[t], tensors[t + 1], W, 0, 0, 0); t += 2;
-    put(g.iDIR, 0, H, tensors[t], tensors[t + 1], W + 27, 27, W, GEN_DV_ROWS); t += 2;
-    put(g.iSIGMA, 0, 1, tensors[t], tensors[t + 1], W, 0, 0, 0); t += 2;
-    put(g.iRGB, 0, 3 + g.C, tensors[t], tensors[t + 1], H, 0, 0, 0); t += 2;
-    if (g.fine) {
-        put(g.iT0, 0, H, tensors[t], tensors[t + 1], W + 27, 27, W, GEN_DV_ROWS); t += 2;
-        put(g.iT1, 0, H, tensors[t], tensors[t + 1], H, 0, 0, 0); t += 2;
-        put(g.iT2, 0, H, tensors[t], tensors[t + 1], H, 0, 0, 0); t += 2;
-        put(g.iTH, 3, 1, tensors[t], tensors[t + 1], H, 0, 0, 0); t += 2;      // transient sigma
-        put(g.iTH, 0, 3, tensors[t], tensors[t + 1], H, 0, 0, 0); t += 2;      // transient rgb
-        put(g.iTH, 4, 1, tensors[t], tensors[t + 1], H, 0, 0, 0); t += 2;      // transient beta
+    });
+    return 0;
+}
+
+// The same scatter on the device (a trainable network after an optimiser step): one launch per tensor pair, plain stores, the blob's
+// padding (zeroed once at allocation) is never touched.
+__global__ __launch_bounds__(256) void gen_pack_kernel(float* __restrict__ out, long long wt, long long wb, long long bias, int Mp,
+                                                       int Kp, GenPut p, const float* __restrict__ w, const float* __restrict__ b) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.rows * p.src_cols) return;
+    const int m = idx / p.src_cols, c = idx - m * p.src_cols;
+    const int k = gen_put_k(p, c);
+    const float v = w[idx];
+    out[wt + (long long)k * Mp + (p.m0 + m)] = v;
+    out[wb + (long long)(p.m0 + m) * Kp + k] = v;
+    if (c == 0) out[bias + p.m0 + m] = b[m];
+}
+
+extern "C" int nefes_generic_pack_device(const NefesGenericNetDesc* desc, const float* const* tensors, int n_tensors, void* blob,
+                                         size_t blob_bytes, void* stream) {
+    GenLayout g;
+    int rc = gen_layout(desc, &g);
+    if (rc) return rc;
+    if (!tensors || !blob) return NEFES_E_BADARG;
+    if (n_tensors != 2 * (g.D + (g.fine ? 10 : 4)) || blob_bytes < (size_t)g.total_floats * 4) return NEFES_E_BADARG;
+    for (int i = 0; i < n_tensors; ++i)
+        if (!tensors[i]) return NEFES_E_BADARG;
+    int err = 0;
+    gen_for_each_put(g, [&](const GenPut& p) {
+        if (err) return;
+        const GenLayer& l = g.L[p.li];
+        const int n = p.rows * p.src_cols;
+        hipLaunchKernelGGL(gen_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float*)blob, l.wt,
+                           l.wb, l.bias, l.Mp, l.Kp, p, tensors[p.t], tensors[p.t + 1]);
+        err = (int)hipGetLastError();
+    });
+    return err;
+}
+
+// ---- train-mode row map: first row of block NEFES_TB_* (layout.h: E, DV, L1..L8, FINAL, DIR, T0..T2, RGB, SIG, TH, END) in a tile of
+// the `acts` / `dacts` buffers of this network.  Blocks the network does not have (layers above its depth, the transient blocks of a
+// network without that head) are empty; every block is a multiple of 32 rows.
+struct GenTrainMap { int off[NEFES_TB_END + 1]; };
+static int gen_train_map(const NefesGenericNetDesc* d, GenTrainMap* m) {
+    if (!gen_desc_ok(d)) return NEFES_E_UNSUPPORTED;
+    const int W = d->width, Hp = (W / 2 + 31) / 32 * 32, fine = d->has_transient;
+    int r = 0;
+    for (int b = 0; b <= NEFES_TB_END; ++b) {
+        m->off[b] = r;
+        if (b == NEFES_TB_E) r += GEN_E_ROWS;
+        else if (b == NEFES_TB_DV) r += GEN_DV_ROWS;
+        else if (b >= NEFES_TB_L1 && b < NEFES_TB_FINAL) r += b - NEFES_TB_L1 < d->depth ? W : 0;
+        else if (b == NEFES_TB_FINAL) r += W;
+        else if (b == NEFES_TB_DIR) r += Hp;
+        else if (b >= NEFES_TB_T0 && b <= NEFES_TB_T2) r += fine ? Hp : 0;
+        else if (b == NEFES_TB_RGB) r += (3 + d->feat_dim + 31) / 32 * 32;
+        else if (b == NEFES_TB_SIG) r += 32;
+        else if (b == NEFES_TB_TH) r += fine ? 32 : 0;
     }
     return 0;
 }
 
+extern "C" size_t nefes_generic_train_rows(const NefesGenericNetDesc* desc) {
+    GenTrainMap m;
+    return gen_train_map(desc, &m) ? 0 : (size_t)m.off[NEFES_TB_END];
+}
+
+extern "C" int nefes_generic_train_row_offset(const NefesGenericNetDesc* desc, int block) {
+    GenTrainMap m;
+    if (block < 0 || block > NEFES_TB_END) return NEFES_E_BADARG;
+    const int rc = gen_train_map(desc, &m);
+    return rc ? rc : m.off[block];
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 struct GenArgs {
+    static constexpr bool train = false;
     GenLayout g;
     const float* blob;
     const float *rays_o, *rays_d, *z, *pts, *viewdirs;
@@ -286,309 +371,77 @@ __device__ __forceinline__ void gen_embed(const GenArgs& a, long long m0, float*
     }
 }
 
-template <int NCB>
-__global__ __launch_bounds__(256, 1) void gen_fwd_kernel(GenArgs a) {
-    constexpr int TS = 32 * NCB;
-    extern __shared__ __attribute__((aligned(16))) float gen_smem[];
-    const GenLayout& g = a.g;
-    const int W = g.W, D = g.D, H = W / 2;
-    float* E = gen_smem;
-    float* DV = E + GEN_E_ROWS * TS;
-    float* X = DV + GEN_DV_ROWS * TS;
-    float* Y = X + W * TS;
-    const long long tile = blockIdx.x, m0 = tile * TS;
-    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
-    const float* blob = a.blob;
-    uint32_t* mk = a.masks ? a.masks + (tile * g.mask_words) * 64 + lane : nullptr;
+// Train mode: where a kernel's operands go.  buf = `acts` (forward) or `dacts` (backward), [tile128][rows][128] in the train layout.
+struct GenTrain {
+    float* buf;
+    int rows;
+    GenTrainMap map;
+};
 
-    gen_embed<NCB>(a, m0, E, DV);
-    __syncthreads();
-
-    // hidden layer: ReLU, mask word, activations to LDS (rows beyond m_real are zero rows of the blob: relu(0) = 0)
-    auto hidden = [&](float* out, int slot) {
-        const int so = g.slot_off[slot];
-        return [=](int rb, f32x16(&acc)[NCB]) {
-            uint32_t bits = 0u;
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = acc[c][r];
-                    bits |= (v > 0.f ? 1u : 0u) << (16 * c + r);
-                    out[(rb * 32 + gen_rho(half, r)) * TS + 32 * c + l31] = v > 0.f ? v : 0.f;
-                }
-            if (mk) mk[(so + rb) * 64] = bits;
-        };
-    };
-    auto linear = [&](float* out) {
-        return [=](int rb, f32x16(&acc)[NCB]) {
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) out[(rb * 32 + gen_rho(half, r)) * TS + 32 * c + l31] = acc[c][r];
-        };
-    };
-    // raw_t[n][ch][s] of this lane's samples
-    long long base[NCB];
-    bool live[NCB];
-#pragma unroll
-    for (int c = 0; c < NCB; ++c) {
-        const long long m = m0 + 32 * c + l31;
-        live[c] = m < a.M;
-        base[c] = live[c] ? (m / a.S) * a.R * a.S + m % a.S : 0;
-    }
-    // head: kind 0 identity, 1 softplus, 2 transient (rows 0..2 sigmoid, 3..4 softplus)
-    float* const raw = a.raw_t;
-    const long long S64 = a.S;
-    auto head = [&](int ch0, int m_real, int kind) {
-        return [=](int rb, f32x16(&acc)[NCB]) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rb * 32 + gen_rho(half, r);
-                if (row >= m_real) continue;
-#pragma unroll
-                for (int c = 0; c < NCB; ++c) {
-                    if (!live[c]) continue;
-                    float v = acc[c][r];
-                    if (kind == 1 || (kind == 2 && row >= 3)) v = softplus_ref(v);
-                    else if (kind == 2) v = sigmoid_ref(v);
-                    raw[base[c] + (long long)(ch0 + row) * S64] = v;
-                }
-            }
-        };
-    };
-
-    float *cur = X, *oth = Y;
-    {
-        const GenLayer& l = g.L[0];
-        gen_layer<NCB>(blob + l.wt, E, GEN_E_ROWS, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, hidden(cur, 0));
-    }
-    __syncthreads();
-    for (int i = 1; i < D; ++i) {
-        const GenLayer& l = g.L[i];
-        if (i == g.skip)
-            gen_layer<NCB>(blob + l.wt, E, GEN_E_ROWS, blob + l.wt + (long long)GEN_E_ROWS * l.Mp, cur, W, l.Mp, l.Mp, W / 32,
-                           blob + l.bias, hidden(oth, i));
-        else
-            gen_layer<NCB>(blob + l.wt, cur, W, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, hidden(oth, i));
-        float* t = cur; cur = oth; oth = t;
-        __syncthreads();
-    }
-    {
-        const GenLayer& l = g.L[g.iSIGMA];
-        const int ch = a.mode == NEFES_FIELD_SIGMA ? 0 : 3 + g.C;
-        gen_layer<NCB>(blob + l.wt, cur, W, nullptr, nullptr, 0, l.Mp, l.Mp, 1, blob + l.bias, head(ch, 1, 1));
-    }
-    if (a.mode == NEFES_FIELD_SIGMA) return;
-    {
-        const GenLayer& l = g.L[g.iFINAL];
-        gen_layer<NCB>(blob + l.wt, cur, W, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, linear(oth));
-    }
-    __syncthreads();
-    float *fin = oth, *gbuf = cur;
-    {
-        const GenLayer& l = g.L[g.iDIR];
-        gen_layer<NCB>(blob + l.wt, fin, W, blob + l.wt + (long long)W * l.Mp, DV, GEN_DV_ROWS, l.Mp, l.Mp, l.Mp / 32, blob + l.bias,
-                       hidden(gbuf, D));
-    }
-    __syncthreads();
-    {
-        const GenLayer& l = g.L[g.iRGB];
-        gen_layer<NCB>(blob + l.wt, gbuf, H, nullptr, nullptr, 0, l.Mp, l.Mp, l.Mp / 32, blob + l.bias, head(0, 3 + g.C, 0));
-    }
-    if (a.mode != NEFES_FIELD_FULL) return;
-    __syncthreads();
-    {
-        const GenLayer& l = g.L[g.iT0];
-        gen_layer<NCB>(blob + l.wt, fin, W, blob + l.wt + (long long)W * l.Mp, DV, GEN_DV_ROWS, l.Mp, l.Mp, l.Mp / 32, blob + l.bias,
-                       hidden(gbuf, D + 1));
-    }
-    __syncthreads();
-    {
-        const GenLayer& l = g.L[g.iT1];
-        gen_layer<NCB>(blob + l.wt, gbuf, H, nullptr, nullptr, 0, l.Mp, l.Mp, l.Mp / 32, blob + l.bias, hidden(fin, D + 2));
-    }
-    __syncthreads();
-    {
-        const GenLayer& l = g.L[g.iT2];
-        gen_layer<NCB>(blob + l.wt, fin, H, nullptr, nullptr, 0, l.Mp, l.Mp, l.Mp / 32, blob + l.bias, hidden(gbuf, D + 3));
-    }
-    __syncthreads();
-    {
-        const GenLayer& l = g.L[g.iTH];
-        gen_layer<NCB>(blob + l.wt, gbuf, H, nullptr, nullptr, 0, l.Mp, l.Mp, 1, blob + l.bias, head(3 + g.C + 1, 5, 2));
+// rows [0, rows_p) x the tile's TS samples of block `block`: LDS [row][TS] -> the train buffer, rows >= rows_real as zeros.  Sixteen
+// bytes per lane: a row's TS / 4 quads go to consecutive lanes (one conflict-free LDS row per 16 / 8 lanes) and four consecutive rows
+// of a 16-sample group are 256 contiguous bytes of the buffer (layout.h nefes_train_off).  rows_p is a multiple of 32.
+template <int TS>
+__device__ __forceinline__ void gen_train_store(const GenTrain& t, long long m0, int block, const float* src, int rows_real, int rows_p) {
+    float* dst = t.buf + (size_t)(m0 >> 7) * t.rows * 128;
+    const int s0 = (int)(m0 & 127), row0 = t.map.off[block];
+    for (int i = threadIdx.x; i < rows_p * (TS / 4); i += 256) {
+        const int q = i % (TS / 4), r = i / (TS / 4);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < rows_real) v = *(const float4*)(src + r * TS + 4 * q);
+        *(float4*)(dst + nefes_train_off(row0 + r, s0 + 4 * q)) = v;
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// backward to the inputs (frozen weights): mode FULL or STATIC
-template <int NCB>
-__global__ __launch_bounds__(256, 1) void gen_bwd_kernel(GenArgs a) {
-    constexpr int TS = 32 * NCB;
-    extern __shared__ __attribute__((aligned(16))) float gen_smem[];
-    const GenLayout& g = a.g;
-    const int W = g.W, D = g.D, H = W / 2, C = g.C;
-    const int RB = W > GEN_HEAD_ROWS ? W : GEN_HEAD_ROWS;
-    float* gE = gen_smem;
-    float* gDV = gE + GEN_E_ROWS * TS;
-    float* A = gDV + GEN_DV_ROWS * TS;
-    float* B = A + RB * TS;
-    float* dsig = B + RB * TS;
-    const long long tile = blockIdx.x, m0 = tile * TS;
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-    const float* blob = a.blob;
-    const uint32_t* mk = a.masks + (tile * g.mask_words) * 64 + lane;
-    const bool full = a.mode == NEFES_FIELD_FULL;
-
-    // this thread's sample column for the cooperative loads (256 % TS == 0: the same for every row it touches)
-    const int s_ld = tid % TS, row_ld = tid / TS;
-    const long long m_ld = m0 + s_ld;
-    const bool live_ld = m_ld < a.M;
-    const long long base_ld = live_ld ? (m_ld / a.S) * a.R * a.S + m_ld % a.S : 0;
-    // rows [0, rows_p) of `dst` = d loss / d (pre-activation) of head channels ch0 .. ch0 + m_real - 1; kind as in the forward
-    auto load_head = [&](float* dst, int ch0, int m_real, int rows_p, int kind) {
-        for (int row = row_ld; row < rows_p; row += 256 / TS) {
-            float v = 0.f;
-            if (live_ld && row < m_real) {
-                const long long at = base_ld + (long long)(ch0 + row) * a.S;
-                v = a.g_raw_t[at];
-                if (kind == 1 || (kind == 2 && row >= 3)) v *= 1.f - expf(-a.raw_in[at]);
-                else if (kind == 2) { const float y = a.raw_in[at]; v *= y * (1.f - y); }
-            }
-            dst[row * TS + s_ld] = v;
-        }
-    };
-    // gradient of a hidden layer's output: keep where the forward's pre-activation was positive; rows < m_real only
-    auto masked = [&](float* out, int slot, int m_real, const float* wsig) {
-        const int so = g.slot_off[slot];
-        return [=](int rb, f32x16(&acc)[NCB]) {
-            const uint32_t bits = mk[(so + rb) * 64];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rb * 32 + gen_rho(half, r);
-                if (row >= m_real) continue;
-                const float ws = wsig ? wsig[row] : 0.f;
-#pragma unroll
-                for (int c = 0; c < NCB; ++c) {
-                    float v = acc[c][r];
-                    if (wsig) v += ws * dsig[32 * c + l31];
-                    out[row * TS + 32 * c + l31] = ((bits >> (16 * c + r)) & 1u) ? v : 0.f;
-                }
-            }
-        };
-    };
-    auto plain = [&](float* out, int m_real, bool accumulate) {
-        return [=](int rb, f32x16(&acc)[NCB]) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rb * 32 + gen_rho(half, r);
-                if (row >= m_real) continue;
-#pragma unroll
-                for (int c = 0; c < NCB; ++c) {
-                    float* p = out + row * TS + 32 * c + l31;
-                    *p = accumulate ? *p + acc[c][r] : acc[c][r];
-                }
-            }
-        };
-    };
-    const int HB = (H + 31) / 32;
-
-    if (tid < TS) {      // d loss / d (static density's pre-activation): a rank-1 term of the trunk's last gradient
-        float v = 0.f;
-        if (live_ld) {
-            const long long at = base_ld + (long long)(3 + C) * a.S;
-            v = a.g_raw_t[at] * (1.f - expf(-a.raw_in[at]));
-        }
-        dsig[tid] = v;
-    }
-    if (full) {
-        const GenLayer &th = g.L[g.iTH], &t2 = g.L[g.iT2], &t1 = g.L[g.iT1];
-        load_head(A, 3 + C + 1, 5, 32, 2);
-        __syncthreads();
-        gen_layer<NCB>(blob + th.wb, A, 32, nullptr, nullptr, 0, th.Kp, H, HB, nullptr, masked(B, D + 3, H, nullptr));
-        __syncthreads();
-        gen_layer<NCB>(blob + t2.wb, B, H, nullptr, nullptr, 0, t2.Kp, H, HB, nullptr, masked(A, D + 2, H, nullptr));
-        __syncthreads();
-        gen_layer<NCB>(blob + t1.wb, A, H, nullptr, nullptr, 0, t1.Kp, H, HB, nullptr, masked(B, D + 1, H, nullptr));
-        __syncthreads();
-    }
-    {
-        const GenLayer& rgb = g.L[g.iRGB];
-        load_head(A, 0, 3 + C, rgb.Mp, 0);
-        __syncthreads();
-        gen_layer<NCB>(blob + rgb.wb, A, rgb.Mp, nullptr, nullptr, 0, rgb.Kp, H, HB, nullptr, masked(B + H * TS, D, H, nullptr));
-        __syncthreads();
-    }
-    {
-        // d loss / d [final, direction embedding] = DIR^T g_g (+ T0^T g_t0)
-        const GenLayer& dir = g.L[g.iDIR];
-        const float* w0 = blob + dir.wb;
-        const float* in0 = B + H * TS;
-        const float *w1 = nullptr, *in1 = nullptr;
-        int K1 = 0;
-        if (full) { w1 = blob + g.L[g.iT0].wb; in1 = B; K1 = H; }
-        gen_layer<NCB>(w0, in0, H, w1, in1, K1, dir.Kp, W, W / 32, nullptr, plain(A, W, false));
-        gen_layer<NCB>(w0 + W, in0, H, w1 ? w1 + W : nullptr, in1, K1, dir.Kp, GEN_DV_ROWS, 1, nullptr, plain(gDV, GEN_DV_ROWS, false));
-        __syncthreads();
-    }
-    {
-        const GenLayer &fin = g.L[g.iFINAL], &sg = g.L[g.iSIGMA];
-        gen_layer<NCB>(blob + fin.wb, A, W, nullptr, nullptr, 0, fin.Kp, W, W / 32, nullptr, masked(B, D - 1, W, blob + sg.wb));
-        __syncthreads();
-    }
-    float *cur = B, *oth = A;
-    const bool have_skip = g.skip > 0 && g.skip < D;
-    for (int i = D - 1; i >= 1; --i) {
-        const GenLayer& l = g.L[i];
-        const int hoff = i == g.skip ? GEN_E_ROWS : 0;
-        gen_layer<NCB>(blob + l.wb + hoff, cur, W, nullptr, nullptr, 0, l.Kp, W, W / 32, nullptr, masked(oth, i - 1, W, nullptr));
-        if (i == g.skip)
-            gen_layer<NCB>(blob + l.wb, cur, W, nullptr, nullptr, 0, l.Kp, GEN_E_ROWS, GEN_E_ROWS / 32, nullptr, plain(gE, GEN_E_ROWS, false));
-        float* t = cur; cur = oth; oth = t;
-        __syncthreads();
-    }
-    {
-        const GenLayer& l = g.L[0];
-        gen_layer<NCB>(blob + l.wb, cur, W, nullptr, nullptr, 0, l.Kp, GEN_E_ROWS, GEN_E_ROWS / 32, nullptr, plain(gE, GEN_E_ROWS, have_skip));
-        __syncthreads();
-    }
-    // through the embeddings: d sin(f x) = f cos(f x), d cos(f x) = -f sin(f x)
-    for (int i = tid; i < 3 * TS; i += 256) {
-        const int s = i % TS, axis = i / TS;
-        const long long m = m0 + s;
-        if (m >= a.M) continue;
-        {
-            const float x = gen_coord(a, m, axis);
-            uint32_t hi, lo;
-            turns_fixed(x, hi, lo);
-            float gx = gE[axis * TS + s];
-            for (int k = 0; k < 10; ++k) {
-                const uint32_t ph = phase_of(hi, lo, k);
-                const float f = (float)(1 << k);
-                gx += gE[(3 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x40000000u));
-                gx += gE[(6 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x80000000u));
-            }
-            a.g_pts[m * 3 + axis] = gx;
-        }
-        {
-            const float x = a.viewdirs[(m / a.S) * 3 + axis];
-            uint32_t hi, lo;
-            turns_fixed(x, hi, lo);
-            float gx = gDV[axis * TS + s];
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t ph = phase_of(hi, lo, k);
-                const float f = (float)(1 << k);
-                gx += gDV[(3 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x40000000u));
-                gx += gDV[(6 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x80000000u));
-            }
-            a.g_vs[m * 3 + axis] = gx;
-        }
+// a tile past the last sample (the launch covers whole 128-sample train tiles): rows [row_lo, row_hi) of its columns are zeros, so
+// that the weight-gradient sums over the whole buffer read no unwritten memory
+template <int TS>
+__device__ __forceinline__ void gen_train_zero(const GenTrain& t, long long m0, int row_lo, int row_hi) {
+    float* dst = t.buf + (size_t)(m0 >> 7) * t.rows * 128;
+    const int s0 = (int)(m0 & 127);
+    for (int i = threadIdx.x; i < (row_hi - row_lo) * (TS / 4); i += 256) {
+        const int q = i % (TS / 4), r = row_lo + i / (TS / 4);
+        *(float4*)(dst + nefes_train_off(r, s0 + 4 * q)) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 
+struct GenArgsTrain : GenArgs {
+    static constexpr bool train = true;
+    GenTrain t;
+};
+template <class Args>
+__device__ __forceinline__ const GenTrain* gen_train_of(const Args& a) {
+    if constexpr (Args::train) return &a.t;
+    else return nullptr;
+}
+
+#define GEN_KERNEL gen_fwd_kernel
+#define GEN_ARGS GenArgs
+#include "field_generic_fwd.inc"
+#undef GEN_KERNEL
+#undef GEN_ARGS
+#define GEN_KERNEL gen_fwd_train_kernel
+#define GEN_ARGS GenArgsTrain
+#include "field_generic_fwd.inc"
+#undef GEN_KERNEL
+#undef GEN_ARGS
+
 // ---------------------------------------------------------------------------------------------------------------------------
-template <class K>
-static int gen_launch(K k, const GenArgs& a, size_t lds, long long n_tiles, hipStream_t st) {
+// backward to the inputs: mode FULL or STATIC.  TRAIN: also every layer's pre-activation gradient to `dacts`
+#define GEN_KERNEL gen_bwd_kernel
+#define GEN_ARGS GenArgs
+#include "field_generic_bwd.inc"
+#undef GEN_KERNEL
+#undef GEN_ARGS
+#define GEN_KERNEL gen_bwd_train_kernel
+#define GEN_ARGS GenArgsTrain
+#include "field_generic_bwd.inc"
+#undef GEN_KERNEL
+#undef GEN_ARGS
+
+// ---------------------------------------------------------------------------------------------------------------------------
+template <class K, class Args>
+static int gen_launch(K k, const Args& a, size_t lds, long long n_tiles, hipStream_t st) {
     if (n_tiles > 0x7fffffffLL) return NEFES_E_UNSUPPORTED;
     hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
@@ -649,4 +502,62 @@ extern "C" int nefes_field_bwd_generic(const NefesGenericNetDesc* desc, const vo
     const long long n_tiles = (a.M + TS - 1) / TS;
     if (TS == 64) return gen_launch(gen_bwd_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
     return gen_launch(gen_bwd_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+}
+
+// ---- train mode ------------------------------------------------------------------------------------------------------------------
+static int gen_fill_train(GenTrain& t, const NefesGenericNetDesc* desc, float* buf) {
+    t.buf = buf;
+    const int rc = gen_train_map(desc, &t.map);
+    t.rows = t.map.off[NEFES_TB_END];
+    return rc;
+}
+
+// whole 128-sample train tiles: the tiles past the last sample write zeros (gen_train_zero)
+static long long gen_train_tiles(long long M, int TS) { return (M + 127) / 128 * (128 / TS); }
+
+extern "C" int nefes_field_fwd_train_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                             const float* rays_o, const float* rays_d, const float* z, const float* viewdirs,
+                                             float* raw_t, float* acts, uint32_t* masks, void* stream) {
+    if (!desc || !packed || !raw_t || !acts || !masks || !viewdirs || !rays_o || !rays_d || !z || N <= 0 || S <= 0) return NEFES_E_BADARG;
+    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
+    GenArgsTrain a;
+    memset(&a, 0, sizeof(a));
+    int rc = gen_fill(a, desc, packed, mode, N, S);
+    if (rc) return rc;
+    GenTrain& t = a.t;
+    rc = gen_fill_train(t, desc, acts);
+    if (rc) return rc;
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.viewdirs = viewdirs;
+    a.raw_t = raw_t; a.masks = masks;
+    const int TS = gen_tile(a.g.W);
+    const size_t lds = (size_t)(GEN_E_ROWS + GEN_DV_ROWS + 2 * a.g.W) * TS * 4;
+    const long long n_tiles = gen_train_tiles(a.M, TS);
+    if (TS == 64) return gen_launch(gen_fwd_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_launch(gen_fwd_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+}
+
+extern "C" int nefes_field_bwd_train_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                             const float* rays_o, const float* rays_d, const float* z, const float* viewdirs,
+                                             const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* dacts, float* g_pts,
+                                             float* g_viewdirs_s, void* stream) {
+    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !dacts || !g_pts || !g_viewdirs_s || !viewdirs || !rays_o || !rays_d || !z ||
+        N <= 0 || S <= 0)
+        return NEFES_E_BADARG;
+    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
+    GenArgsTrain a;
+    memset(&a, 0, sizeof(a));
+    int rc = gen_fill(a, desc, packed, mode, N, S);
+    if (rc) return rc;
+    GenTrain& t = a.t;
+    rc = gen_fill_train(t, desc, dacts);
+    if (rc) return rc;
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.viewdirs = viewdirs;
+    a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
+    a.g_pts = g_pts; a.g_vs = g_viewdirs_s;
+    const int TS = gen_tile(a.g.W);
+    const int RB = a.g.W > GEN_HEAD_ROWS ? a.g.W : GEN_HEAD_ROWS;
+    const size_t lds = (size_t)(GEN_E_ROWS + GEN_DV_ROWS + 2 * RB + 1) * TS * 4;
+    const long long n_tiles = gen_train_tiles(a.M, TS);
+    if (TS == 64) return gen_launch(gen_bwd_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_launch(gen_bwd_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
 }

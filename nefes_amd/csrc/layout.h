@@ -162,6 +162,8 @@ NEFES_HD int nefes_mask_words(int W) { return 8 * (W / 64) + 4 * (W / 128); }
 //   `acts`  (forward):  E, DV = embeddings in slot order (row 2s+h); L1..L8, FINAL, DIR, T0..T2 = PRE-activations
 //   `dacts` (backward): L1..T2 = gradient w.r.t. those pre-activations; RGB, SIG, TH = head pre-activation gradients
 // Hidden blocks are in natural feature order.  Head blocks are padded to whole 32-row tiles.
+// The train-mode instances of the GENERIC kernels (field_generic.hip) use the same layout and block enumeration with a row map of
+// their own (nefes_generic_train_row_offset), E / DV in the reference's feature order, and `acts` = layer OUTPUTS (after ReLU).
 enum { NEFES_TB_E = 0, NEFES_TB_DV = 1, NEFES_TB_L1 = 2 /* .. L8 = 9 */, NEFES_TB_FINAL = 10, NEFES_TB_DIR = 11,
        NEFES_TB_T0 = 12, NEFES_TB_T1 = 13, NEFES_TB_T2 = 14, NEFES_TB_RGB = 15, NEFES_TB_SIG = 16, NEFES_TB_TH = 17,
        NEFES_TB_END = 18 };

@@ -748,7 +748,7 @@ extern "C" int nefes_pack_weights(const NefesNetDesc* desc, const float* const* 
     memset(base, 0, info.total_bytes);
     uint32_t* hdr = (uint32_t*)base;
     hdr[0] = 0x5346454eu;  // 'NEFS'
-    hdr[1] = NEFES_ABI_VERSION;
+    hdr[1] = NEFES_BLOB_FORMAT;
     memcpy(hdr + 2, desc, sizeof(*desc));
     memcpy(hdr + 8, &info, sizeof(info));
     return pack_walk(desc, n, base, nullptr, info, st);

@@ -271,21 +271,35 @@ class NeRFH_NFF(nn.Module):
         return cols
 
     def packed_generic(self) -> ops.PackedGeneric:
-        """The network packed for the generic kernels; cached and invalidated like packed().  Frozen weights only."""
+        """The network packed for the generic kernels; cached and invalidated like packed(): packed on the host once, re-packed on the
+        device when only the versions of a trainable network's parameters changed."""
         if not self._generic_supported():
             raise RuntimeError(f"nefes_amd: no field kernel serves {self._shape()}.  Compiled: {ops.COMPILED_SET}")
         names = ops.PackedGeneric.layer_names(self.D, self.encode_transient)
         sd = dict(self.named_parameters())
         prm = [sd[n + s] for n in names for s in (".weight", ".bias")]
         key = tuple((p.data_ptr(), p._version, str(p.device)) for p in prm)
-        if self._pk_gen is None or key != self._pk_gen_key:
-            dev = prm[0].device if prm[0].is_cuda else torch.device("cuda")
+        pad = self._generic_embedding_columns()
+
+        def kernel_sd():
             ksd = {n: p.detach() for n, p in sd.items()}
-            for name, at, have, want in self._generic_embedding_columns():
+            for name, at, have, want in pad:
                 w = ksd[name]
                 ksd[name] = torch.cat([w[:, :at + have], w.new_zeros(w.shape[0], want - have), w[:, at + have:]], 1)
+            return ksd
+
+        old = self._pk_gen_key
+        if (self._pk_gen is not None and old is not None and key != old and len(old) == len(key)
+                and all(a[0] == b[0] and a[2] == b[2] for a, b in zip(old, key)) and any(p.requires_grad for p in prm)
+                and all(p.is_cuda and p.device == self._pk_gen.blob.device for p in prm)):
+            # a trainable network whose versions alone changed (an optimiser step): same blob, re-packed on the device -- no host copy,
+            # no sync.  A FROZEN network whose values changed takes the host packer below, as it always did (the old blob stays valid).
+            self._pk_gen.repack(kernel_sd())
+            self._pk_gen_key = key
+        elif self._pk_gen is None or key != old:
+            dev = prm[0].device if prm[0].is_cuda else torch.device("cuda")
             skip = 4 if (4 in self.skips and self.D > 4) else -1
-            self._pk_gen = ops.PackedGeneric(ksd, self.W, self.D, skip, self.W_features, self.encode_transient, dev)
+            self._pk_gen = ops.PackedGeneric(kernel_sd(), self.W, self.D, skip, self.W_features, self.encode_transient, dev)
             self._pk_gen_key = key
         return self._pk_gen
 
@@ -303,7 +317,15 @@ class NeRFH_NFF(nn.Module):
 
     def require_frozen_for_generic(self, what):
         raise NotImplementedError(f"nefes_amd: {what} is not built for the generic field kernels ({self._shape()}); they serve frozen "
-                                  f"weights with the frequency embedding only.  Tuned instances: {ops.COMPILED_SET}")
+                                  f"weights with the frequency embedding only.  Their train-mode instances are opt-in: set "
+                                  f"NEFES_GENERIC_TRAIN=1 (ops.GENERIC_TRAIN).  Tuned instances: {ops.COMPILED_SET}")
+
+    def shrink_grads_generic(self, g):
+        """shrink_grads for any depth: drops the columns packed_generic padded (_generic_embedding_columns)."""
+        for name, at, have, want in self._generic_embedding_columns():
+            if name in g:
+                g[name] = torch.cat([g[name][:, :at + have], g[name][:, at + want:]], 1)
+        return g
 
     def invalidate_packed(self):
         """Force a re-pack on the next render.  The cache key is (data_ptr, _version, device) per parameter, which sees

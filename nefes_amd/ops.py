@@ -752,6 +752,9 @@ class FieldFromPoints(torch.autograd.Function):
 # "1": networks the tuned instances DO serve run on the generic kernels too (off by default; so that the two can be compared on
 # the same weights).  Networks the tuned instances do not serve always take the generic kernels.
 FIELD_GENERIC = os.environ.get("NEFES_FIELD_GENERIC", "0") == "1"
+# "1": a trainable network on the generic kernels trains (train.field_train_generic: their train-mode instances + the weight-gradient
+# kernels of csrc/train.hip).  Off by default: such a network is refused, as before the train-mode instances existed.
+GENERIC_TRAIN = os.environ.get("NEFES_GENERIC_TRAIN", "0") == "1"
 GENERIC_SET = L.GENERIC_SET
 
 
@@ -764,7 +767,8 @@ def generic_shape_ok(width, depth, skips, feat_dim):
 
 class PackedGeneric:
     """Device-resident weights of one NeRFH_NFF network in the generic kernels' layout (nefes_generic_pack): per layer the matrix
-    transposed, the matrix, the bias -- plain padded fp32.  Frozen weights only: no device re-pack."""
+    transposed, the matrix, the bias -- plain padded fp32.  Packed on the host once; repack() refreshes the same blob on the device
+    (a trainable network after an optimiser step: no host copy, no sync)."""
 
     generic = True
     h3_valid = False             # (never on the fp16 two-part instances: fused_coarse_pass_ok and friends say no)
@@ -797,12 +801,31 @@ class PackedGeneric:
         self.generation = 0
         self.tile = 64 if self.width <= 256 else 32
 
+    def repack(self, state_dict):
+        """Same blob (same pointer, same shapes) from the current values of the parameters, on the device (nefes_generic_pack_device:
+        bit-identical to the host packer; the blob's padding was zeroed at allocation and is never written)."""
+        dev = self.blob.device
+        t = []
+        for name in self.layer_names(self.depth, self.has_transient):
+            t.append(state_dict[name + ".weight"].detach().to(dev, torch.float32).contiguous())
+            t.append(state_dict[name + ".bias"].detach().to(dev, torch.float32).contiguous())
+        ptrs = (C.c_void_p * len(t))(*[x.data_ptr() for x in t])
+        L.check(L.load().nefes_generic_pack_device(self.desc, ptrs, len(t), C.c_void_p(self.blob.data_ptr()), self.blob.numel(), _stream()),
+                "nefes_generic_pack_device")
+        self.generation += 1
+        del t            # (stream-ordered allocator: temporaries made above stay valid for the launches already queued)
+
     def check_generation(self, gen):
         if gen != self.generation:
             raise RuntimeError("nefes_amd: the network weights were re-packed between this forward pass and its backward pass")
 
     def mask_bytes(self, M):
         return L.load().nefes_generic_mask_bytes(self.desc, M)
+
+    def train_rows(self):
+        """(rows per tile, first row of block L.TB_*) of the train-mode acts / dacts buffers (nefes_generic_train_row_offset)."""
+        lib = L.load()
+        return int(lib.nefes_generic_train_rows(self.desc)), [int(lib.nefes_generic_train_row_offset(self.desc, b)) for b in range(L.TB_END + 1)]
 
     def n_raw(self, mode):
         return 1 if mode == L.FIELD_SIGMA else (3 + self.feat_dim + (1 if mode == L.FIELD_STATIC else 6))

@@ -141,9 +141,11 @@ def _render_core(rays_o, rays_d, viewdirs, near, far, network_fn, network_fine, 
         # inference instances, so it runs on the train-mode ones too (without the weight gradients); the full head does (_field)
         grid_static = mode == L.FIELD_STATIC and _grid_trainable(cfg.xyz_encoder)
         if (trainable(net) or grid_static) and mode != L.FIELD_SIGMA:
-            if ops.is_generic(pk):
-                net.require_frozen_for_generic("train mode (weight gradients)")
             from . import train as T
+            if ops.is_generic(pk):
+                if not ops.GENERIC_TRAIN or cfg.xyz_encoder is not None:
+                    net.require_frozen_for_generic("train mode (weight gradients)")
+                return T.field_train_generic(net, mode, rays_o, rays_d, viewdirs, z_)
             if cfg.xyz_encoder is not None:
                 return T.field_train_encoded(net, mode, cfg.xyz_encoder, rays_o, rays_d, viewdirs, z_)
             return T.field_train(net, mode, rays_o, rays_d, viewdirs, z_)

@@ -399,3 +399,154 @@ def field_train_encoded(net, mode, grid, rays_o, rays_d, viewdirs, z):
     pts = rays_o[:, None, :] + rays_d[:, None, :] * z[..., None]
     sd = dict(net.named_parameters())
     return FieldTrainEncoded.apply(grid(pts), viewdirs, net, mode, *[sd[n] for n in param_names(net, mode)])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Train mode on the generic kernels (csrc/field_generic.hip TRAIN instances): any --netwidth / --netdepth.  Opt-in: ops.GENERIC_TRAIN.
+# ---------------------------------------------------------------------------------------------------------------------------------
+class _GenericPass(_Pass):
+    """_Pass on the generic row map (nefes_generic_train_row_offset): same declarations, same launches."""
+
+    def __init__(self, pk, n_tiles, acts, dacts):
+        self.lib, self.desc, self.n_tiles = L.load(), pk.desc, n_tiles
+        self.acts, self.dacts = acts, dacts
+        self.rows, self.offsets = pk.train_rows()
+        self.stream = ops._stream()
+        self.dev = acts.device
+        self.db = {}
+        self.jobs, self.cols = [], 0
+
+
+def param_names_generic(net, mode):
+    """param_names for a network of any depth: the parameters on the path of `mode`, in nefes_generic_pack's order."""
+    names = ops.PackedGeneric.layer_names(net.D, mode == L.FIELD_FULL)
+    return [n + s for n in names for s in (".weight", ".bias")]
+
+
+def generic_train_bytes(pk, M):
+    """bytes of the acts + dacts buffers of M samples."""
+    return 2 * ((M + 127) // 128) * pk.train_rows()[0] * 128 * 4
+
+
+def _generic_buffers_fit(pk, N, S, dev):
+    need = generic_train_bytes(pk, N * S)
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    if need > free:
+        per_ray = generic_train_bytes(pk, 128 * S) / 128.
+        raise RuntimeError(f"nefes_amd: train mode of the generic kernels at W={pk.width}, D={pk.depth} keeps {need} bytes of activations and "
+                           f"gradients for {N} rays x {S} samples ({need // (N * S)} per sample); {free} are free.  About "
+                           f"{int(free / per_ray)} rays of {S} samples would fit: render fewer rays per step (chunk)")
+
+
+def weight_grads_generic(net, pk, mode, N, S, raw_t, g_raw_t, acts, o, d, v, zz, masks):
+    """weight_grads on the generic kernels: one fused backward launch (ray gradients + every layer's pre-activation gradient to
+    `dacts`), then dW = G X^T per layer on nefes_train_dw_bias.  `acts` holds layer OUTPUTS (after ReLU) and the embeddings in the
+    reference's order: x_relu = 0 everywhere, no slot permutation."""
+    lib = L.load()
+    W, D, Cf, skip = pk.width, pk.depth, pk.feat_dim, pk.skip
+    C3, H2 = 3 + Cf, W // 2
+    full = mode == L.FIELD_FULL
+    dev = acts.device
+    dacts = torch.empty_like(acts)
+    g_pts, g_vs = torch.empty(N * S, 3, device=dev), torch.empty(N * S, 3, device=dev)
+    L.check(lib.nefes_field_bwd_train_generic(pk.desc, pk.blob.data_ptr(), mode, N, S, o.data_ptr(), d.data_ptr(), zz.data_ptr(), v.data_ptr(),
+                                              raw_t.data_ptr(), g_raw_t.data_ptr(), masks.data_ptr(), dacts.data_ptr(), g_pts.data_ptr(),
+                                              g_vs.data_ptr(), ops._stream()), "nefes_field_bwd_train_generic")
+    P = _GenericPass(pk, acts.shape[0], acts, dacts)
+    TB = lambda l: L.TB_L1 + (l - 1)
+    h = {1: P.dw(TB(1), W, L.TB_E, 64, False)}
+    he = None
+    for l in range(2, D + 1):
+        h[l] = P.dw(TB(l), W, TB(l - 1), W, False)
+        if l - 1 == skip:                                              # the layer that reads cat([embedding, h]); its bias once
+            he = P.dw(TB(l), W, L.TB_E, 64, False, bias=False)
+    hsig, hfin = P.dw(L.TB_SIG, 1, TB(D), W, False), P.dw(L.TB_FINAL, W, TB(D), W, False)
+    hdir, hdird = P.dw(L.TB_DIR, H2, L.TB_FINAL, W, False), P.dw(L.TB_DIR, H2, L.TB_DV, 32, False, bias=False)
+    hrgb = P.dw(L.TB_RGB, C3, L.TB_DIR, H2, False)
+    if full:
+        ht0, ht0d = P.dw(L.TB_T0, H2, L.TB_FINAL, W, False), P.dw(L.TB_T0, H2, L.TB_DV, 32, False, bias=False)
+        ht1, ht2 = P.dw(L.TB_T1, H2, L.TB_T0, H2, False), P.dw(L.TB_T2, H2, L.TB_T1, H2, False)
+        hth = P.dw(L.TB_TH, 5, L.TB_T2, H2, False)
+    P.run()
+    g = {"xyz_encoding_1.0.weight": h[1].v[:W, :EMB_XYZ]}
+    for l in range(2, D + 1):
+        dh = h[l].v[:W, :W]
+        if l - 1 == skip:
+            dh = torch.cat([he.v[:W, :EMB_XYZ], dh], 1)
+        g[f"xyz_encoding_{l}.0.weight"] = dh
+    g["static_sigma.0.weight"] = hsig.v[:1, :W]
+    g["xyz_encoding_final.weight"] = hfin.v[:W, :W]
+    g["dir_encoding.0.weight"] = torch.cat([hdir.v[:H2, :W], hdird.v[:H2, :EMB_DIR]], 1)
+    g["static_rgb.0.weight"] = hrgb.v[:C3, :H2]
+    blk = lambda b, n: P.db[b][:n]
+    for l in range(1, D + 1):
+        g[f"xyz_encoding_{l}.0.bias"] = blk(TB(l), W)
+    g["xyz_encoding_final.bias"], g["dir_encoding.0.bias"] = blk(L.TB_FINAL, W), blk(L.TB_DIR, H2)
+    g["static_sigma.0.bias"], g["static_rgb.0.bias"] = blk(L.TB_SIG, 1), blk(L.TB_RGB, C3)
+    if full:
+        g["transient_encoding.0.weight"] = torch.cat([ht0.v[:H2, :W], ht0d.v[:H2, :EMB_DIR]], 1)
+        g["transient_encoding.2.weight"] = ht1.v[:H2, :H2]
+        g["transient_encoding.4.weight"] = ht2.v[:H2, :H2]
+        d_th, b_th = hth.v[:5, :H2], blk(L.TB_TH, 5)                   # nefes_generic_pack's rows: rgb (3) | sigma | beta
+        g["transient_rgb.0.weight"], g["transient_sigma.0.weight"], g["transient_beta.0.weight"] = d_th[:3], d_th[3:4], d_th[4:5]
+        g["transient_rgb.0.bias"], g["transient_sigma.0.bias"], g["transient_beta.0.bias"] = b_th[:3], b_th[3:4], b_th[4:5]
+        g["transient_encoding.0.bias"], g["transient_encoding.2.bias"] = blk(L.TB_T0, H2), blk(L.TB_T1, H2)
+        g["transient_encoding.4.bias"] = blk(L.TB_T2, H2)
+    if DEBUG is not None:
+        DEBUG.update(acts=rows_view(acts), dacts=rows_view(dacts), rows=P.rows, off={b: P.off(b) for b in range(L.TB_END + 1)})
+    g["__rays__"] = (g_pts, g_vs)
+    return g
+
+
+class FieldTrainGeneric(torch.autograd.Function):
+    """FieldTrain on the generic kernels: raw_t [N,R,S], differentiable w.r.t. the network parameters (*params in
+    `param_names_generic` order) and, when asked, the rays."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, viewdirs, z, net, mode, *params):
+        pk = net.packed_generic()
+        lib = L.load()
+        if mode not in (L.FIELD_STATIC, L.FIELD_FULL):
+            raise ValueError("nefes_amd: train mode evaluates the static or the full head")
+        if mode == L.FIELD_FULL and not pk.has_transient:
+            raise ValueError("nefes_amd: the full head of a network without a transient head")
+        o, d, v, zz = ops._f32(rays_o), ops._f32(rays_d), ops._f32(viewdirs), ops._f32(z)
+        N, S = zz.shape
+        _generic_buffers_fit(pk, N, S, zz.device)
+        rows, off = pk.train_rows()
+        raw_t = torch.empty(N, pk.n_raw(mode), S, device=zz.device)
+        acts = torch.empty((N * S + 127) // 128, rows, 128, device=zz.device)
+        masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=zz.device)
+        with ops._timed("field_fwd_train[generic]"):
+            L.check(lib.nefes_field_fwd_train_generic(pk.desc, pk.blob.data_ptr(), mode, N, S, ops._chk(o, "rays_o"), ops._chk(d, "rays_d"),
+                                                      ops._chk(zz, "z"), ops._chk(v, "viewdirs"), raw_t.data_ptr(), acts.data_ptr(),
+                                                      masks.data_ptr(), ops._stream()), "nefes_field_fwd_train_generic")
+        ops._tap("masks_generic", (masks, N, S, pk, mode))
+        ctx.save_for_backward(raw_t, acts, o, d, v, zz, masks)
+        if DEBUG is not None:
+            DEBUG.update(acts=rows_view(acts), rows=rows, off=dict(enumerate(off)))
+        ctx.net, ctx.pk, ctx.mode, ctx.NS, ctx.pk_gen = net, pk, mode, (N, S), pk.generation
+        return raw_t
+
+    @staticmethod
+    def backward(ctx, g_raw_t):
+        if ctx.needs_input_grad[3]:
+            raise NotImplementedError("nefes_amd: the depths z carry no gradient in train mode (rendering.py:139 detaches them)")
+        ctx.pk.check_generation(ctx.pk_gen)
+        raw_t, acts, o, d, v, zz, masks = ctx.saved_tensors
+        N, S = ctx.NS
+        with ops._timed("field_bwd_train[generic]"):
+            g = weight_grads_generic(ctx.net, ctx.pk, ctx.mode, N, S, raw_t, ops._f32(g_raw_t), acts, o, d, v, zz, masks)
+        g_pts, g_vs = g.pop("__rays__")
+        g = ctx.net.shrink_grads_generic(g)    # a network on fewer embedding octaves: drop the columns packed_generic padded
+        g_rays = (None, None, None)
+        if any(ctx.needs_input_grad[:3]):
+            g_rays = ops.ray_grad_reduce(N, S, zz, g_pts, g_vs)
+        return g_rays + (None,) * 3 + tuple(g[n].contiguous() for n in param_names_generic(ctx.net, ctx.mode))
+
+
+def field_train_generic(net, mode, rays_o, rays_d, viewdirs, z):
+    if not ops.GENERIC_TRAIN:
+        net.require_frozen_for_generic("train mode (weight gradients)")
+    sd = dict(net.named_parameters())
+    return FieldTrainGeneric.apply(rays_o, rays_d, viewdirs, z, net, mode, *[sd[n] for n in param_names_generic(net, mode)])
