@@ -12,6 +12,7 @@ import torch
 from oracle import ref_cpu as O
 from tests import branch as B
 from tests import parity_log as P
+from tests.sampler_ref import cdf_from_weights
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -217,6 +218,8 @@ def test_sample_pdf_indices_bit_exact(golden, ops, tag, det, Ni):
     # ulp; report the index mismatch rate and require every mismatch to be an ulp-level tie, samples continuous.
     zf2, zs2, inds2, cdf2 = ops.sample_pdf_merge(z, w, Ni, u=u, want_debug=True)
     np.testing.assert_allclose(cdf2.cpu().numpy(), g[f"{tag}.cdf"], rtol=0, atol=2.4e-7)
+    # ... while the kernel's documented arithmetic (exact float64 sums) is: bit for bit against its numpy restatement
+    assert np.array_equal(cdf2.cpu().numpy(), cdf_from_weights(T(g["w"])).numpy())
     bad = inds2.cpu().numpy().astype(np.int64) != g[f"{tag}.inds"]
     print(f"[{tag}] index mismatch rate with in-kernel CDF: {bad.mean():.4%}")
     if bad.any():
