@@ -218,12 +218,14 @@ class NeRFH_NFF(nn.Module):
                 and self.W in (128, 256) and self.out_ch_size != 3 and 0 < self.W_features <= ops.HEAD_MAX_C
                 and (freq_xyz or self.W == 256))
 
-    # layers whose input holds an embedding: (name, column where the embedding starts, its width here, its width in the kernels)
+    # layers whose input holds an embedding shorter than the kernels' 63 / 27 features: (name, column where the embedding starts, its
+    # width here, its width in the kernels).  Any depth: the first layer and the skip layers read the xyz embedding (layers 1 and 5 of
+    # the tuned networks); 32 inputs are an external encoding, which is never padded.
     def _embedding_columns(self):
         ex, ed, W = self.in_channels_xyz, self.in_channels_dir, self.W
         cols = []
         if ex != 32 and ex < 63:
-            cols += [("xyz_encoding_1.0.weight", 0, ex, 63), ("xyz_encoding_5.0.weight", 0, ex, 63)]
+            cols += [(f"xyz_encoding_{i + 1}.0.weight", 0, ex, 63) for i in range(self.D) if i == 0 or i in self.skips]
         if ed < 27:
             cols += [("dir_encoding.0.weight", W, ed, 27)]
             if self.encode_transient:
@@ -248,6 +250,12 @@ class NeRFH_NFF(nn.Module):
                 g[name] = torch.cat([g[name][:, :at + have], g[name][:, at + want:]], 1)
         return g
 
+    def _path_params(self, names):
+        """-> (the named parameters, those of the layers `names` as [weight, bias, ...], the cache key of a pack made from them)."""
+        sd = dict(self.named_parameters())
+        prm = [sd[n + s] for n in names for s in (".weight", ".bias")]
+        return sd, prm, tuple((p.data_ptr(), p._version, str(p.device)) for p in prm)
+
     def _generic_supported(self):
         """The generic kernels (csrc/field_generic.hip) serve this network: any width that is a multiple of 32 up to 512, depth 1..8 with
         the reference's skips=[4] (a no-op when D <= 4), the frequency embeddings or a prefix of them, a feature head."""
@@ -258,36 +266,13 @@ class NeRFH_NFF(nn.Module):
         return (f"D={self.D}, skips={self.skips}, W={self.W}, f_dim={self.W_features}, in_channels_xyz={self.in_channels_xyz}, "
                 f"in_channels_dir={self.in_channels_dir}")
 
-    def _generic_embedding_columns(self):
-        """_embedding_columns for any depth: the layers that read an embedding shorter than the kernels' 63 / 27 features."""
-        ex, ed, W = self.in_channels_xyz, self.in_channels_dir, self.W
-        cols = []
-        if ex < 63:
-            cols += [(f"xyz_encoding_{i + 1}.0.weight", 0, ex, 63) for i in range(self.D) if i == 0 or i in self.skips]
-        if ed < 27:
-            cols += [("dir_encoding.0.weight", W, ed, 27)]
-            if self.encode_transient:
-                cols += [("transient_encoding.0.weight", W, ed, 27)]
-        return cols
-
     def packed_generic(self) -> ops.PackedGeneric:
         """The network packed for the generic kernels; cached and invalidated like packed(): packed on the host once, re-packed on the
         device when only the versions of a trainable network's parameters changed."""
         if not self._generic_supported():
             raise RuntimeError(f"nefes_amd: no field kernel serves {self._shape()}.  Compiled: {ops.COMPILED_SET}")
-        names = ops.PackedGeneric.layer_names(self.D, self.encode_transient)
-        sd = dict(self.named_parameters())
-        prm = [sd[n + s] for n in names for s in (".weight", ".bias")]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in prm)
-        pad = self._generic_embedding_columns()
-
-        def kernel_sd():
-            ksd = {n: p.detach() for n, p in sd.items()}
-            for name, at, have, want in pad:
-                w = ksd[name]
-                ksd[name] = torch.cat([w[:, :at + have], w.new_zeros(w.shape[0], want - have), w[:, at + have:]], 1)
-            return ksd
-
+        sd, prm, key = self._path_params(ops.PackedGeneric.layer_names(self.D, self.encode_transient))
+        kernel_sd = lambda: self._kernel_params({n: p.detach() for n, p in sd.items()})
         old = self._pk_gen_key
         if (self._pk_gen is not None and old is not None and key != old and len(old) == len(key)
                 and all(a[0] == b[0] and a[2] == b[2] for a, b in zip(old, key)) and any(p.requires_grad for p in prm)
@@ -306,9 +291,7 @@ class NeRFH_NFF(nn.Module):
     def uses_generic(self):
         """The routing decision: True when renders of this network take the generic kernels -- the tuned instances do not serve it, or
         NEFES_FIELD_GENERIC=1 asks for the comparison."""
-        if self._supported() and not (ops.FIELD_GENERIC and self._generic_supported()):
-            return False
-        return True
+        return not self._supported() or (ops.FIELD_GENERIC and self._generic_supported())
 
     def packed_any(self):
         """What the callers (render, refine, run_network_NeRFH_NFF) hand the kernels: the tuned pack where an instance serves this
@@ -319,13 +302,6 @@ class NeRFH_NFF(nn.Module):
         raise NotImplementedError(f"nefes_amd: {what} is not built for the generic field kernels ({self._shape()}); they serve frozen "
                                   f"weights with the frequency embedding only.  Their train-mode instances are opt-in: set "
                                   f"NEFES_GENERIC_TRAIN=1 (ops.GENERIC_TRAIN).  Tuned instances: {ops.COMPILED_SET}")
-
-    def shrink_grads_generic(self, g):
-        """shrink_grads for any depth: drops the columns packed_generic padded (_generic_embedding_columns)."""
-        for name, at, have, want in self._generic_embedding_columns():
-            if name in g:
-                g[name] = torch.cat([g[name][:, :at + have], g[name][:, at + want:]], 1)
-        return g
 
     def invalidate_packed(self):
         """Force a re-pack on the next render.  The cache key is (data_ptr, _version, device) per parameter, which sees
@@ -345,9 +321,7 @@ class NeRFH_NFF(nn.Module):
                                f"W={self.W}, f_dim={self.W_features}, in_channels_xyz={self.in_channels_xyz}, "
                                f"in_channels_dir={self.in_channels_dir}.  Compiled: {ops.COMPILED_SET}")
         names = ops.PackedField.LAYERS_FINE if self.encode_transient else ops.PackedField.LAYERS_COARSE
-        sd = dict(self.named_parameters())
-        prm = [sd[n + s] for n in names for s in (".weight", ".bias")]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in prm)
+        sd, prm, key = self._path_params(names)
         pad = bool(self._embedding_columns())
         if os.environ.get("NEFES_DEBUG_PACK_CHECKSUM", "0") == "1":      # debug: also key on the values (one sync per call)
             key += (float(sum(p.detach().double().sum() for p in prm)),)
@@ -378,18 +352,14 @@ class NeRFH_NFF(nn.Module):
     def fold_ok(self):
         """The folded kernels apply to this network's full pass (csrc/field_fwd_h3.hip FOLD): a FROZEN fine network of a shape with folded
         instances, on the fp16 two-part pipe.  Evaluated per render: a network made trainable afterwards takes the unfolded kernels."""
-        return (ops.FOLD_FINAL and ops.SPLIT == "h3" and ops.USE_X6 and not ops.FIELD_GENERIC and self.encode_transient and self._supported()
-                and ops.fold_shape(self.W, self.W_features, L.XYZ_EXTERNAL32 if self.in_channels_xyz == 32 else L.XYZ_FREQ10)
-                and self._field_frozen())
+        return (ops.fold_serves(self.W, self.W_features, L.XYZ_EXTERNAL32 if self.in_channels_xyz == 32 else L.XYZ_FREQ10)
+                and self.encode_transient and self._supported() and self._field_frozen())
 
     def packed_folded(self) -> ops.PackedField:
         """packed() with xyz_encoding_final multiplied into dir_encoding / transient_encoding.0 by the packer (NefesNetDesc.fold_final):
         what the fine pass of a frozen network runs on.  Cached and invalidated like packed(); always packed on the host (the fold is a
         product of parameters in double)."""
-        names = ops.PackedField.LAYERS_FINE
-        sd = dict(self.named_parameters())
-        prm = [sd[n + s] for n in names for s in (".weight", ".bias")]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in prm)
+        sd, prm, key = self._path_params(ops.PackedField.LAYERS_FINE)
         if self._pk_fold is None or key != self._pk_fold_key:
             dev = prm[0].device if prm[0].is_cuda else torch.device("cuda")
             self._pk_fold = ops.PackedField(self._kernel_params({n: p.detach() for n, p in sd.items()}), self.W, self.W_features,
@@ -400,16 +370,13 @@ class NeRFH_NFF(nn.Module):
     def factored_head_ok(self):
         """The factored-head kernels apply (csrc/field_fwd_h3.hip FH): a FROZEN fine network of width 128 on the frequency embedding whose
         rgb+feature head has more channels than g = relu(dir_encoding) has features (+ the ones channel), on the fp16 two-part pipe."""
-        return (ops.FACTORED_HEAD and not ops.FIELD_GENERIC and self.encode_transient and self.W == 128 and self.in_channels_xyz != 32 and self._supported()
-                and 3 + self.W_features > 3 + self.W // 2 + 1 and ops.SPLIT == "h3" and self._field_frozen())
+        return (ops.factored_head_serves(self.W, self.W_features) and self.encode_transient and self.in_channels_xyz != 32
+                and self._supported() and self._field_frozen())
 
     def packed_fh(self):
         """(PackedField of the network WITHOUT its feature rows -- static_rgb = its three colour rows, f_dim 0 --, W_f [C, W/2], W_f^T, b_f [C]):
         what the factored-head kernels and the per-ray feature head of nefes_amd/render.py take.  Cached like packed()."""
-        names = ops.PackedField.LAYERS_FINE
-        sd = dict(self.named_parameters())
-        prm = [sd[n + s] for n in names for s in (".weight", ".bias")]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in prm)
+        sd, prm, key = self._path_params(ops.PackedField.LAYERS_FINE)
         if getattr(self, "_pk_fh", None) is None or key != self._pk_fh_key:
             dev = prm[0].device if prm[0].is_cuda else torch.device("cuda")
             ksd = dict(self._kernel_params({n: p.detach() for n, p in sd.items()}))

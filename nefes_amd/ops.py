@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the stream; every computatio
 path is a HIP kernel in libnefes_hip.so.  All tensors are fp32 CUDA(=HIP) tensors; wrappers
 check dtype/contiguity/device and raise rather than silently converting on a different path.
 """
+import collections
 import ctypes as C
 from typing import Optional
 
@@ -204,29 +205,15 @@ def fused_coarse_pass_ok(pk, Nc, Ni, N=0, grid=None):
     instances, frequency embedding (or a hash grid the field kernel gathers itself: hashgrid_fused_ok), Nc = 64 / 128 / 256,
     Nc + Ni <= 512 (csrc/sample_pdf.hip coarse_sample_kernel)."""
     enc_ok = pk.xyz_encoding == L.XYZ_FREQ10 if grid is None else hashgrid_fused_ok(pk, grid)
-    return (FUSED_COARSE and _h3(pk) and h3_shape(pk) and enc_ok and Nc in (64, 128, 256)
-            and Ni > 0 and Nc + Ni <= 512 and N * Nc < (1 << 31) - 256)      # (beyond the 32-bit sample index: the four-launch path)
+    return (FUSED_COARSE and h3_serves(pk) and enc_ok and Nc in (64, 128, 256)
+            and Ni > 0 and Nc + Ni <= 512 and N * Nc < H3_MAX_SAMPLES)      # (beyond the 32-bit sample index: the four-launch path)
 
 
 def field_sigma_row(pk, rays_o, rays_d, z_row, grid=None):
     """sigma [N,1,Nc] of the coarse network along rays whose depths are ONE shared row (no gradient: nerfh_nff.py:192-202).
     grid: an ops.HashGrid whose encoding the kernel evaluates itself (hashgrid_fused_ok)."""
     rays_o, rays_d = _f32(rays_o), _f32(rays_d)
-    N, S = rays_o.shape[0], z_row.numel()
-    if N * S >= (1 << 31) - 256:
-        raise RuntimeError("nefes_amd: too many samples for one launch of the fp16 two-part kernels (32-bit sample index)")
-    raw_t = torch.empty(N, 1, S, device=rays_o.device)
-    if grid is not None:
-        with _timed("field_fwd[sigma,h3,hashgrid]"):
-            L.check(L.load().nefes_field_fwd_h3_hashgrid(pk.desc, _chk(pk.blob, "blob", torch.uint8), grid.desc, _chk(grid.table, "table"), L.FIELD_SIGMA,
-                                                         N, S, _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(z_row, "z_row"), 1, None,
-                                                         _chk(raw_t, "raw_t"), None, _stream()), "nefes_field_fwd_h3_hashgrid")
-        return raw_t
-    with _timed("field_fwd[sigma,h3]"):
-        L.check(L.load().nefes_field_fwd_h3_zrow(pk.desc, _chk(pk.blob, "blob", torch.uint8), L.FIELD_SIGMA, N, S, _chk(rays_o, "rays_o"),
-                                                 _chk(rays_d, "rays_d"), _chk(z_row, "z_row"), None, _chk(raw_t, "raw_t"), None, _stream()),
-                "nefes_field_fwd_h3_zrow")
-    return raw_t
+    return _field_fwd(pk, L.FIELD_SIGMA, rays_o.shape[0], z_row.numel(), rays_o=rays_o, rays_d=rays_d, z=z_row, grid=grid)[0]
 
 
 def coarse_sample(sigma, z, Ni, u=None, want_samples=True, want_weights=False):
@@ -344,25 +331,6 @@ class PackedField:
         return 1 if mode == L.FIELD_SIGMA else (3 + self.feat_dim + (1 if mode == L.FIELD_STATIC else 6))
 
 
-def field_fwd(pk: PackedField, mode, N, S, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, want_masks=False,
-              xyz_enc=None):
-    dev = pk.blob.device
-    if not canonical_shape(pk):
-        raise RuntimeError(f"nefes_amd: the {('sigma', 'static', 'full')[mode]} forward of W={pk.width}, f_dim={pk.feat_dim} was routed to "
-                           f"the fp32-MFMA instances (NEFES_SPLIT={SPLIT}; or a frozen network's static head with test_time=False), "
-                           f"which exist for the canonical shapes only.  Compiled: {COMPILED_SET}")
-    raw_t = torch.empty(N, pk.n_raw(mode), S, device=dev)
-    masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=dev) if want_masks else None
-    with _timed(f"field_fwd[{('sigma', 'static', 'full')[mode]}]"):
-      L.check(L.load().nefes_field_fwd(pk.desc, _chk(pk.blob, "blob", torch.uint8), mode, N, S, _chk(rays_o, "rays_o"),
-                                     _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(xyz_enc, "xyz_enc"),
-                                     _chk(viewdirs, "viewdirs"), _chk(raw_t, "raw_t"), _chk(masks, "masks", torch.int32),
-                                     _stream()), "nefes_field_fwd")
-    if masks is not None:
-        _tap("masks", (masks, N, S, pk.width, mode))
-    return raw_t, masks
-
-
 # Which matrix-core arithmetic the field kernels use where an instance exists (width 256 / C = 16, width 128 / C = 128):
 #   "h3"  (default) fp16 two-part split products, three cross terms on v_mfma_f32_32x32x16_f16 (csrc/field_h3.h): fp32-level
 #         accuracy at half the matrix-core work of bf16x6; tests/test_gpu_h3.py against the float64 oracle
@@ -376,10 +344,25 @@ USE_X6 = os.environ.get("NEFES_X6", "1") != "0"
 # the coarse pass at test time as two launches instead of four (coarse_depth_row / field_sigma_row / coarse_sample); "0": the separate
 # coarse_depths, sigma field, composite D and sample_pdf_merge launches (the tests compare the two bit for bit)
 FUSED_COARSE = os.environ.get("NEFES_FUSED_COARSE", "1") != "0"
+# Frozen networks on the fp16 pipe: xyz_encoding_final (a Linear with no activation behind it) is multiplied into dir_encoding /
+# transient_encoding.0 by the packer and its W x W product leaves the fine pass's forward and backward kernels (csrc/field_fwd_h3.hip
+# FOLD; NeRFH_NFF.packed_folded).  "0": the unfolded kernels for every network.
+FOLD_FINAL = os.environ.get("NEFES_FOLD_FINAL", "1") != "0"
+# The factored feature head (csrc/field_fwd_h3.hip FH, nefes_amd/render.py): a frozen width-128 fine network emits g = relu(dir_encoding)
+# instead of its 128 feature channels and the head's matrix is applied once per ray to the composited g; "0": the plain kernels.
+FACTORED_HEAD = os.environ.get("NEFES_FACTORED_HEAD", "1") != "0"
+# "1": networks the tuned instances DO serve run on the generic kernels (csrc/field_generic.hip) too (off by default; so that the two
+# can be compared on the same weights).  Networks the tuned instances do not serve always take the generic kernels.
+FIELD_GENERIC = os.environ.get("NEFES_FIELD_GENERIC", "0") == "1"
+# BASELINE configs[3] with the hash grid evaluated INSIDE the field kernels (csrc/hashgrid.h, nefes_field_fwd_h3_hashgrid /
+# nefes_field_bwd_h3_hashgrid); "0": the separate launches HashGridEncode + FieldFromEncoding (the tests compare the two)
+FUSED_HASHGRID = os.environ.get("NEFES_FUSED_HASHGRID", "1") != "0"
 
 
 HEAD_MAX_C = 141          # csrc/layout.h NEFES_HEAD_MAX_C: the larger head class serves 3 + C <= 144
 COMPILED_SET = L.COMPILED_SET
+H3_MAX_SAMPLES = (1 << 31) - 256      # the fp16 two-part kernels index the samples of one launch with 32 bits
+MODE_NAMES = ("sigma", "static", "full")
 
 
 def head_class(C):
@@ -387,13 +370,14 @@ def head_class(C):
     return -1 if C < 0 else (0 if 3 + C <= 32 else (1 if 3 + C <= 144 else -1))
 
 
-def canonical_shape(pk: PackedField):
+# -- the primitives every routing decision below is built from: canonical_shape, h3_shape, _h3 ---------------------------------
+def canonical_shape(pk):
     """Shapes that ALSO have bf16x6 and fp32-MFMA instances: width 256 / C = 16 (either xyz encoding) and the reference-default
     width 128 / C = 128 (frequency embedding)."""
     return (pk.width == 256 and pk.feat_dim == 16) or (pk.width == 128 and pk.feat_dim == 128 and pk.xyz_encoding == L.XYZ_FREQ10)
 
 
-def h3_shape(pk: PackedField):
+def h3_shape(pk):
     """Shapes with fp16 two-part instances (csrc/field_fwd_h3.hip nefes_field_fwd_h3): both widths x both head classes with the
     frequency embedding; width 256 x both head classes with an external embedding."""
     cls = head_class(pk.feat_dim)
@@ -402,10 +386,44 @@ def h3_shape(pk: PackedField):
     return True if pk.xyz_encoding == L.XYZ_FREQ10 else pk.width == 256
 
 
-# Frozen networks on the fp16 pipe: xyz_encoding_final (a Linear with no activation behind it) is multiplied into dir_encoding /
-# transient_encoding.0 by the packer and its W x W product leaves the fine pass's forward and backward kernels (csrc/field_fwd_h3.hip
-# FOLD; NeRFH_NFF.packed_folded).  "0": the unfolded kernels for every network.
-FOLD_FINAL = os.environ.get("NEFES_FOLD_FINAL", "1") != "0"
+def _h3(pk):
+    """The fp16 two-part pipe is selected and this network's fp16 streams are current."""
+    if SPLIT not in ("h3", "x6", "f32"):
+        raise ValueError("nefes_amd.ops.SPLIT must be 'h3', 'x6' or 'f32'")
+    return SPLIT == "h3" and pk.h3_valid
+
+
+def h3_serves(pk):
+    """fp16 two-part instances serve this pack: pipe selected, streams current, shape compiled."""
+    return _h3(pk) and h3_shape(pk)
+
+
+def static_h3(pk):
+    """The static-head instances of the fp16 two-part kernels apply (csrc/field_fwd_h3.hip H3_STATIC, nefes_field_bwd_static_h3;
+    the train-mode instances too: train.fp16_pipe): every compiled (width, head class) pair with the frequency embedding."""
+    return h3_serves(pk) and pk.xyz_encoding == L.XYZ_FREQ10
+
+
+def _has_instance(pk):
+    return canonical_shape(pk) or h3_serves(pk)
+
+
+def x6_supported(pk, mode):
+    """A split-product instance (fp16 two-part or bf16x6) serves this network and mode: sigma-only or full, forward and backward --
+    and, on the fp16 two-part instances with the frequency embedding, the static head alone (round 5: a frozen coarse network with
+    test_time False, a fine network with NeRFW off)."""
+    if mode == L.FIELD_STATIC:
+        return static_h3(pk)
+    return _has_instance(pk) and (mode == L.FIELD_SIGMA or (mode == L.FIELD_FULL and pk.has_transient))
+
+
+def require_instance(pk, what):
+    """Fail loudly, naming the compiled set, before a launch that no kernel instance serves."""
+    if _has_instance(pk):
+        return
+    raise RuntimeError(f"nefes_amd: no kernel instance serves {what} for W={pk.width}, f_dim={pk.feat_dim}, "
+                       f"xyz_encoding={pk.xyz_encoding} with NEFES_SPLIT={SPLIT}"
+                       f"{'' if pk.h3_valid else ' (fp16 streams stale: NEFES_REPACK_H3=0)'}.  Compiled: {COMPILED_SET}")
 
 
 def fold_shape(width, feat_dim, xyz_encoding=L.XYZ_FREQ10):
@@ -413,113 +431,206 @@ def fold_shape(width, feat_dim, xyz_encoding=L.XYZ_FREQ10):
     return width == 256 and head_class(feat_dim) >= 0 and xyz_encoding == L.XYZ_FREQ10
 
 
-def x6_supported(pk: PackedField, mode, forward=True):
-    """A split-product instance (fp16 two-part or bf16x6) serves this network and mode: sigma-only or full, forward and backward --
-    and, on the fp16 two-part instances with the frequency embedding, the static head alone (round 5: a frozen coarse network with
-    test_time False, a fine network with NeRFW off)."""
-    if mode == L.FIELD_STATIC:
-        return static_h3(pk)
-    ok = canonical_shape(pk) or (_h3(pk) and h3_shape(pk))
-    return ok and (mode == L.FIELD_SIGMA or (mode == L.FIELD_FULL and pk.has_transient))
+def fold_serves(width, feat_dim, xyz_encoding):
+    """A frozen fine network of this shape renders on a folded pack (NeRFH_NFF.fold_ok adds the network's own conditions)."""
+    return FOLD_FINAL and SPLIT == "h3" and USE_X6 and not FIELD_GENERIC and fold_shape(width, feat_dim, xyz_encoding)
 
 
-def static_h3(pk: PackedField):
-    """The static-head inference instances of the fp16 two-part kernels apply (csrc/field_fwd_h3.hip H3_STATIC,
-    nefes_field_bwd_static_h3): every compiled (width, head class) pair with the frequency embedding."""
-    return _h3(pk) and h3_shape(pk) and pk.xyz_encoding == L.XYZ_FREQ10
+def factored_head_serves(width, feat_dim):
+    """A frozen fine network of this shape on the frequency embedding renders with the factored head (NeRFH_NFF.factored_head_ok):
+    width 128 and a head with more channels than g = relu(dir_encoding) has features (+ the ones channel).  (NEFES_X6 is not asked.)"""
+    return FACTORED_HEAD and SPLIT == "h3" and not FIELD_GENERIC and width == 128 and 3 + feat_dim > 3 + width // 2 + 1
 
 
-def _h3(pk):
-    """fp16 two-part instances apply: selected, this network's fp16 streams are current, and M fits the kernels' 32-bit index."""
-    if SPLIT not in ("h3", "x6", "f32"):
-        raise ValueError("nefes_amd.ops.SPLIT must be 'h3', 'x6' or 'f32'")
-    return SPLIT == "h3" and pk.h3_valid
+def is_generic(pk):
+    return bool(getattr(pk, "generic", False))
 
 
-def require_instance(pk: PackedField, what):
-    """Fail loudly, naming the compiled set, before a launch that no kernel instance serves."""
-    if canonical_shape(pk) or (_h3(pk) and h3_shape(pk)):
-        return
-    raise RuntimeError(f"nefes_amd: no kernel instance serves {what} for W={pk.width}, f_dim={pk.feat_dim}, "
-                       f"xyz_encoding={pk.xyz_encoding} with NEFES_SPLIT={SPLIT}"
-                       f"{'' if pk.h3_valid else ' (fp16 streams stale: NEFES_REPACK_H3=0)'}.  Compiled: {COMPILED_SET}")
+def hashgrid_fused_ok(pk, grid):
+    """The fp16 two-part field kernels can gather this hash grid themselves: width 256, head class 0, sixteen levels x two features.
+    (Head class 1 -- the 128-channel feature head -- has instances on a SUPPLIED encoding only, csrc/field_bwd_h3.hip part 13: its
+    renders take HashGridEncode + FieldFromEncoding, and with them the four-launch coarse pass.)"""
+    return (FUSED_HASHGRID and isinstance(grid, HashGrid) and h3_serves(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32
+            and head_class(pk.feat_dim) == 0 and grid.desc.n_levels == 16 and grid.desc.n_features == 2)
 
 
-def field_fwd_x6(pk: PackedField, mode, N, S, rays_o=None, rays_d=None, z=None, viewdirs=None, want_masks=False, xyz_enc=None,
-                 pts=None):
-    """field_fwd on the split-product instances (same outputs, same mask words): fp16 two-part (default) or bf16x6."""
-    dev = pk.blob.device
-    raw_t = torch.empty(N, pk.n_raw(mode), S, device=dev)
-    masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=dev) if want_masks else None
-    h3 = _h3(pk) and h3_shape(pk) and N * S < (1 << 31) - 256
-    if mode == L.FIELD_STATIC and not h3:
-        return field_fwd(pk, mode, N, S, rays_o=rays_o, rays_d=rays_d, z=z, pts=pts, viewdirs=viewdirs, want_masks=want_masks, xyz_enc=xyz_enc)
-    if not h3 and not canonical_shape(pk):
-        raise RuntimeError(f"nefes_amd: {N * S} samples in one launch exceed the fp16 two-part kernels' 32-bit sample index and "
-                           f"W={pk.width}, f_dim={pk.feat_dim} has no other instance; render fewer rays per launch")
+Route = collections.namedtuple("Route", "entry key label g_enc")
+
+
+def field_route(pk, mode, backward=False, kind="rays", M=0, override=None):
+    """Which kernel serves one field pass -> Route(entry: the C entry point's name, key: the timer key, label: what L.check prints,
+    g_enc: the backward hands back d loss / d encoding [M, 32] in the place of d loss / d pts).  Pure: no tensors, no library, no
+    device work; SPLIT, USE_X6 and the packs' h3_valid are read at call time.
+
+    pk: a pack's attributes (width, feat_dim, xyz_encoding, has_transient, h3_valid, fold, generic); mode: L.FIELD_*; kind: "rays",
+    "points", "enc" (a supplied 32-feature encoding), "hashgrid" (gathered in the kernel) or "zrow" (rays that share one row of
+    depths: field_sigma_row); M = N * S samples; override (forward only): None -- the switches decide, what the autograd Functions
+    do; "split" -- a split-product instance whatever NEFES_X6 / NEFES_SPLIT=f32 say (field_fwd_x6); "f32" -- the strict fp32-MFMA
+    entry point (field_fwd).  DESIGN.md 4.1.1 is this function as a table.  The decisions, each as it has been since its family
+    of instances arrived:
+
+    * hashgrid / zrow: fp16 two-part instances only, M below H3_MAX_SAMPLES; no static head.  Whether they serve the pack at all is
+      the caller's question (hashgrid_fused_ok, fused_coarse_pass_ok) and is not asked again here.
+    * a generic pack (NeRFH_NFF.packed_generic): nefes_field_fwd_generic / nefes_field_bwd_generic, every mode, any M.
+    * forward, switches decide: the split route when USE_X6, SPLIT != "f32" and x6_supported(pk, mode) -- and, for POINTS input,
+      only with the frequency embedding.  Otherwise the strict route.
+    * forward, split route: fp16 two-part when h3_serves(pk) and M < H3_MAX_SAMPLES.  Otherwise the STATIC head falls to the strict
+      route; sigma / full drop to bf16x6 on canonical shapes and are refused elsewhere (which is what happens to a non-canonical
+      shape at M >= H3_MAX_SAMPLES).  A folded pack serves FULL on fp16 only.
+    * forward, strict route: nefes_field_fwd, canonical shapes only.
+    * backward, STATIC: fp16 when USE_X6, SPLIT != "f32", static_h3(pk) and M < H3_MAX_SAMPLES; else nefes_field_bwd_static,
+      canonical shapes only.
+    * backward, any other mode is the FULL head: a split instance when USE_X6, SPLIT != "f32" and x6_supported(pk, FULL) -- fp16 when
+      _h3(pk), else bf16x6, which refuses a folded pack.  Otherwise nefes_field_bwd, WITHOUT a shape check (the C side refuses).  So
+      a folded pack under SPLIT = "f32" lands on the strict entry point: that stream of a folded blob is the unfolded one and raw_t /
+      masks are the same (tests/test_gpu_fold.py relies on it).
+    * the FULL backward does not look at M at all: at M >= H3_MAX_SAMPLES it still names the fp16 instance.  Known, kept as it is
+      (it cannot be reached at test sizes; changing it is a change of behaviour).
+    """
+    name = MODE_NAMES[mode]
+    d = "bwd" if backward else "fwd"
+    switched = USE_X6 and SPLIT != "f32"
+    route = lambda entry, key, g_enc=False: Route(entry, key, entry, g_enc)
+    if kind in ("hashgrid", "zrow"):
+        if M >= H3_MAX_SAMPLES:
+            raise RuntimeError("nefes_amd: too many samples for one launch of the fp16 two-part kernels (32-bit sample index)")
+        if kind == "zrow":
+            return route("nefes_field_fwd_h3_zrow", "field_fwd[sigma,h3]")
+        if backward:
+            return route("nefes_field_bwd_h3_hashgrid", "field_bwd[h3,hashgrid]")
+        if mode == L.FIELD_STATIC:
+            raise NotImplementedError("nefes_amd: the hash-grid field kernels evaluate the sigma-only or the full head")
+        return route("nefes_field_fwd_h3_hashgrid", f"field_fwd[{name},h3,hashgrid]")
+    if is_generic(pk):
+        return route(f"nefes_field_{d}_generic", f"field_{d}[{name},generic]")
     fold = getattr(pk, "fold", False)
-    if fold and not (h3 and mode == L.FIELD_FULL):
-        raise RuntimeError("nefes_amd: a folded pack serves the full pass on the fp16 two-part kernels only")
-    fn = L.load().nefes_field_fwd_h3 if h3 else L.load().nefes_field_fwd_x6
-    with _timed(f"field_fwd[{('sigma', 'static', 'full')[mode]},{'h3' if h3 else 'x6'}{',fold' if fold else ''}]"):
-        L.check(fn(pk.desc, _chk(pk.blob, "blob", torch.uint8), mode, N, S, _chk(rays_o, "rays_o"),
-                                            _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(xyz_enc, "xyz_enc"),
-                                            _chk(viewdirs, "viewdirs"),
-                                            _chk(raw_t, "raw_t"), _chk(masks, "masks", torch.int32), _stream()),
-                "nefes_field_fwd_x6")
-    if masks is not None:
-        _tap("masks", (masks, N, S, pk.width, mode))
-    return raw_t, masks
-
-
-def field_bwd(pk: PackedField, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None,
-              mode=L.FIELD_FULL):
-    dev = pk.blob.device
-    ext = pk.xyz_encoding == L.XYZ_EXTERNAL32
-    if mode == L.FIELD_STATIC and USE_X6 and SPLIT != "f32" and static_h3(pk) and N * S < (1 << 31) - 256:
-        g_pts, g_vs = torch.empty(N * S, 3, device=dev), torch.empty(N * S, 3, device=dev)
-        with _timed("field_bwd[static,h3]"):
-            L.check(L.load().nefes_field_bwd_static_h3(pk.desc, _chk(pk.blob, "blob", torch.uint8), N, S, _chk(rays_o, "rays_o"),
-                                                       _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
-                                                       _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32),
-                                                       _chk(g_pts, "g_pts"), _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_static_h3")
-        return g_pts, g_vs
-    if mode == L.FIELD_STATIC:                      # static head only on the fp32 MFMA (canonical shapes)
+    if not backward:
+        if override is None:
+            split = switched and x6_supported(pk, mode) and (kind != "points" or pk.xyz_encoding == L.XYZ_FREQ10)
+        else:
+            split = override == "split"
+        if split:
+            h3 = h3_serves(pk) and M < H3_MAX_SAMPLES
+            if h3 or mode != L.FIELD_STATIC:
+                if not h3 and not canonical_shape(pk):
+                    raise RuntimeError(f"nefes_amd: {M} samples in one launch exceed the fp16 two-part kernels' 32-bit sample index and "
+                                       f"W={pk.width}, f_dim={pk.feat_dim} has no other instance; render fewer rays per launch")
+                if fold and not (h3 and mode == L.FIELD_FULL):
+                    raise RuntimeError("nefes_amd: a folded pack serves the full pass on the fp16 two-part kernels only")
+                return route("nefes_field_fwd_h3" if h3 else "nefes_field_fwd_x6",
+                             f"field_fwd[{name},{'h3' if h3 else 'x6'}{',fold' if fold else ''}]")
+        if not canonical_shape(pk):
+            raise RuntimeError(f"nefes_amd: the {name} forward of W={pk.width}, f_dim={pk.feat_dim} was routed to "
+                               f"the fp32-MFMA instances (NEFES_SPLIT={SPLIT}; or a frozen network's static head with test_time=False), "
+                               f"which exist for the canonical shapes only.  Compiled: {COMPILED_SET}")
+        return route("nefes_field_fwd", f"field_fwd[{name}]")
+    if mode == L.FIELD_STATIC:
+        if switched and static_h3(pk) and M < H3_MAX_SAMPLES:
+            return route("nefes_field_bwd_static_h3", "field_bwd[static,h3]")
         if not canonical_shape(pk):
             raise RuntimeError(f"nefes_amd: the static-head backward of W={pk.width}, f_dim={pk.feat_dim} was routed to the fp32-MFMA "
                                f"instances (NEFES_SPLIT={SPLIT}), which exist for the canonical shapes only.  Compiled: {COMPILED_SET}")
-        g_pts, g_vs = torch.empty(N * S, 3, device=dev), torch.empty(N * S, 3, device=dev)
-        with _timed("field_bwd[static]"):
-            L.check(L.load().nefes_field_bwd_static(pk.desc, _chk(pk.blob, "blob", torch.uint8), N, S, _chk(rays_o, "rays_o"),
-                                                    _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
-                                                    _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32),
-                                                    _chk(g_pts, "g_pts"), _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_static")
-        return g_pts, g_vs
-    g_pts = None if ext else torch.empty(N * S, 3, device=dev)
-    g_enc = torch.empty(N * S, 32, device=dev) if ext else None
-    g_vs = torch.empty(N * S, 3, device=dev)
-    if USE_X6 and SPLIT != "f32" and x6_supported(pk, L.FIELD_FULL, forward=False):
+        return route("nefes_field_bwd_static", "field_bwd[static]")
+    ext = pk.xyz_encoding == L.XYZ_EXTERNAL32
+    if switched and x6_supported(pk, L.FIELD_FULL):
         h3 = _h3(pk)
-        # (a folded pack with SPLIT switched to "f32" between forward and backward -- tests do that -- lands in the strict-fp32 call
-        # at the end of this function: that stream of a folded blob is the unfolded one and the masks / raw_t are the same)
-        fold = getattr(pk, "fold", False)
         if fold and not h3:
             raise RuntimeError("nefes_amd: a folded pack serves the fp16 two-part kernels only")
-        fn = L.load().nefes_field_bwd_h3 if h3 else L.load().nefes_field_bwd_x6
-        with _timed(("field_bwd[h3,fold]" if fold else "field_bwd[h3]") if h3 else "field_bwd[x6]"):
-            L.check(fn(pk.desc, _chk(pk.blob, "blob", torch.uint8), N, S, _chk(rays_o, "rays_o"),
-                                                _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
-                                                _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32),
-                                                _chk(g_pts, "g_pts"), _chk(g_enc, "g_enc"), _chk(g_vs, "g_vs"), _stream()),
-                    "nefes_field_bwd_x6")
-        return (g_enc if ext else g_pts), g_vs
-    with _timed("field_bwd"):
-      L.check(L.load().nefes_field_bwd(pk.desc, _chk(pk.blob, "blob", torch.uint8), N, S, _chk(rays_o, "rays_o"),
-                                     _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
-                                     _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32),
-                                     _chk(g_pts, "g_pts"), _chk(g_enc, "g_enc"), _chk(g_vs, "g_vs"), _stream()),
-              "nefes_field_bwd")
-    return (g_enc if ext else g_pts), g_vs
+        return route("nefes_field_bwd_h3" if h3 else "nefes_field_bwd_x6",
+                     ("field_bwd[h3,fold]" if fold else "field_bwd[h3]") if h3 else "field_bwd[x6]", ext)
+    return route("nefes_field_bwd", "field_bwd", ext)
+
+
+def _blob(pk):
+    return _chk(pk.blob, "blob", torch.uint8)
+
+
+def _alloc_masks(pk, M, dev, want):
+    return torch.empty(pk.mask_bytes(M) // 4, dtype=torch.int32, device=dev) if want else None
+
+
+def _tap_masks(pk, masks, N, S, mode):
+    if masks is not None and is_generic(pk):
+        _tap("masks_generic", (masks, N, S, pk, mode))
+    elif masks is not None:
+        _tap("masks", (masks, N, S, pk.width, mode))
+
+
+def _input_kind(z, pts, xyz_enc, grid):
+    if grid is not None:
+        return "hashgrid"
+    if z is not None and z.dim() == 1:
+        return "zrow"
+    return "points" if pts is not None else ("enc" if xyz_enc is not None else "rays")
+
+
+def _field_fwd(pk, mode, N, S, rays_o=None, rays_d=None, z=None, pts=None, xyz_enc=None, viewdirs=None, want_masks=False, grid=None,
+               override=None):
+    """THE forward launcher: the kernel field_route names, on freshly allocated raw_t [N, R, S] (+ the ReLU masks a backward needs).
+    Inputs: rays_o / rays_d [N,3] with z [N,S] (or z [S]: one row shared by every ray), or pts [N*S,3], or xyz_enc [N*S,32];
+    grid: an ops.HashGrid the kernel gathers itself."""
+    rt = field_route(pk, mode, False, _input_kind(z, pts, xyz_enc, grid), N * S, override)
+    dev = pk.blob.device
+    raw_t = torch.empty(N, pk.n_raw(mode), S, device=dev)
+    masks = _alloc_masks(pk, N * S, dev, want_masks)
+    o, d, zz, v = _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs")
+    if rt.entry == "nefes_field_fwd_generic":
+        args = (mode, N, S, o, d, zz, _chk(pts, "pts"), v)
+    elif rt.entry == "nefes_field_fwd_h3_hashgrid":
+        args = (grid.desc, _chk(grid.table, "table"), mode, N, S, o, d, zz, 1 if z.dim() == 1 else 0, v)
+    elif rt.entry == "nefes_field_fwd_h3_zrow":
+        args = (mode, N, S, o, d, zz, v)
+    else:                                             # nefes_field_fwd, nefes_field_fwd_x6, nefes_field_fwd_h3: one prototype
+        args = (mode, N, S, o, d, zz, _chk(pts, "pts"), _chk(xyz_enc, "xyz_enc"), v)
+    with _timed(rt.key):
+        L.check(getattr(L.load(), rt.entry)(pk.desc, _blob(pk), *args, _chk(raw_t, "raw_t"), _chk(masks, "masks", torch.int32), _stream()),
+                rt.label)
+    _tap_masks(pk, masks, N, S, mode)
+    return raw_t, masks
+
+
+def _field_bwd(pk, mode, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, grid=None):
+    """THE backward launcher: the kernel field_route names -> (d loss / d pts [N*S,3] -- or d loss / d encoding [N*S,32] for a pack on
+    an external encoding --, d loss / d viewdirs per sample [N*S,3])."""
+    rt = field_route(pk, mode, True, _input_kind(z, pts, None, grid), N * S)
+    dev = pk.blob.device
+    g_in, g_vs = torch.empty(N * S, 32 if rt.g_enc else 3, device=dev), torch.empty(N * S, 3, device=dev)
+    o, d, zz, v = _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs")
+    out = (_chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32))
+    if rt.entry == "nefes_field_bwd_generic":
+        args = (mode, N, S, o, d, zz, _chk(pts, "pts"), v, *out, _chk(g_in, "g_pts"))
+    elif rt.entry == "nefes_field_bwd_h3_hashgrid":
+        args = (grid.desc, _chk(grid.table, "table"), N, S, o, d, zz, v, *out, _chk(g_in, "g_pts"))
+    elif rt.entry.startswith("nefes_field_bwd_static"):       # nefes_field_bwd_static, nefes_field_bwd_static_h3
+        args = (N, S, o, d, zz, _chk(pts, "pts"), v, *out, _chk(g_in, "g_pts"))
+    else:                                             # nefes_field_bwd, nefes_field_bwd_x6, nefes_field_bwd_h3: g_pts AND g_enc
+        args = (N, S, o, d, zz, _chk(pts, "pts"), v, *out, None if rt.g_enc else _chk(g_in, "g_pts"), _chk(g_in, "g_enc") if rt.g_enc else None)
+    with _timed(rt.key):
+        L.check(getattr(L.load(), rt.entry)(pk.desc, _blob(pk), *args, _chk(g_vs, "g_vs"), _stream()), rt.label)
+    return g_in, g_vs
+
+
+def field_fwd(pk, mode, N, S, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, want_masks=False, xyz_enc=None):
+    """The strict fp32-MFMA forward (canonical shapes) -> (raw_t, masks)."""
+    return _field_fwd(pk, mode, N, S, rays_o, rays_d, z, pts, xyz_enc, viewdirs, want_masks, override="f32")
+
+
+def field_fwd_x6(pk, mode, N, S, rays_o=None, rays_d=None, z=None, viewdirs=None, want_masks=False, xyz_enc=None, pts=None):
+    """field_fwd on the split-product instances (same outputs, same mask words): fp16 two-part (default) or bf16x6, with the
+    fallbacks of field_route's split route."""
+    return _field_fwd(pk, mode, N, S, rays_o, rays_d, z, pts, xyz_enc, viewdirs, want_masks, override="split")
+
+
+def field_bwd(pk, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, mode=L.FIELD_FULL):
+    return _field_bwd(pk, mode, N, S, raw_t, g_raw_t, masks, rays_o, rays_d, z, pts, viewdirs)
+
+
+def field_fwd_generic(pk, mode, N, S, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, want_masks=False):
+    return _field_fwd(pk, mode, N, S, rays_o, rays_d, z, pts, None, viewdirs, want_masks)
+
+
+def field_bwd_generic(pk, mode, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None):
+    return _field_bwd(pk, mode, N, S, raw_t, g_raw_t, masks, rays_o, rays_d, z, pts, viewdirs)
 
 
 def ray_grad_reduce(N, S, z, g_pts, g_vs):
@@ -531,19 +642,21 @@ def ray_grad_reduce(N, S, z, g_pts, g_vs):
     return g_o, g_d, g_v
 
 
+_NO_SIGMA_BWD = ("nefes_amd: the sigma-only field pass has no backward (the reference evaluates it without gradients at test time: "
+                 "nerfh_nff.py:192-202)")
+
+
 class FieldFromRays(torch.autograd.Function):
-    """Fused pts = o + d*z -> embed -> MLP (rendering.py:142 + nerfh_nff.py:217-231, :525-576).
-    Returns raw_t [N, R, S].  Differentiable w.r.t. rays_o, rays_d, viewdirs in FULL mode (frozen weights)."""
+    """Fused pts = o + d*z -> embed -> MLP (rendering.py:142 + nerfh_nff.py:217-231, :525-576) on whichever kernels field_route names
+    for `pk` (a tuned or a generic pack).  Returns raw_t [N, R, S].  Differentiable w.r.t. rays_o, rays_d, viewdirs in FULL and
+    STATIC mode (frozen weights)."""
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, viewdirs, z, pk, mode):
         rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
         N, S = z.shape
         need = mode in (L.FIELD_FULL, L.FIELD_STATIC) and any(ctx.needs_input_grad[:3])
-        if USE_X6 and SPLIT != "f32" and x6_supported(pk, mode):
-            raw_t, masks = field_fwd_x6(pk, mode, N, S, rays_o, rays_d, z, viewdirs=viewdirs, want_masks=need)
-        else:
-            raw_t, masks = field_fwd(pk, mode, N, S, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs, want_masks=need)
+        raw_t, masks = _field_fwd(pk, mode, N, S, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs, want_masks=need)
         ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
         if need:
             ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks)
@@ -552,20 +665,13 @@ class FieldFromRays(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_raw_t):
         if not ctx.have:
-            raise NotImplementedError("nefes_amd: the sigma-only field pass has no backward (the reference evaluates it "
-                                      "without gradients at test time: nerfh_nff.py:192-202)")
+            raise NotImplementedError(_NO_SIGMA_BWD)
         rays_o, rays_d, viewdirs, z, raw_t, masks = ctx.saved_tensors
         N, S = z.shape
         ctx.pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = field_bwd(ctx.pk, N, S, raw_t, _f32(g_raw_t), masks, rays_o=rays_o, rays_d=rays_d, z=z,
-                                viewdirs=viewdirs, mode=ctx.mode)
+        g_pts, g_vs = _field_bwd(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs)
         g_o, g_d, g_v = ray_grad_reduce(N, S, z, g_pts, g_vs)
         return g_o, g_d, g_v, None, None, None
-
-
-# The factored feature head (csrc/field_fwd_h3.hip FH, nefes_amd/render.py): a frozen width-128 fine network emits g = relu(dir_encoding)
-# instead of its 128 feature channels and the head's matrix is applied once per ray to the composited g; "0": the plain kernels.
-FACTORED_HEAD = os.environ.get("NEFES_FACTORED_HEAD", "1") != "0"
 
 
 class FeatHead(torch.autograd.Function):
@@ -596,6 +702,32 @@ class FeatHead(torch.autograd.Function):
         return g_gmap, None, None, None
 
 
+def _fh_fwd(pk, rays_o, rays_d, viewdirs, z, want_masks):
+    """The factored-head forward launch -> (raw_t [N, 3 + (W/2 + 1) + 6, S] = rgb | g | ones | sigma | transient (5), masks)."""
+    N, S = z.shape
+    raw_t = torch.empty(N, 3 + pk.width // 2 + 1 + 6, S, device=z.device)
+    masks = _alloc_masks(pk, N * S, z.device, want_masks)
+    with _timed("field_fwd[full,h3,fh]"):
+        L.check(L.load().nefes_field_fwd_h3_fh(pk.desc, _blob(pk), L.FIELD_FULL, N, S, _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"),
+                                               _chk(z, "z"), _chk(viewdirs, "viewdirs"), _chk(raw_t, "raw_t"),
+                                               _chk(masks, "masks", torch.int32), _stream()), "nefes_field_fwd_h3_fh")
+    _tap_masks(pk, masks, N, S, L.FIELD_FULL)
+    return raw_t, masks
+
+
+def _fh_bwd(pk, rays_o, rays_d, viewdirs, z, raw_t, g_raw_t, g_gmap, masks):
+    """The factored-head backward launch + the reduction over each ray's samples -> (g_o, g_d, g_v).  g_gmap [N, W/2 + 1]: the per-ray
+    gradient of the composited g channels (the kernel forms d loss / d g = w_s g_gmap[ray] itself), or None: g_raw_t holds it."""
+    N, S = z.shape
+    g_pts, g_vs = torch.empty(N * S, 3, device=z.device), torch.empty(N * S, 3, device=z.device)
+    with _timed("field_bwd[h3,fh]"):
+        L.check(L.load().nefes_field_bwd_h3_fh(pk.desc, _blob(pk), N, S, _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(z, "z"),
+                                               _chk(viewdirs, "viewdirs"), _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"),
+                                               _chk(g_gmap, "g_gmap"), _chk(masks, "masks", torch.int32), _chk(g_pts, "g_pts"),
+                                               _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_h3_fh")
+    return ray_grad_reduce(N, S, z, g_pts, g_vs)
+
+
 class FieldFromRaysFH(torch.autograd.Function):
     """FieldFromRays for the factored head: raw_t [N, 3 + (W/2 + 1) + 6, S] = rgb | g | ones | sigma | transient (5); pk = the network packed
     without its feature rows (NeRFH_NFF.packed_fh).  Differentiable w.r.t. rays_o, rays_d, viewdirs (frozen weights)."""
@@ -603,19 +735,10 @@ class FieldFromRaysFH(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rays_o, rays_d, viewdirs, z, pk):
         rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
-        N, S = z.shape
-        if N * S >= (1 << 31) - 256:
+        if z.shape[0] * z.shape[1] >= H3_MAX_SAMPLES:
             raise RuntimeError("nefes_amd: too many samples for one launch of the fp16 two-part kernels (32-bit sample index)")
         need = any(ctx.needs_input_grad[:3])
-        R = 3 + pk.width // 2 + 1 + 6
-        raw_t = torch.empty(N, R, S, device=z.device)
-        masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=z.device) if need else None
-        with _timed("field_fwd[full,h3,fh]"):
-            L.check(L.load().nefes_field_fwd_h3_fh(pk.desc, _chk(pk.blob, "blob", torch.uint8), L.FIELD_FULL, N, S, _chk(rays_o, "rays_o"),
-                                                   _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs"), _chk(raw_t, "raw_t"),
-                                                   _chk(masks, "masks", torch.int32), _stream()), "nefes_field_fwd_h3_fh")
-        if masks is not None:
-            _tap("masks", (masks, N, S, pk.width, L.FIELD_FULL))
+        raw_t, masks = _fh_fwd(pk, rays_o, rays_d, viewdirs, z, need)
         ctx.pk, ctx.have, ctx.pk_gen = pk, need, pk.generation
         if need:
             ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks)
@@ -626,17 +749,8 @@ class FieldFromRaysFH(torch.autograd.Function):
         if not ctx.have:
             return None, None, None, None, None
         rays_o, rays_d, viewdirs, z, raw_t, masks = ctx.saved_tensors
-        N, S = z.shape
-        pk = ctx.pk
-        pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = torch.empty(N * S, 3, device=z.device), torch.empty(N * S, 3, device=z.device)
-        with _timed("field_bwd[h3,fh]"):
-            L.check(L.load().nefes_field_bwd_h3_fh(pk.desc, _chk(pk.blob, "blob", torch.uint8), N, S, _chk(rays_o, "rays_o"),
-                                                   _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs"), _chk(raw_t, "raw_t"),
-                                                   _chk(_f32(g_raw_t), "g_raw_t"), None, _chk(masks, "masks", torch.int32), _chk(g_pts, "g_pts"),
-                                                   _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_h3_fh")
-        g_o, g_d, g_v = ray_grad_reduce(N, S, z, g_pts, g_vs)
-        return g_o, g_d, g_v, None, None
+        ctx.pk.check_generation(ctx.pk_gen)
+        return _fh_bwd(ctx.pk, rays_o, rays_d, viewdirs, z, raw_t, _f32(g_raw_t), None, masks) + (None, None)
 
 
 class RenderFineFH(torch.autograd.Function):
@@ -652,14 +766,7 @@ class RenderFineFH(torch.autograd.Function):
         N, S = z.shape
         need = any(ctx.needs_input_grad[:3])
         Cg = pk.width // 2
-        raw_t = torch.empty(N, 3 + Cg + 1 + 6, S, device=z.device)
-        masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=z.device) if need else None
-        with _timed("field_fwd[full,h3,fh]"):
-            L.check(L.load().nefes_field_fwd_h3_fh(pk.desc, _chk(pk.blob, "blob", torch.uint8), L.FIELD_FULL, N, S, _chk(rays_o, "rays_o"),
-                                                   _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs"), _chk(raw_t, "raw_t"),
-                                                   _chk(masks, "masks", torch.int32), _stream()), "nefes_field_fwd_h3_fh")
-        if masks is not None:
-            _tap("masks", (masks, N, S, pk.width, L.FIELD_FULL))
+        raw_t, masks = _fh_fwd(pk, rays_o, rays_d, viewdirs, z, need)
         rgb, gmap, disp, acc, _, _, _ = composite_fwd(raw_t, z, Cg + 1, flags, beta_min)
         if emit_gmap:
             # the caller applies the feature head itself, folded into whatever linear layer consumes the features (the refinement loop:
@@ -703,18 +810,11 @@ class RenderFineFH(torch.autograd.Function):
             L.check(L.load().nefes_composite_bwd(N, S, Cg + 1, flags | L.COMP_FEAT_WEIGHTS_ONLY, _chk(raw_t, "raw_t"), _chk(z, "z"),
                                                  _chk(g_rgb, "g_rgb"), None, _chk(g_disp, "g_disp"), _chk(g_acc, "g_acc"), None, None, None,
                                                  _chk(g_raw_t, "g_raw_t"), _stream()), "nefes_composite_bwd")
-        g_pts, g_vs = torch.empty(N * S, 3, device=z.device), torch.empty(N * S, 3, device=z.device)
-        with _timed("field_bwd[h3,fh]"):
-            L.check(L.load().nefes_field_bwd_h3_fh(pk.desc, _chk(pk.blob, "blob", torch.uint8), N, S, _chk(rays_o, "rays_o"),
-                                                   _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs"), _chk(raw_t, "raw_t"),
-                                                   _chk(g_raw_t, "g_raw_t"), _chk(g_gmap, "g_gmap"), _chk(masks, "masks", torch.int32),
-                                                   _chk(g_pts, "g_pts"), _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_h3_fh")
-        g_o, g_d, g_v = ray_grad_reduce(N, S, z, g_pts, g_vs)
-        return g_o, g_d, g_v, None, None, None, None, None, None, None, None
+        return _fh_bwd(pk, rays_o, rays_d, viewdirs, z, raw_t, g_raw_t, g_gmap, masks) + (None,) * 8
 
 
 class FieldFromPoints(torch.autograd.Function):
-    """run_network_NeRFH_NFF call surface: explicit pts [N,S,3] (+ viewdirs [N,3]) -> raw_t [N,R,S]."""
+    """run_network_NeRFH_NFF call surface: explicit pts [N,S,3] (+ viewdirs [N,3]) -> raw_t [N,R,S], on a tuned or a generic pack."""
 
     @staticmethod
     def forward(ctx, pts, viewdirs, pk, mode):
@@ -724,10 +824,7 @@ class FieldFromPoints(torch.autograd.Function):
             viewdirs = torch.zeros(N, 3, device=pts.device)
         viewdirs = _f32(viewdirs)
         need = mode in (L.FIELD_FULL, L.FIELD_STATIC) and any(ctx.needs_input_grad[:2])
-        if USE_X6 and SPLIT != "f32" and x6_supported(pk, mode) and pk.xyz_encoding == L.XYZ_FREQ10:
-            raw_t, masks = field_fwd_x6(pk, mode, N, S, pts=pts.reshape(-1, 3), viewdirs=viewdirs, want_masks=need)
-        else:
-            raw_t, masks = field_fwd(pk, mode, N, S, pts=pts.reshape(-1, 3), viewdirs=viewdirs, want_masks=need)
+        raw_t, masks = _field_fwd(pk, mode, N, S, pts=pts.reshape(-1, 3), viewdirs=viewdirs, want_masks=need)
         ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
         if need:
             ctx.save_for_backward(pts, viewdirs, raw_t, masks)
@@ -736,11 +833,11 @@ class FieldFromPoints(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_raw_t):
         if not ctx.have:
-            raise NotImplementedError("nefes_amd: the sigma-only field pass has no backward (nerfh_nff.py:192-202 runs it without gradients)")
+            raise NotImplementedError(_NO_SIGMA_BWD)
         pts, viewdirs, raw_t, masks = ctx.saved_tensors
         N, S = pts.shape[0], pts.shape[1]
         ctx.pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = field_bwd(ctx.pk, N, S, raw_t, _f32(g_raw_t), masks, pts=pts.reshape(-1, 3), viewdirs=viewdirs, mode=ctx.mode)
+        g_pts, g_vs = _field_bwd(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, pts=pts.reshape(-1, 3), viewdirs=viewdirs)
         zeros = torch.zeros(N, S, device=pts.device)
         _, _, g_v = ray_grad_reduce(N, S, zeros, g_pts, g_vs)
         return g_pts.reshape(N, S, 3), g_v, None, None
@@ -749,9 +846,6 @@ class FieldFromPoints(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------
 # generic field kernels (csrc/field_generic.hip): any --netwidth / --netdepth, frozen weights
 # ---------------------------------------------------------------------------------------------
-# "1": networks the tuned instances DO serve run on the generic kernels too (off by default; so that the two can be compared on
-# the same weights).  Networks the tuned instances do not serve always take the generic kernels.
-FIELD_GENERIC = os.environ.get("NEFES_FIELD_GENERIC", "0") == "1"
 # "1": a trainable network on the generic kernels trains (train.field_train_generic: their train-mode instances + the weight-gradient
 # kernels of csrc/train.hip).  Off by default: such a network is refused, as before the train-mode instances existed.
 GENERIC_TRAIN = os.environ.get("NEFES_GENERIC_TRAIN", "0") == "1"
@@ -831,103 +925,13 @@ class PackedGeneric:
         return 1 if mode == L.FIELD_SIGMA else (3 + self.feat_dim + (1 if mode == L.FIELD_STATIC else 6))
 
 
-def is_generic(pk):
-    return bool(getattr(pk, "generic", False))
-
-
-def field_fwd_generic(pk: PackedGeneric, mode, N, S, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, want_masks=False):
-    dev = pk.blob.device
-    raw_t = torch.empty(N, pk.n_raw(mode), S, device=dev)
-    masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=dev) if want_masks else None
-    with _timed(f"field_fwd[{('sigma', 'static', 'full')[mode]},generic]"):
-        L.check(L.load().nefes_field_fwd_generic(pk.desc, _chk(pk.blob, "blob", torch.uint8), mode, N, S, _chk(rays_o, "rays_o"),
-                                                 _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
-                                                 _chk(raw_t, "raw_t"), _chk(masks, "masks", torch.int32), _stream()),
-                "nefes_field_fwd_generic")
-    if masks is not None:
-        _tap("masks_generic", (masks, N, S, pk, mode))
-    return raw_t, masks
-
-
-def field_bwd_generic(pk: PackedGeneric, mode, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None):
-    dev = pk.blob.device
-    g_pts, g_vs = torch.empty(N * S, 3, device=dev), torch.empty(N * S, 3, device=dev)
-    with _timed(f"field_bwd[{('sigma', 'static', 'full')[mode]},generic]"):
-        L.check(L.load().nefes_field_bwd_generic(pk.desc, _chk(pk.blob, "blob", torch.uint8), mode, N, S, _chk(rays_o, "rays_o"),
-                                                 _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(pts, "pts"), _chk(viewdirs, "viewdirs"),
-                                                 _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32),
-                                                 _chk(g_pts, "g_pts"), _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_generic")
-    return g_pts, g_vs
-
-
-class FieldFromRaysGeneric(torch.autograd.Function):
-    """FieldFromRays on the generic kernels: same arguments, same raw_t [N, R, S]; differentiable w.r.t. rays_o, rays_d, viewdirs in
-    FULL and STATIC mode (frozen weights)."""
-
-    @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, z, pk, mode):
-        rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
-        N, S = z.shape
-        need = mode in (L.FIELD_FULL, L.FIELD_STATIC) and any(ctx.needs_input_grad[:3])
-        raw_t, masks = field_fwd_generic(pk, mode, N, S, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs, want_masks=need)
-        ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
-        if need:
-            ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks)
-        return raw_t
-
-    @staticmethod
-    def backward(ctx, g_raw_t):
-        if not ctx.have:
-            raise NotImplementedError("nefes_amd: the sigma-only field pass has no backward (the reference evaluates it "
-                                      "without gradients at test time: nerfh_nff.py:192-202)")
-        rays_o, rays_d, viewdirs, z, raw_t, masks = ctx.saved_tensors
-        N, S = z.shape
-        ctx.pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = field_bwd_generic(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, rays_o=rays_o, rays_d=rays_d, z=z,
-                                        viewdirs=viewdirs)
-        g_o, g_d, g_v = ray_grad_reduce(N, S, z, g_pts, g_vs)
-        return g_o, g_d, g_v, None, None, None
-
-
-class FieldFromPointsGeneric(torch.autograd.Function):
-    """FieldFromPoints on the generic kernels."""
-
-    @staticmethod
-    def forward(ctx, pts, viewdirs, pk, mode):
-        pts = _f32(pts)
-        N, S = pts.shape[0], pts.shape[1]
-        if viewdirs is None:
-            viewdirs = torch.zeros(N, 3, device=pts.device)
-        viewdirs = _f32(viewdirs)
-        need = mode in (L.FIELD_FULL, L.FIELD_STATIC) and any(ctx.needs_input_grad[:2])
-        raw_t, masks = field_fwd_generic(pk, mode, N, S, pts=pts.reshape(-1, 3), viewdirs=viewdirs, want_masks=need)
-        ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
-        if need:
-            ctx.save_for_backward(pts, viewdirs, raw_t, masks)
-        return raw_t
-
-    @staticmethod
-    def backward(ctx, g_raw_t):
-        if not ctx.have:
-            raise NotImplementedError("nefes_amd: the sigma-only field pass has no backward (nerfh_nff.py:192-202 runs it without gradients)")
-        pts, viewdirs, raw_t, masks = ctx.saved_tensors
-        N, S = pts.shape[0], pts.shape[1]
-        ctx.pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = field_bwd_generic(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, pts=pts.reshape(-1, 3), viewdirs=viewdirs)
-        zeros = torch.zeros(N, S, device=pts.device)
-        _, _, g_v = ray_grad_reduce(N, S, zeros, g_pts, g_vs)
-        return g_pts.reshape(N, S, 3), g_v, None, None
-
-
 def field_from_rays(rays_o, rays_d, viewdirs, z, pk, mode):
     """The field along rays on whichever kernels `pk` was packed for (NeRFH_NFF.packed_any)."""
-    fn = FieldFromRaysGeneric if is_generic(pk) else FieldFromRays
-    return fn.apply(rays_o, rays_d, viewdirs, z, pk, mode)
+    return FieldFromRays.apply(rays_o, rays_d, viewdirs, z, pk, mode)
 
 
 def field_from_points(pts, viewdirs, pk, mode):
-    fn = FieldFromPointsGeneric if is_generic(pk) else FieldFromPoints
-    return fn.apply(pts, viewdirs, pk, mode)
+    return FieldFromPoints.apply(pts, viewdirs, pk, mode)
 
 
 class FieldFromEncoding(torch.autograd.Function):
@@ -940,10 +944,7 @@ class FieldFromEncoding(torch.autograd.Function):
         N, S = enc.shape[0], enc.shape[1]
         viewdirs = torch.zeros(N, 3, device=enc.device) if viewdirs is None else _f32(viewdirs)
         need = mode == L.FIELD_FULL and any(ctx.needs_input_grad[:2])
-        if USE_X6 and SPLIT != "f32" and x6_supported(pk, mode):
-            raw_t, masks = field_fwd_x6(pk, mode, N, S, xyz_enc=enc.reshape(-1, 32), viewdirs=viewdirs, want_masks=need)
-        else:
-            raw_t, masks = field_fwd(pk, mode, N, S, xyz_enc=enc.reshape(-1, 32), viewdirs=viewdirs, want_masks=need)
+        raw_t, masks = _field_fwd(pk, mode, N, S, xyz_enc=enc.reshape(-1, 32), viewdirs=viewdirs, want_masks=need)
         ctx.pk, ctx.have, ctx.pk_gen = pk, need, pk.generation
         if need:
             ctx.save_for_backward(viewdirs, raw_t, masks)
@@ -957,7 +958,7 @@ class FieldFromEncoding(torch.autograd.Function):
         viewdirs, raw_t, masks = ctx.saved_tensors
         N, S = ctx.shape
         ctx.pk.check_generation(ctx.pk_gen)
-        g_enc, g_vs = field_bwd(ctx.pk, N, S, raw_t, _f32(g_raw_t), masks, viewdirs=viewdirs)
+        g_enc, g_vs = _field_bwd(ctx.pk, L.FIELD_FULL, N, S, raw_t, _f32(g_raw_t), masks, viewdirs=viewdirs)
         zeros = torch.zeros(N, S, device=raw_t.device)
         _, _, g_v = ray_grad_reduce(N, S, zeros, g_vs, g_vs)
         return g_enc.reshape(N, S, 32), g_v, None, None
@@ -1090,42 +1091,17 @@ class HashGrid:
         return torch.is_grad_enabled() and self.table.requires_grad
 
 
-# BASELINE configs[3] with the hash grid evaluated INSIDE the field kernels (csrc/hashgrid.h, nefes_field_fwd_h3_hashgrid /
-# nefes_field_bwd_h3_hashgrid); "0": the separate launches HashGridEncode + FieldFromEncoding (the tests compare the two)
-FUSED_HASHGRID = os.environ.get("NEFES_FUSED_HASHGRID", "1") != "0"
-
-
-def hashgrid_fused_ok(pk, grid):
-    """The fp16 two-part field kernels can gather this hash grid themselves: width 256, head class 0, sixteen levels x two features.
-    (Head class 1 -- the 128-channel feature head -- has instances on a SUPPLIED encoding only, csrc/field_bwd_h3.hip part 13: its
-    renders take HashGridEncode + FieldFromEncoding, and with them the four-launch coarse pass.)"""
-    return (FUSED_HASHGRID and isinstance(grid, HashGrid) and _h3(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32 and pk.width == 256
-            and head_class(pk.feat_dim) == 0 and grid.desc.n_levels == 16 and grid.desc.n_features == 2)
-
-
 class FieldFromRaysHashGrid(torch.autograd.Function):
     """pts = o + d z -> hash-grid encoding -> MLP in ONE launch each way (rendering.py:114,142 + nerfh_tcnn.py:151-182): raw_t [N, R, S];
     differentiable w.r.t. rays_o, rays_d, viewdirs in FULL mode (frozen weights, frozen table).  Forward bit-identical to
-    HashGridEncode + FieldFromEncoding."""
+    HashGridEncode + FieldFromEncoding.  The caller asks hashgrid_fused_ok first (NEFES_FUSED_HASHGRID: "0" = those separate launches)."""
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, viewdirs, z, pk, mode, grid):
         rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
         N, S = z.shape
-        if N * S >= (1 << 31) - 256:
-            raise RuntimeError("nefes_amd: too many samples for one launch of the fp16 two-part kernels (32-bit sample index)")
-        if mode not in (L.FIELD_SIGMA, L.FIELD_FULL):
-            raise NotImplementedError("nefes_amd: the hash-grid field kernels evaluate the sigma-only or the full head")
         need = mode == L.FIELD_FULL and any(ctx.needs_input_grad[:3])
-        raw_t = torch.empty(N, pk.n_raw(mode), S, device=z.device)
-        masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=z.device) if need else None
-        with _timed(f"field_fwd[{('sigma', 'static', 'full')[mode]},h3,hashgrid]"):
-            L.check(L.load().nefes_field_fwd_h3_hashgrid(pk.desc, _chk(pk.blob, "blob", torch.uint8), grid.desc, _chk(grid.table, "table"), mode, N, S,
-                                                         _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(z, "z"), 0, _chk(viewdirs, "viewdirs"),
-                                                         _chk(raw_t, "raw_t"), _chk(masks, "masks", torch.int32), _stream()),
-                    "nefes_field_fwd_h3_hashgrid")
-        if masks is not None:
-            _tap("masks", (masks, N, S, pk.width, mode))
+        raw_t, masks = _field_fwd(pk, mode, N, S, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs, want_masks=need, grid=grid)
         ctx.pk, ctx.grid, ctx.have, ctx.pk_gen = pk, grid, need, pk.generation
         if need:
             ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks)
@@ -1134,17 +1110,12 @@ class FieldFromRaysHashGrid(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_raw_t):
         if not ctx.have:
-            raise NotImplementedError("nefes_amd: the sigma-only field pass has no backward (nerfh_nff.py:192-202 runs it without gradients)")
+            raise NotImplementedError(_NO_SIGMA_BWD)
         rays_o, rays_d, viewdirs, z, raw_t, masks = ctx.saved_tensors
         N, S = z.shape
-        pk, grid = ctx.pk, ctx.grid
-        pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = torch.empty(N * S, 3, device=z.device), torch.empty(N * S, 3, device=z.device)
-        with _timed("field_bwd[h3,hashgrid]"):
-            L.check(L.load().nefes_field_bwd_h3_hashgrid(pk.desc, _chk(pk.blob, "blob", torch.uint8), grid.desc, _chk(grid.table, "table"), N, S,
-                                                         _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs"),
-                                                         _chk(raw_t, "raw_t"), _chk(_f32(g_raw_t), "g_raw_t"), _chk(masks, "masks", torch.int32),
-                                                         _chk(g_pts, "g_pts"), _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_h3_hashgrid")
+        ctx.pk.check_generation(ctx.pk_gen)
+        g_pts, g_vs = _field_bwd(ctx.pk, L.FIELD_FULL, N, S, raw_t, _f32(g_raw_t), masks, rays_o=rays_o, rays_d=rays_d, z=z,
+                                 viewdirs=viewdirs, grid=ctx.grid)
         g_o, g_d, g_v = ray_grad_reduce(N, S, z, g_pts, g_vs)
         return g_o, g_d, g_v, None, None, None, None
 

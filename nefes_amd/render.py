@@ -116,7 +116,7 @@ def _field(pk, mode, rays_o, rays_d, viewdirs, z, xyz_encoder):
     if ops.is_generic(pk):
         raise NotImplementedError(f"nefes_amd: an external / hash-grid encoding is not built for the generic field kernels "
                                   f"(W={pk.width}, D={pk.depth}, f_dim={pk.feat_dim})")
-    if (mode != L.FIELD_STATIC and ops.hashgrid_fused_ok(pk, xyz_encoder) and z.shape[0] * z.shape[1] < (1 << 31) - 256
+    if (mode != L.FIELD_STATIC and ops.hashgrid_fused_ok(pk, xyz_encoder) and z.shape[0] * z.shape[1] < ops.H3_MAX_SAMPLES
             and not _grid_trainable(xyz_encoder)):
         # (a trainable table takes the separate launches below: they hand HashGridEncode the gradient of the encoding)
         # BASELINE configs[3]: the field kernels gather the hash grid themselves (no [M, 32] encoding, no pts tensor)
@@ -213,7 +213,7 @@ def _fine_pass(rays_o, rays_d, viewdirs, z_fine, z_samples, network_fine, cfg, C
     z_f = z_samples if cfg.use_fine_only else z_fine
     flags = 0
     if (cfg.test_time and cfg.NeRFW and cfg.nerfh_nff and cfg.xyz_encoder is None and cfg.raw_noise_std == 0.
-            and z_f.shape[0] * z_f.shape[1] < (1 << 31) - 256 and network_fine.factored_head_ok()):
+            and z_f.shape[0] * z_f.shape[1] < ops.H3_MAX_SAMPLES and network_fine.factored_head_ok()):
         # FACTORED HEAD (frozen width-128 network, test time).  The rgb+feature head is linear in g = relu(dir_encoding) and compositing is
         # linear in the head's outputs with weights that do not depend on them (nerfh_nff.py:119-125, :487-490):
         #     feat = sum_s w_s (W_f g_s + b_f) = W_f (sum_s w_s g_s) + b_f sum_s w_s.
@@ -232,7 +232,7 @@ def _fine_pass(rays_o, rays_d, viewdirs, z_fine, z_samples, network_fine, cfg, C
             ret["feat_is_gmap"] = True
         return ret
     mode = L.FIELD_FULL if cfg.NeRFW else L.FIELD_STATIC
-    if (mode == L.FIELD_FULL and cfg.xyz_encoder is None and z_f.shape[0] * z_f.shape[1] < (1 << 31) - 256
+    if (mode == L.FIELD_FULL and cfg.xyz_encoder is None and z_f.shape[0] * z_f.shape[1] < ops.H3_MAX_SAMPLES
             and network_fine.fold_ok()):
         # a frozen network on the fp16 pipe: the pack with xyz_encoding_final folded into the head matrices (decided per render;
         # forward and backward of the autograd node use this one pack)

@@ -146,14 +146,15 @@ def param_names(net, mode):
 
 def fp16_pipe(pk):
     """The train-mode forward (and the fused dX chain) run on the fp16 two-part instances when ops.SPLIT selects them, the
-    network's fp16 streams are current, and the shape has them (both widths x both head classes, frequency embedding)."""
-    return ops._h3(pk) and ops.h3_shape(pk) and pk.xyz_encoding == L.XYZ_FREQ10
+    network's fp16 streams are current, and the shape has them (both widths x both head classes, frequency embedding): the
+    static head's condition."""
+    return ops.static_h3(pk)
 
 
 def ext_pipe(pk):
     """The train-mode instances of a network on an external 32-feature encoding (a hash grid): fp16 two-part pipe, width 256, either
     head class (csrc/field_fwd_h3.hip H3_TRAIN_EXT_*, parts 3 / 15)."""
-    return ops._h3(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32 and pk.width == 256 and ops.head_class(pk.feat_dim) >= 0
+    return ops.h3_serves(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32        # (h3_shape: width 256 is the external encoding's only width)
 
 
 FUSED_DX = True       # one fused backward launch (nefes_field_bwd_train) instead of the layer-by-layer nefes_train_dx chain
@@ -352,7 +353,7 @@ class FieldTrainEncoded(torch.autograd.Function):
                                       f"on the fp16 two-part instances (NEFES_SPLIT=h3); got W={pk.width}, f_dim={pk.feat_dim}, "
                                       f"NEFES_SPLIT={ops.SPLIT}.  Compiled: {ops.COMPILED_SET}")
         N, S = enc.shape[0], enc.shape[1]
-        if N * S >= (1 << 31) - 256:
+        if N * S >= ops.H3_MAX_SAMPLES:
             raise RuntimeError("nefes_amd: too many samples for one launch of the fp16 two-part kernels (32-bit sample index)")
         e, v = ops._f32(enc).reshape(N * S, 32), ops._f32(viewdirs)
         R = 3 + pk.feat_dim + (1 if mode == L.FIELD_STATIC else 6)
@@ -538,7 +539,7 @@ class FieldTrainGeneric(torch.autograd.Function):
         with ops._timed("field_bwd_train[generic]"):
             g = weight_grads_generic(ctx.net, ctx.pk, ctx.mode, N, S, raw_t, ops._f32(g_raw_t), acts, o, d, v, zz, masks)
         g_pts, g_vs = g.pop("__rays__")
-        g = ctx.net.shrink_grads_generic(g)    # a network on fewer embedding octaves: drop the columns packed_generic padded
+        g = ctx.net.shrink_grads(g)    # a network on fewer embedding octaves: drop the columns packed_generic padded
         g_rays = (None, None, None)
         if any(ctx.needs_input_grad[:3]):
             g_rays = ops.ray_grad_reduce(N, S, zz, g_pts, g_vs)
