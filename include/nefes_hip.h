@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define NEFES_ABI_VERSION 18
+#define NEFES_ABI_VERSION 19
 /* layout version of the blob nefes_pack_weights writes (second header word): moves when that layout does, not with every new call */
 #define NEFES_BLOB_FORMAT 17
 
@@ -300,6 +300,20 @@ int nefes_feat_head_bwd(int N, int C, int F, const float* g_feat, const float* w
 int nefes_field_bwd_static_h3(const NefesNetDesc* desc, const void* packed, int N, int S, const float* rays_o, const float* rays_d,
                               const float* z, const float* pts, const float* viewdirs, const float* raw_t, const float* g_raw_t,
                               const uint32_t* masks, float* g_pts, float* g_viewdirs_s, void* stream);
+/* Which compiled instance of the fp16 two-part kernels (csrc/field_h3_instances.h) an entry point above or one of the
+ * nefes_field_{fwd,bwd}_train_h3[_ext] calls below would launch for `desc`, without launching it (host code only; for tests).
+ * request_flags names the entry point: 0 = nefes_field_fwd_h3 / nefes_field_bwd_h3, or one of the NEFES_H3_REQ_* families
+ * (NEFES_H3_REQ_EXT together with NEFES_H3_REQ_TRAIN: the _ext calls); `mode` as that entry point takes it, ignored by those that
+ * take none.  Returns what the entry point would return with every pointer valid, a sixteen-level grid and a small N * S: 0 and the
+ * instance as text in name[cap], e.g. "fwd p5 <FULL,FREQ10,256,5,0,0>" (object part, then the table row), or the entry point's
+ * refusal and an empty name; NEFES_E_BADARG for flags that name no entry point. */
+#define NEFES_H3_REQ_TRAIN 1
+#define NEFES_H3_REQ_EXT 2
+#define NEFES_H3_REQ_HASHGRID 4
+#define NEFES_H3_REQ_FH 8
+#define NEFES_H3_REQ_ZROW 16       /* forward only */
+#define NEFES_H3_REQ_STATIC_BWD 32 /* backward only: nefes_field_bwd_static_h3 */
+int nefes_field_h3_instance(const NefesNetDesc* desc, int backward, int mode, unsigned request_flags, char* name, size_t cap);
 
 /* ---- generic field kernels: any --netwidth / --netdepth (script/models/options.py:30-31, nerfh_nff.py:452-478,640-662) ----
  * The calls above serve the tuned instances (depth 8, skip at layer 5, widths 128 / 256).  These serve every other shape on one

@@ -4,21 +4,21 @@
 // (field_bwd.hip); the transposed products of transient_encoding.{4,2,0}, dir_encoding, xyz_encoding_final and layers 8..1 run on
 // v_mfma_f32_32x32x16_f16 as hh + hl + lh of power-of-two scaled (hi, lo) fp16 pairs; the three narrow head products (3+C, 5 and
 // 1 k-values) stay on the fp32 MFMA.  Every gradient vector carries a per-lane scale exponent (field_h3.h).
-#if defined(NEFES_TU_PART) && NEFES_TU_PART >= 2 && NEFES_TU_PART % 2 == 0
-#define NEFES_SLAB_KIB 16      // even parts from 2 on: the Wd = 128 instances (layout.h NEFES_H3_BWD_SLAB_KIB_128)
+#include "field_h3_instances.h"   // the instance table; NEFES_TU_W128 / NEFES_TU_BWD_WIDE: which of its rows this object holds
+#ifdef NEFES_TU_W128
+#define NEFES_SLAB_KIB 16      // the Wd = 128 instances (layout.h NEFES_H3_BWD_SLAB_KIB_128)
 #define NEFES_ASM_READS_ACC    // built with -amdgpu-mfma-vgpr-form: the functors' asm statements read the MFMAs' own VGPRs (field_common.h)
 #define NEFES_ACC_VGPR_FORM
 #define NEFES_FENCE_TILES
 #else
 #define NEFES_SLAB_KIB 32
-// The Wd = 256 inference objects (parts 0, 1) run their 8-/10-tile products on field_h3.h's gap-by-gap schedule (asm MFMAs on AGPR
+// The Wd = 256 inference objects run their 8-/10-tile products on field_h3.h's gap-by-gap schedule (asm MFMAs on AGPR
 // tiles, source tiles read out of their AGPRs inside the gaps), like the forward.  That needs the accumulator file to hold EXACTLY
 // the 2 x NTW ping-pong tiles: with a seventeenth tile alive hipcc relocates whole tiles with v_accvgpr_mov in the middle of the asm
 // runs -- behind an MFMA that has not written them yet.  So the three embedding-gradient tiles are consumed
 // where they are produced (below), layer 5's two extra output tiles live in VGPRs for the length of that run, and
 // tests/test_pack_stream.py disassembles the library and fails if a v_accvgpr_mov shows up in these kernels.
-#if !defined(NEFES_TU_PART) || NEFES_TU_PART == 0 || NEFES_TU_PART == 1 || NEFES_TU_PART == 5 || NEFES_TU_PART == 9 || NEFES_TU_PART == 11 || \
-    NEFES_TU_PART == 13
+#ifdef NEFES_TU_BWD_WIDE
 #define H3B_WIDE
 #define H3_ACC_READ_ASM        // source tiles are read out of their AGPRs inside the MFMA gaps (field_h3.h acc_read)
 #define NEFES_ASM_READS_ACC    // ... by asm statements: compiler-placed runs end with field_common.h mfma_results_fence_tiles
@@ -35,7 +35,6 @@
 #include "field_h3.h"
 #include "hashgrid.h"
 #include "../../include/nefes_hip.h"
-#define NEFES_XYZ_HASHGRID_FUSED 2   /* kernel-internal ENC value (field_fwd_h3.hip): the 32-feature hash-grid encoding evaluated by the kernel */
 #ifndef H3B_WIDE_LAYERS
 #define H3B_WIDE_LAYERS 0x1ff   /* bit L: layer L's transposed product on the gap-by-gap schedule; bit 0: xyz_encoding_final's (debugging) */
 #endif
@@ -124,8 +123,8 @@ __device__ __forceinline__ T ld_stream(const T* p) {
 // 3 .. 3 + W/2, which joins the 3-row colour head's transposed product in front of dir_encoding^T.
 // FOLD (NefesNetDesc.fold_final): the stream carries the packer's folded head matrices and no xyz_encoding_final^T segment -- the
 // transposed head products deliver d h8 (before layer 8's mask) themselves, static_sigma^T's k-step joins them, layer 8 follows.
-// The folded instances carry the flag in their head-class parameter (KRF = KR16 | NEFES_H3B_FOLD: the kernel keeps its template signature).
-#define NEFES_H3B_FOLD 16
+// The folded instances carry the flag in their head-class parameter (KRF = KR16 | NEFES_H3B_FOLD, field_h3_instances.h: the kernel keeps
+// its template signature).
 template <int W, int KRF, int ENC, bool HAS_T = true, bool TRAIN = false, bool FH = false>
 __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kernel(FieldBwdH3Args a) {
     constexpr bool FOLD = (KRF & NEFES_H3B_FOLD) != 0;
@@ -142,7 +141,7 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
     // v_accvgpr_mov one wait state behind the asm MFMA that writes the tile, where hipcc would put twelve behind an MFMA of its own
     // (tools/hazard_lint.py rule B1; tests/test_pack_stream.py finds the move itself; round 3 saw wrong gradients from such a move).  With compiler-placed MFMAs a moved tile is
     // the compiler's to pad.  Costs configs[3] ~4 ms of 590 per frame.
-    // (KR16 = 9 with the hash grid exists in NEFES_H3_HG_CLASS1 builds only, on the schedule: part 13's note)
+    // (KR16 = 9 with the hash grid exists in NEFES_H3_HG_CLASS1 builds only, on the schedule: field_h3_instances.h, the note at the <256, 9, EXTERNAL32> row)
     constexpr int WIDE_LAYERS = (ENC == NEFES_XYZ_HASHGRID_FUSED && KR16 == 2) ? 0 : H3B_WIDE_LAYERS;
     static_assert(KR16 == 2 || KR16 == 9, "head classes of layout.h (nefes_head_kr16 / nefes_head_ntr)");
     const int C3 = 3 + a.C;                                         // static rgb/feature head^T: 3+C upstream channels as fp16 k-steps
@@ -501,7 +500,7 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
         float ge[ENC != NEFES_XYZ_FREQ10 ? NEFES_X_STEPS : 1];
         {
             const float inv = pow2i(-es_e);
-            if constexpr (ENC != NEFES_XYZ_FREQ10) {        // kept in registers until layer 1's share exists (see part 1's note below)
+            if constexpr (ENC != NEFES_XYZ_FREQ10) {        // kept in registers until layer 1's share exists (see the note at the HASHGRID_FUSED row of field_h3_instances.h)
 #pragma unroll
                 for (int s_ = 0; s_ < NEFES_X_STEPS; ++s_) ge[s_] = XP[0][s_] * inv;
             } else {
@@ -601,115 +600,132 @@ static int launch_bwd_h3(const FieldBwdH3Args& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// Instances spread over thirteen objects built from this one source (Makefile: -DNEFES_TU_PART=0..9, 11, 13, 15; even parts from 2 on are the
-// Wd = 128 objects; parts 9 / 11 = the folded Wd = 256 instances of head class 0 / 1; parts 13 / 15 = the external-encoding (hash-grid)
-// instances of Wd = 256 / head class 1 and their TRAIN instances): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instance, part 2 = Wd = 128 / class 1,
-// parts 3 / 4 = their TRAIN instances, parts 5 / 6 = Wd = 256 / class 1 and Wd = 128 / class 0, parts 7 / 8 = their TRAIN instances.
-#ifndef NEFES_TU_PART
-#define NEFES_TU_PART 0
+// The instances are the rows of NEFES_H3_BWD_INSTANCES (field_h3_instances.h).  This object instantiates the rows of its own part
+// and defines their launch function; the object of the table's first part also holds the selector and the entry points.
+#ifdef NEFES_TU_W128
+constexpr bool kTuW128 = true, kTuWide = false;
+#elif defined(NEFES_TU_BWD_WIDE)
+constexpr bool kTuW128 = false, kTuWide = true;
+#else
+constexpr bool kTuW128 = false, kTuWide = false;
 #endif
-enum { BWD_H3_EXT = 0, BWD_H3_FULL, BWD_H3_TRAIN_STATIC, BWD_H3_TRAIN_FULL, BWD_H3_STATIC, BWD_H3_HG, BWD_H3_FH, BWD_H3_TRAIN_EXT_STATIC,
-       BWD_H3_TRAIN_EXT_FULL };
-int nefes_bwd_h3_launch_part1(int which, const FieldBwdH3Args& a, hipStream_t st);
-int nefes_bwd_h3_launch_part2(int which, const FieldBwdH3Args& a, hipStream_t st);
-int nefes_bwd_h3_launch_part3(int which, const FieldBwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 256, class 0
-int nefes_bwd_h3_launch_part4(int which, const FieldBwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 128, class 1
-int nefes_bwd_h3_launch_part5(int which, const FieldBwdH3Args& a, hipStream_t st);   // Wd = 256, class 1
-int nefes_bwd_h3_launch_part6(int which, const FieldBwdH3Args& a, hipStream_t st);   // Wd = 128, class 0
-int nefes_bwd_h3_launch_part7(int which, const FieldBwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 256, class 1
-int nefes_bwd_h3_launch_part8(int which, const FieldBwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 128, class 0
-int nefes_bwd_h3_launch_part9(int which, const FieldBwdH3Args& a, hipStream_t st);   // folded (FOLD) instance, Wd = 256, class 0
-int nefes_bwd_h3_launch_part11(int which, const FieldBwdH3Args& a, hipStream_t st);  // folded (FOLD) instance, Wd = 256, class 1
-int nefes_bwd_h3_launch_part13(int which, const FieldBwdH3Args& a, hipStream_t st);  // external encoding / hash grid, Wd = 256, class 1
-int nefes_bwd_h3_launch_part15(int which, const FieldBwdH3Args& a, hipStream_t st);  // ... their TRAIN instances
+#define X(part, W, KR16, ENC, HAS_T, TRAIN, FH)                                                                                     \
+    static_assert(part != NEFES_TU_PART || (W == 128) == kTuW128, "a Wd = 128 row belongs to an object built for Wd = 128, and no other row does"); \
+    static_assert(part != NEFES_TU_PART || kTuW128 || (TRAIN == 0) == kTuWide, "Wd = 256: the gap-by-gap schedule for the inference rows, not for TRAIN rows");
+NEFES_H3_BWD_INSTANCES(X)
+#undef X
 
-#if NEFES_TU_PART == 1
-int nefes_bwd_h3_launch_part1(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_EXT) return launch_bwd_h3<256, 2, NEFES_XYZ_EXTERNAL32>(a, st);
-    if (which == BWD_H3_STATIC) return launch_bwd_h3<256, 2, NEFES_XYZ_FREQ10, false>(a, st);     // static head alone, inference (round 5)
-    // The hash grid's backward in the epilogue (round 5), on the gap-by-gap schedule like its neighbours.  Its first form parked the
-    // skip connection's share of d encoding in LDS across layers 4..1 and hipcc then split an accumulator tile's live range inside
-    // an asm-scheduled run (a v_accvgpr_mov behind an MFMA that has not written the tile yet: tests/test_pack_stream.py caught it,
-    // no numerical test did); with the share in sixteen registers, as the external-encoding instance keeps it, the tiles stay put.
-    if (which == BWD_H3_HG) return launch_bwd_h3<256, 2, NEFES_XYZ_HASHGRID_FUSED>(a, st);
+template <int PART>
+static int h3_bwd_launch_rows(const NefesH3BwdKey& k, const FieldBwdH3Args& a, hipStream_t st) {
+#define X(part, W, KR16, ENC, HAS_T, TRAIN, FH)                                                                        \
+    if constexpr (part == PART) {                                                                                      \
+        if (k == NEFES_H3_BWD_KEY(W, KR16, ENC, HAS_T, TRAIN, FH))                                                     \
+            return launch_bwd_h3<W, KR16, NEFES_XYZ_##ENC, HAS_T != 0, TRAIN != 0, FH != 0>(a, st);                    \
+    }
+    NEFES_H3_BWD_INSTANCES(X)
+#undef X
     return NEFES_E_UNSUPPORTED;
 }
-#elif NEFES_TU_PART == 2      // built with -mllvm -amdgpu-mfma-vgpr-form: see field_fwd_h3.hip
-int nefes_bwd_h3_launch_part2(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_FULL) return launch_bwd_h3<128, 9, NEFES_XYZ_FREQ10>(a, st);
-    if (which == BWD_H3_STATIC) return launch_bwd_h3<128, 9, NEFES_XYZ_FREQ10, false>(a, st);
-    return NEFES_E_UNSUPPORTED;
+#define X(part, W, KR16, ENC, HAS_T, TRAIN, FH) int NEFES_H3_BWD_PART_FN(part)(const NefesH3BwdKey&, const FieldBwdH3Args&, hipStream_t);
+NEFES_H3_BWD_INSTANCES(X)
+#undef X
+int NEFES_H3_BWD_PART_FN(NEFES_TU_PART)(const NefesH3BwdKey& k, const FieldBwdH3Args& a, hipStream_t st) {
+    return h3_bwd_launch_rows<NEFES_TU_PART>(k, a, st);
 }
-#elif NEFES_TU_PART == 3
-int nefes_bwd_h3_launch_part3(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_TRAIN_STATIC) return launch_bwd_h3<256, 2, NEFES_XYZ_FREQ10, false, true>(a, st);
-    if (which == BWD_H3_TRAIN_FULL) return launch_bwd_h3<256, 2, NEFES_XYZ_FREQ10, true, true>(a, st);
-    if (which == BWD_H3_TRAIN_EXT_STATIC) return launch_bwd_h3<256, 2, NEFES_XYZ_EXTERNAL32, false, true>(a, st);   // trainable hash grid
-    if (which == BWD_H3_TRAIN_EXT_FULL) return launch_bwd_h3<256, 2, NEFES_XYZ_EXTERNAL32, true, true>(a, st);
-    return NEFES_E_UNSUPPORTED;
+
+#if NEFES_TU_PART == 0
+struct H3BwdRow {
+    NefesH3BwdKey key;
+    const char* name;
+    int (*launch)(const NefesH3BwdKey&, const FieldBwdH3Args&, hipStream_t);
+};
+static const H3BwdRow h3_bwd_rows[] = {
+#define X(part, W, KR16, ENC, HAS_T, TRAIN, FH) \
+    {NEFES_H3_BWD_KEY(W, KR16, ENC, HAS_T, TRAIN, FH), "bwd p" #part " <" #W "," #KR16 "," #ENC "," #HAS_T "," #TRAIN "," #FH ">", NEFES_H3_BWD_PART_FN(part)},
+    NEFES_H3_BWD_INSTANCES(X)
+#undef X
+};
+
+// Which row serves `desc` for a request, as field_fwd_h3.hip's h3_fwd_select: `mode` counts for the train entry points only (the
+// others have none: NEFES_H3_REQ_STATIC_BWD is the backward of a NEFES_FIELD_STATIC forward, every other request of a full one).
+struct H3BwdSel {
+    int rc;
+    const H3BwdRow* row;
+};
+static H3BwdSel h3_bwd_select(const NefesNetDesc* desc, int mode, unsigned req) {
+    const bool train = req & NEFES_H3_REQ_TRAIN, fh = req & NEFES_H3_REQ_FH, fused_grid = req & NEFES_H3_REQ_HASHGRID;
+    const bool ext = desc->xyz_encoding == NEFES_XYZ_EXTERNAL32, fold = desc->fold_final != 0;
+    const int cls = nefes_head_class(desc->feat_dim), w = desc->width;
+    // (the _hashgrid entry points take no network without a grid in front, the _fh ones have no argument for a supplied encoding)
+    if (fused_grid ? !ext : (fh && ext)) return {NEFES_E_BADARG, nullptr};
+    if (train && mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return {NEFES_E_BADARG, nullptr};
+    const bool full = train ? mode == NEFES_FIELD_FULL : !(req & NEFES_H3_REQ_STATIC_BWD);
+    bool ok = !(full && !desc->has_transient) && cls >= 0;
+    if (train)             // as the forward: a supplied encoding (the _ext entry points) at width 256; no folded row reads these streams
+        ok = ok && !fold && ((req & NEFES_H3_REQ_EXT) ? (w == 256 && ext) : ((w == 256 || w == 128) && desc->xyz_encoding == NEFES_XYZ_FREQ10));
+    else if (!full)
+        ok = ok && !fold && (w == 256 || w == 128) && desc->xyz_encoding == NEFES_XYZ_FREQ10;
+    else                   // a folded pack: folded rows exist at width 256 with the frequency embedding and the network's own head;
+                           // factored head: see nefes_field_fwd_h3_fh
+        ok = ok && !(fold && (w != 256 || ext || fh)) && !(fh && (desc->feat_dim != 0 || w != 128 || ext));
+    if (!ok) return {NEFES_E_UNSUPPORTED, nullptr};
+    const NefesH3BwdKey key = {w, (cls == 0 ? 2 : 9) | (fold ? NEFES_H3B_FOLD : 0), fused_grid ? NEFES_XYZ_HASHGRID_FUSED : desc->xyz_encoding,
+                               full, train, fh};
+    for (const H3BwdRow& r : h3_bwd_rows)
+        if (r.key == key) return {0, &r};
+    return {NEFES_E_UNSUPPORTED, nullptr};      // (e.g. a supplied encoding at width 128, the fused hash grid with head class 1)
 }
-#elif NEFES_TU_PART == 4      // (built like part 2)
-int nefes_bwd_h3_launch_part4(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_TRAIN_STATIC) return launch_bwd_h3<128, 9, NEFES_XYZ_FREQ10, false, true>(a, st);
-    if (which == BWD_H3_TRAIN_FULL) return launch_bwd_h3<128, 9, NEFES_XYZ_FREQ10, true, true>(a, st);
-    return NEFES_E_UNSUPPORTED;
+
+static int h3_bwd_stream(const NefesNetDesc* desc, const NefesH3BwdKey& k, NefesStreamInfo* si) {
+    NefesBlobInfo info;
+    int rc = nefes_blob_info(desc, &info);
+    if (rc) return rc;
+    *si = info.stream[k.has_t ? NEFES_STREAM_BWD_FULL_H3 : NEFES_STREAM_BWD_STATIC_H3];
+    const int n_seg = (k.kr16 & NEFES_H3B_FOLD) ? NEFES_H3BF_N : (k.has_t ? NEFES_H3B_N : NEFES_H3B_N_STATIC);
+    return si->n_slabs == 0 || si->scale_count < 2 * (uint32_t)n_seg ? NEFES_E_UNSUPPORTED : 0;
 }
-#elif NEFES_TU_PART == 5      // (gap-by-gap schedule, like part 0)
-int nefes_bwd_h3_launch_part5(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_FULL) return launch_bwd_h3<256, 9, NEFES_XYZ_FREQ10>(a, st);
-    if (which == BWD_H3_STATIC) return launch_bwd_h3<256, 9, NEFES_XYZ_FREQ10, false>(a, st);
-    return NEFES_E_UNSUPPORTED;
+
+// Everything of the kernel's arguments that follows from the row and the shape; `a` arrives with the entry point's pointers set
+// and the rest zero.  (M is not looked at here: DESIGN.md 4.1.1.)
+static int h3_bwd_args(const NefesNetDesc* desc, const void* packed, const NefesH3BwdKey& k, int N, int S,
+                       const NefesHashGridDesc* grid, FieldBwdH3Args& a) {
+    NefesStreamInfo si;
+    int rc = h3_bwd_stream(desc, k, &si);
+    if (rc) return rc;
+    a.stream = (const char*)packed + si.slab_off;
+    a.tab = (const int*)((const char*)packed + si.bias_off) + si.scale_off;
+    a.n_slabs = si.n_slabs;
+    if (k.enc == NEFES_XYZ_HASHGRID_FUSED) {
+        rc = hg_geometry(grid, &a.hg, nullptr);
+        if (rc) return rc;
+        if (a.hg.n_levels != 16) return NEFES_E_UNSUPPORTED;
+    }
+    a.gout = k.fh ? k.w / 2 : 0;                                  // factored head: see nefes_field_fwd_h3_fh
+    a.N = N; a.S = S; a.C = k.fh ? a.gout + 1 : desc->feat_dim;
+    a.R = 3 + a.C + (k.has_t ? 6 : 1);
+    a.M = (long long)N * S;
+    a.n_tiles = (int)((a.M + 127) / 128);
+    a.rows = k.train ? nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END) : 0;
+    return 0;
 }
-#elif NEFES_TU_PART == 6      // (built like part 2)
-int nefes_bwd_h3_launch_part6(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_FULL) return launch_bwd_h3<128, 2, NEFES_XYZ_FREQ10>(a, st);
-    if (which == BWD_H3_STATIC) return launch_bwd_h3<128, 2, NEFES_XYZ_FREQ10, false>(a, st);
-    if (which == BWD_H3_FH) return launch_bwd_h3<128, 2, NEFES_XYZ_FREQ10, true, false, true>(a, st);      // factored head (round 5)
-    return NEFES_E_UNSUPPORTED;
+
+// select -> args -> launch, behind the entry point's own pointer checks
+static int h3_bwd_run(const NefesNetDesc* desc, const void* packed, int mode, unsigned req, int N, int S,
+                      const NefesHashGridDesc* grid, FieldBwdH3Args& a, void* stream) {
+    const H3BwdSel s = h3_bwd_select(desc, mode, req);
+    if (s.rc) return s.rc;
+    const int rc = h3_bwd_args(desc, packed, s.row->key, N, S, grid, a);
+    return rc ? rc : s.row->launch(s.row->key, a, (hipStream_t)stream);
 }
-#elif NEFES_TU_PART == 7
-int nefes_bwd_h3_launch_part7(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_TRAIN_STATIC) return launch_bwd_h3<256, 9, NEFES_XYZ_FREQ10, false, true>(a, st);
-    if (which == BWD_H3_TRAIN_FULL) return launch_bwd_h3<256, 9, NEFES_XYZ_FREQ10, true, true>(a, st);
-    return NEFES_E_UNSUPPORTED;
+
+// the backward half of nefes_field_h3_instance (field_fwd_h3.hip)
+int nefes_h3_bwd_instance(const NefesNetDesc* desc, int mode, unsigned req, const char** name) {
+    const H3BwdSel s = h3_bwd_select(desc, mode, req);
+    NefesStreamInfo si;
+    const int rc = s.rc ? s.rc : h3_bwd_stream(desc, s.row->key, &si);
+    if (!rc) *name = s.row->name;
+    return rc;
 }
-#elif NEFES_TU_PART == 8      // (built like part 2)
-int nefes_bwd_h3_launch_part8(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_TRAIN_STATIC) return launch_bwd_h3<128, 2, NEFES_XYZ_FREQ10, false, true>(a, st);
-    if (which == BWD_H3_TRAIN_FULL) return launch_bwd_h3<128, 2, NEFES_XYZ_FREQ10, true, true>(a, st);
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 9      // (gap-by-gap schedule, like part 0)
-int nefes_bwd_h3_launch_part9(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_FULL) return launch_bwd_h3<256, 2 | NEFES_H3B_FOLD, NEFES_XYZ_FREQ10>(a, st);
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 11     // (gap-by-gap schedule, like part 0)
-int nefes_bwd_h3_launch_part11(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_FULL) return launch_bwd_h3<256, 9 | NEFES_H3B_FOLD, NEFES_XYZ_FREQ10>(a, st);
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 13     // (gap-by-gap schedule, like part 0)
-// Head class 1 on a SUPPLIED encoding.  The instance with the hash grid in its epilogue, <256, 9, NEFES_XYZ_HASHGRID_FUSED>, is not
-// built: on the gap-by-gap schedule hipcc relocates accumulator tiles inside the asm-scheduled runs (v_accvgpr_mov one to six wait
-// states behind the asm MFMA that writes the tile: tools/hazard_lint.py rule B1 -- 512 registers, no scratch), the failure the class-0
-// instance avoids by leaving the schedule, and the seventy-two upstream values of this class leave it less room, not more.  Such
-// networks take nefes_hashgrid_fwd / _bwd_x around the EXT instance (ops.hashgrid_fused_ok).
-// make EXTRA_H3=-DNEFES_H3_HG_CLASS1 builds it (experiments: the linter and tests/test_pack_stream.py are red on that library).
-int nefes_bwd_h3_launch_part13(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_EXT) return launch_bwd_h3<256, 9, NEFES_XYZ_EXTERNAL32>(a, st);
-#ifdef NEFES_H3_HG_CLASS1
-    if (which == BWD_H3_HG) return launch_bwd_h3<256, 9, NEFES_XYZ_HASHGRID_FUSED>(a, st);
-#endif
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 15
-int nefes_bwd_h3_launch_part15(int which, const FieldBwdH3Args& a, hipStream_t st) {
-    if (which == BWD_H3_TRAIN_EXT_STATIC) return launch_bwd_h3<256, 9, NEFES_XYZ_EXTERNAL32, false, true>(a, st);
-    if (which == BWD_H3_TRAIN_EXT_FULL) return launch_bwd_h3<256, 9, NEFES_XYZ_EXTERNAL32, true, true>(a, st);
-    return NEFES_E_UNSUPPORTED;
-}
-#else   // part 0
 
 // The fused dX chain of the train-mode backward on the fp16 pipe: as nefes_field_bwd_train (field_bwd.hip), same `dacts` rows.
 extern "C" int nefes_field_bwd_train_h3(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
@@ -719,32 +735,10 @@ extern "C" int nefes_field_bwd_train_h3(const NefesNetDesc* desc, const void* pa
     if (!desc || !packed || !viewdirs || !raw_t || !g_raw_t || !masks || !dacts || !g_pts || !g_viewdirs_s || N <= 0 || S <= 0)
         return NEFES_E_BADARG;
     if (!(rays_o && rays_d && z)) return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
-    const bool full = mode == NEFES_FIELD_FULL;
-    if (full && !desc->has_transient) return NEFES_E_UNSUPPORTED;
-    const int cls = nefes_head_class(desc->feat_dim);
-    if ((desc->width != 256 && desc->width != 128) || cls < 0 || desc->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;
-    if (desc->fold_final) return NEFES_E_UNSUPPORTED;               // (no folded instance reads this stream)
-    NefesBlobInfo info;
-    int rc = nefes_blob_info(desc, &info);
-    if (rc) return rc;
-    const NefesStreamInfo& si = info.stream[full ? NEFES_STREAM_BWD_FULL_H3 : NEFES_STREAM_BWD_STATIC_H3];
-    if (si.n_slabs == 0 || si.scale_count < 2 * (uint32_t)(full ? NEFES_H3B_N : NEFES_H3B_N_STATIC)) return NEFES_E_UNSUPPORTED;
-    FieldBwdH3Args a;
-    a.stream = (const char*)packed + si.slab_off;
-    a.tab = (const int*)((const char*)packed + si.bias_off) + si.scale_off;
-    a.n_slabs = si.n_slabs;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = nullptr; a.viewdirs = viewdirs;
-    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.g_pts = g_pts; a.g_enc = nullptr; a.g_vs = g_viewdirs_s;
-    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = 3 + a.C + (full ? 6 : 1);
-    a.M = (long long)N * S;
-    a.n_tiles = (int)((a.M + 127) / 128);
-    a.dacts = dacts; a.gout = 0; a.hg_table = nullptr; a.g_gmap = nullptr;
-    a.rows = nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END);
-    const int which = full ? BWD_H3_TRAIN_FULL : BWD_H3_TRAIN_STATIC;
-    hipStream_t st = (hipStream_t)stream;
-    if (desc->width == 256) return cls == 0 ? nefes_bwd_h3_launch_part3(which, a, st) : nefes_bwd_h3_launch_part7(which, a, st);
-    return cls == 1 ? nefes_bwd_h3_launch_part4(which, a, st) : nefes_bwd_h3_launch_part8(which, a, st);
+    FieldBwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.viewdirs = viewdirs;
+    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.dacts = dacts; a.g_pts = g_pts; a.g_vs = g_viewdirs_s;
+    return h3_bwd_run(desc, packed, mode, NEFES_H3_REQ_TRAIN, N, S, nullptr, a, stream);
 }
 
 // The same for a NEFES_XYZ_EXTERNAL32 network (nefes_field_fwd_train_h3_ext): `dacts` as above, g_xyz_enc [N*S, 32] = d loss / d its
@@ -754,33 +748,12 @@ extern "C" int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void
                                             float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
     if (!desc || !packed || !viewdirs || !raw_t || !g_raw_t || !masks || !dacts || !g_xyz_enc || !g_viewdirs_s || N <= 0 || S <= 0)
         return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
-    const bool full = mode == NEFES_FIELD_FULL;
-    if (full && !desc->has_transient) return NEFES_E_UNSUPPORTED;
-    const int cls = nefes_head_class(desc->feat_dim);
-    if (desc->width != 256 || cls < 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
-    if (desc->fold_final) return NEFES_E_UNSUPPORTED;
-    NefesBlobInfo info;
-    int rc = nefes_blob_info(desc, &info);
-    if (rc) return rc;
-    const NefesStreamInfo& si = info.stream[full ? NEFES_STREAM_BWD_FULL_H3 : NEFES_STREAM_BWD_STATIC_H3];
-    if (si.n_slabs == 0 || si.scale_count < 2 * (uint32_t)(full ? NEFES_H3B_N : NEFES_H3B_N_STATIC)) return NEFES_E_UNSUPPORTED;
-    FieldBwdH3Args a;
-    a.stream = (const char*)packed + si.slab_off;
-    a.tab = (const int*)((const char*)packed + si.bias_off) + si.scale_off;
-    a.n_slabs = si.n_slabs;
-    a.rays_o = nullptr; a.rays_d = nullptr; a.z = nullptr; a.pts = nullptr; a.viewdirs = viewdirs;
-    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.g_pts = nullptr; a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
-    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = 3 + a.C + (full ? 6 : 1);
-    a.M = (long long)N * S;
-    a.n_tiles = (int)((a.M + 127) / 128);
-    a.dacts = dacts; a.gout = 0; a.hg_table = nullptr; a.g_gmap = nullptr;
-    a.rows = nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END);
-    const int which = full ? BWD_H3_TRAIN_EXT_FULL : BWD_H3_TRAIN_EXT_STATIC;
-    return cls == 0 ? nefes_bwd_h3_launch_part3(which, a, (hipStream_t)stream) : nefes_bwd_h3_launch_part15(which, a, (hipStream_t)stream);
+    FieldBwdH3Args a = {};
+    a.viewdirs = viewdirs; a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.dacts = dacts; a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
+    return h3_bwd_run(desc, packed, mode, NEFES_H3_REQ_TRAIN | NEFES_H3_REQ_EXT, N, S, nullptr, a, stream);
 }
 
-// nefes_field_bwd_static on the fp16 pipe: backward-to-inputs of a NEFES_FIELD_STATIC forward with frozen weights (round 5: every
+// nefes_field_bwd_static on the fp16 pipe: backward-to-inputs of a NEFES_FIELD_STATIC forward with frozen weights (every
 // compiled (width, head class) pair; the fp32-MFMA nefes_field_bwd_static serves the two canonical shapes only).
 extern "C" int nefes_field_bwd_static_h3(const NefesNetDesc* desc, const void* packed, int N, int S, const float* rays_o,
                                          const float* rays_d, const float* z, const float* pts, const float* viewdirs,
@@ -789,89 +762,32 @@ extern "C" int nefes_field_bwd_static_h3(const NefesNetDesc* desc, const void* p
     if (!desc || !packed || !viewdirs || !raw_t || !g_raw_t || !masks || !g_pts || !g_viewdirs_s || N <= 0 || S <= 0)
         return NEFES_E_BADARG;
     if (!pts && !(rays_o && rays_d && z)) return NEFES_E_BADARG;
-    const int cls = nefes_head_class(desc->feat_dim);
-    if ((desc->width != 256 && desc->width != 128) || cls < 0 || desc->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;
-    if (desc->fold_final) return NEFES_E_UNSUPPORTED;               // (no folded instance reads this stream)
-    NefesBlobInfo info;
-    int rc = nefes_blob_info(desc, &info);
-    if (rc) return rc;
-    const NefesStreamInfo& si = info.stream[NEFES_STREAM_BWD_STATIC_H3];
-    if (si.n_slabs == 0 || si.scale_count < 2 * (uint32_t)NEFES_H3B_N_STATIC) return NEFES_E_UNSUPPORTED;
-    FieldBwdH3Args a;
-    a.stream = (const char*)packed + si.slab_off;
-    a.tab = (const int*)((const char*)packed + si.bias_off) + si.scale_off;
-    a.n_slabs = si.n_slabs;
+    FieldBwdH3Args a = {};
     a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.viewdirs = viewdirs;
-    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.g_pts = g_pts; a.g_enc = nullptr; a.g_vs = g_viewdirs_s;
-    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = 3 + a.C + 1;
-    a.M = (long long)N * S;
-    a.n_tiles = (int)((a.M + 127) / 128);
-    a.dacts = nullptr; a.rows = 0; a.gout = 0; a.hg_table = nullptr; a.g_gmap = nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (desc->width == 256) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_STATIC, a, st) : nefes_bwd_h3_launch_part5(BWD_H3_STATIC, a, st);
-    return cls == 1 ? nefes_bwd_h3_launch_part2(BWD_H3_STATIC, a, st) : nefes_bwd_h3_launch_part6(BWD_H3_STATIC, a, st);
+    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.g_pts = g_pts; a.g_vs = g_viewdirs_s;
+    return h3_bwd_run(desc, packed, NEFES_FIELD_STATIC, NEFES_H3_REQ_STATIC_BWD, N, S, nullptr, a, stream);
 }
 
-static int field_bwd_h3_impl(const NefesNetDesc* desc, const void* packed, int N, int S, const float* rays_o,
-                                  const float* rays_d, const float* z, const float* pts, const float* viewdirs,
-                                  const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* g_pts,
-                                  float* g_xyz_enc, float* g_viewdirs_s, void* stream, const NefesHashGridDesc* grid, const float* table,
-                                  bool fh = false, const float* g_gmap = nullptr) {
-    if (!desc || !packed || !viewdirs || !raw_t || !g_raw_t || !masks || !g_viewdirs_s || N <= 0 || S <= 0)
+// The backward of a full forward: `a` carries the entry point's pointers, `req` says which one is asking.
+static int field_bwd_h3_impl(const NefesNetDesc* desc, const void* packed, unsigned req, int N, int S, const NefesHashGridDesc* grid,
+                             FieldBwdH3Args& a, void* stream) {
+    if (!desc || !packed || !a.viewdirs || !a.raw_t || !a.g_raw_t || !a.masks || !a.g_vs || N <= 0 || S <= 0)
         return NEFES_E_BADARG;
     const bool ext = desc->xyz_encoding == NEFES_XYZ_EXTERNAL32;
-    const bool fused_grid = ext && table != nullptr;            // d pts through the hash grid inside the kernel (hashgrid.h)
-    if (fused_grid ? !(g_pts && grid && rays_o && rays_d && z) : (ext ? !g_xyz_enc : (!g_pts || (!pts && !(rays_o && rays_d && z))))) return NEFES_E_BADARG;
-    if (!desc->has_transient) return NEFES_E_UNSUPPORTED;
-    // a folded pack (NefesNetDesc.fold_final): folded instances exist at width 256 with the frequency embedding and the network's own head
-    const bool fold = desc->fold_final != 0;
-    if (fold && (desc->width != 256 || ext || fh)) return NEFES_E_UNSUPPORTED;
-    NefesBlobInfo info;
-    int rc = nefes_blob_info(desc, &info);
-    if (rc) return rc;
-    const NefesStreamInfo& si = info.stream[NEFES_STREAM_BWD_FULL_H3];
-    if (si.n_slabs == 0 || si.scale_count < 2 * (uint32_t)(fold ? NEFES_H3BF_N : NEFES_H3B_N)) return NEFES_E_UNSUPPORTED;
-    FieldBwdH3Args a;
-    a.stream = (const char*)packed + si.slab_off;
-    a.tab = (const int*)((const char*)packed + si.bias_off) + si.scale_off;
-    a.n_slabs = si.n_slabs;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.viewdirs = viewdirs;
-    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.g_pts = g_pts; a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
-    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = 3 + a.C + 6;
-    a.gout = 0; a.g_gmap = g_gmap;
-    if (fh) {                                                     // factored head: see nefes_field_fwd_h3_fh
-        if (desc->feat_dim != 0 || desc->width != 128 || ext) return NEFES_E_UNSUPPORTED;
-        a.gout = desc->width / 2;
-        a.C = a.gout + 1;
-        a.R = 3 + a.C + 6;
-    }
-    a.M = (long long)N * S;
-    a.n_tiles = (int)((a.M + 127) / 128);
-    a.dacts = nullptr; a.rows = 0;
-    a.hg_table = (const float2*)table;
-    if (fused_grid) {
-        rc = hg_geometry(grid, &a.hg, nullptr);
-        if (rc) return rc;
-        if (a.hg.n_levels != 16) return NEFES_E_UNSUPPORTED;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int cls = nefes_head_class(desc->feat_dim);          // compiled set: as nefes_field_fwd_h3
-    if (cls < 0) return NEFES_E_UNSUPPORTED;
-    if (fh) return nefes_bwd_h3_launch_part6(BWD_H3_FH, a, st);
-    if (desc->width == 256 && fused_grid) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_HG, a, st) : nefes_bwd_h3_launch_part13(BWD_H3_HG, a, st);
-    if (desc->width == 256 && ext) return cls == 0 ? nefes_bwd_h3_launch_part1(BWD_H3_EXT, a, st) : nefes_bwd_h3_launch_part13(BWD_H3_EXT, a, st);
-    if (desc->width == 256 && fold) return cls == 0 ? nefes_bwd_h3_launch_part9(BWD_H3_FULL, a, st) : nefes_bwd_h3_launch_part11(BWD_H3_FULL, a, st);
-    if (desc->width == 256) return cls == 0 ? launch_bwd_h3<256, 2, NEFES_XYZ_FREQ10>(a, st) : nefes_bwd_h3_launch_part5(BWD_H3_FULL, a, st);
-    if (desc->width == 128 && !ext) return cls == 1 ? nefes_bwd_h3_launch_part2(BWD_H3_FULL, a, st) : nefes_bwd_h3_launch_part6(BWD_H3_FULL, a, st);
-    return NEFES_E_UNSUPPORTED;
+    const bool fused_grid = ext && a.hg_table != nullptr;       // d pts through the hash grid inside the kernel (hashgrid.h)
+    if (fused_grid ? !(a.g_pts && grid && a.rays_o && a.rays_d && a.z)
+                   : (ext ? !a.g_enc : (!a.g_pts || (!a.pts && !(a.rays_o && a.rays_d && a.z))))) return NEFES_E_BADARG;
+    return h3_bwd_run(desc, packed, NEFES_FIELD_FULL, req, N, S, grid, a, stream);
 }
 
 extern "C" int nefes_field_bwd_h3(const NefesNetDesc* desc, const void* packed, int N, int S, const float* rays_o,
                                   const float* rays_d, const float* z, const float* pts, const float* viewdirs,
                                   const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* g_pts,
                                   float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
-    return field_bwd_h3_impl(desc, packed, N, S, rays_o, rays_d, z, pts, viewdirs, raw_t, g_raw_t, masks, g_pts, g_xyz_enc, g_viewdirs_s, stream,
-                             nullptr, nullptr);
+    FieldBwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.viewdirs = viewdirs;
+    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.g_pts = g_pts; a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
+    return field_bwd_h3_impl(desc, packed, 0, N, S, nullptr, a, stream);
 }
 
 // nefes_field_bwd_h3 for a nefes_field_fwd_h3_fh forward: g_raw_t [N][3 + (W/2 + 1) + 6][S] carries d loss / d g in channels 3 .. 3 + W/2
@@ -880,8 +796,10 @@ extern "C" int nefes_field_bwd_h3_fh(const NefesNetDesc* desc, const void* packe
                                      const float* z, const float* viewdirs, const float* raw_t, const float* g_raw_t, const float* g_gmap,
                                      const uint32_t* masks, float* g_pts, float* g_viewdirs_s, void* stream) {
     if (!rays_o || !rays_d || !z) return NEFES_E_BADARG;
-    return field_bwd_h3_impl(desc, packed, N, S, rays_o, rays_d, z, nullptr, viewdirs, raw_t, g_raw_t, masks, g_pts, nullptr, g_viewdirs_s, stream,
-                             nullptr, nullptr, true, g_gmap);
+    FieldBwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.viewdirs = viewdirs;
+    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.g_gmap = g_gmap; a.masks = masks; a.g_pts = g_pts; a.g_vs = g_viewdirs_s;
+    return field_bwd_h3_impl(desc, packed, NEFES_H3_REQ_FH, N, S, nullptr, a, stream);
 }
 
 // nefes_field_bwd_h3 for a nefes_field_fwd_h3_hashgrid forward: g_pts [N*S, 3] = d loss / d (o + d z) through the MLP AND the hash
@@ -891,7 +809,9 @@ extern "C" int nefes_field_bwd_h3_hashgrid(const NefesNetDesc* desc, const void*
                                            const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
                                            float* g_pts, float* g_viewdirs_s, void* stream) {
     if (!desc || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32 || !grid || !table) return NEFES_E_BADARG;
-    return field_bwd_h3_impl(desc, packed, N, S, rays_o, rays_d, z, nullptr, viewdirs, raw_t, g_raw_t, masks, g_pts, nullptr, g_viewdirs_s, stream,
-                             grid, table);
+    FieldBwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.viewdirs = viewdirs;
+    a.raw_t = raw_t; a.g_raw_t = g_raw_t; a.masks = masks; a.g_pts = g_pts; a.g_vs = g_viewdirs_s; a.hg_table = (const float2*)table;
+    return field_bwd_h3_impl(desc, packed, NEFES_H3_REQ_HASHGRID, N, S, grid, a, stream);
 }
-#endif   // NEFES_TU_PART
+#endif   // NEFES_TU_PART == 0

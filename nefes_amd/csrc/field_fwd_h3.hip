@@ -8,12 +8,13 @@
 // in LDS between layer 1 and the skip at layer 5 instead of in registers: with one accumulator set in VGPRs (the compiler keeps
 // the set the vector ALU reads there) the kernel has no 32 registers to spare.
 // (layout.h is included below; the two sizes are repeated there as NEFES_H3_FWD_SLAB_KIB / _128 and checked against these)
-#if defined(NEFES_TU_PART) && NEFES_TU_PART >= 2 && NEFES_TU_PART % 2 == 0
-#define NEFES_TU_W128          // even parts from 2 on hold the Wd = 128 instances
+#include "field_h3_instances.h"   // the instance table; NEFES_TU_W128 for the objects that hold its Wd = 128 rows
+#ifdef NEFES_TU_W128
 #define NEFES_SLAB_KIB 16      // 2 x 16 KiB of ring, two workgroups per CU (see launch_h3)
 #else
 #define NEFES_SLAB_KIB 32
 #endif
+#include <stdio.h>
 #include <stdlib.h>
 // Accumulators read by asm statements: the Wd = 128 objects (-amdgpu-mfma-vgpr-form: the functors' asm reads the MFMAs' own VGPRs) and
 // the Wd = 256 objects (H3_ACC_READ_ASM below): compiler-placed runs end with field_common.h mfma_results_fence
@@ -33,7 +34,6 @@
 
 #include "field_x6.h"
 #include "hashgrid.h"
-#define NEFES_XYZ_HASHGRID_FUSED 2   /* kernel-internal ENC value: a NEFES_XYZ_EXTERNAL32 network whose 32 features the kernel gathers itself */
 #if !defined(NEFES_TU_W128) && !defined(H3_NO_ACC_READ_ASM)
 #define H3_ACC_READ_ASM        // Wd = 256 objects: source tiles are read out of their AGPRs inside the MFMA gaps (field_h3.h acc_read)
 #endif
@@ -95,9 +95,8 @@ __device__ __forceinline__ void train_save_h3(float* tile_base, uint32_t voff, i
 // FOLD (frozen networks, NefesNetDesc.fold_final): xyz_encoding_final is a Linear with no activation behind it, so the packer has
 // multiplied it into its two consumers (pack.cpp fold_head).  The stream has no FINAL segment; the trunk ends with layer 8 and the
 // stacked head product reads relu(h8) -- the operand static_sigma reads -- through the functor that also records layer 8's mask.
-// Mask words and raw_t are those of the unfolded kernel.  The folded full pass is a MODE value of its own, known to this file only
-// (the instance keeps the kernel's template signature).
-#define NEFES_FIELD_FULL_FOLD 3
+// Mask words and raw_t are those of the unfolded kernel.  The folded full pass is a MODE value of its own, NEFES_FIELD_FULL_FOLD
+// (field_h3_instances.h: the instance keeps the kernel's template signature).
 template <int MODEF, int ENC, int W = 256, int NTR = 1, bool TRAIN = false, bool FH = false>
 __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(FieldFwdH3Args a) {
     constexpr bool FOLD = MODEF == NEFES_FIELD_FULL_FOLD;
@@ -541,134 +540,158 @@ static int launch_h3(const FieldFwdH3Args& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-// Kernel instances spread over thirteen objects built from this one source (Makefile: -DNEFES_TU_PART=0..9, 11, 13, 15; even parts from 2 on
-// are the Wd = 128 objects; parts 9 / 11 = the folded Wd = 256 instances of head class 0 / 1; parts 13 / 15 = the external-encoding
-// (hash-grid) instances of Wd = 256 / head class 1 and their TRAIN instances): part 0 = entry points + Wd = 256 / head class 0, part 1 = hash-grid instances, part 2 = Wd = 128 / class 1,
-// parts 3 / 4 = their TRAIN instances, parts 5 / 6 = Wd = 256 / class 1 and Wd = 128 / class 0, parts 7 / 8 = their TRAIN instances.
-#ifndef NEFES_TU_PART
-#define NEFES_TU_PART 0
+// The instances are the rows of NEFES_H3_FWD_INSTANCES (field_h3_instances.h).  This object instantiates the rows of its own part
+// and defines their launch function; the object of the table's first part also holds the selector and the entry points.
+#ifdef NEFES_TU_W128
+constexpr bool kTuW128 = true;
+#else
+constexpr bool kTuW128 = false;
 #endif
-enum { H3_EXT_SIGMA = 0, H3_EXT_FULL, H3_SIGMA, H3_FULL, H3_TRAIN_STATIC, H3_TRAIN_FULL, H3_STATIC, H3_HG_SIGMA, H3_HG_FULL, H3_FH_FULL,
-       H3_TRAIN_EXT_STATIC, H3_TRAIN_EXT_FULL };
-int nefes_fwd_h3_launch_part1(int which, const FieldFwdH3Args& a, hipStream_t st);
-int nefes_fwd_h3_launch_part2(int which, const FieldFwdH3Args& a, hipStream_t st);
-int nefes_fwd_h3_launch_part3(int which, const FieldFwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 256, class 0
-int nefes_fwd_h3_launch_part4(int which, const FieldFwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 128, class 1
-int nefes_fwd_h3_launch_part5(int which, const FieldFwdH3Args& a, hipStream_t st);   // Wd = 256, class 1 (the reference's FEATURE_DIM at netwidth 256)
-int nefes_fwd_h3_launch_part6(int which, const FieldFwdH3Args& a, hipStream_t st);   // Wd = 128, class 0
-int nefes_fwd_h3_launch_part7(int which, const FieldFwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 256, class 1
-int nefes_fwd_h3_launch_part8(int which, const FieldFwdH3Args& a, hipStream_t st);   // TRAIN instances, Wd = 128, class 0
-int nefes_fwd_h3_launch_part9(int which, const FieldFwdH3Args& a, hipStream_t st);   // folded (FOLD) instances, Wd = 256, class 0
-int nefes_fwd_h3_launch_part11(int which, const FieldFwdH3Args& a, hipStream_t st);  // folded (FOLD) instances, Wd = 256, class 1
-int nefes_fwd_h3_launch_part13(int which, const FieldFwdH3Args& a, hipStream_t st);  // external encoding / hash grid, Wd = 256, class 1
-int nefes_fwd_h3_launch_part15(int which, const FieldFwdH3Args& a, hipStream_t st);  // ... their TRAIN instances
+#define X(part, MODE, ENC, W, NTR, TRAIN, FH) \
+    static_assert(part != NEFES_TU_PART || (W == 128) == kTuW128, "a Wd = 128 row belongs to an object built for Wd = 128, and no other row does");
+NEFES_H3_FWD_INSTANCES(X)
+#undef X
 
+template <int PART>
+static int h3_fwd_launch_rows(const NefesH3FwdKey& k, const FieldFwdH3Args& a, hipStream_t st) {
+#define X(part, MODE, ENC, W, NTR, TRAIN, FH)                                                                          \
+    if constexpr (part == PART) {                                                                                      \
+        if (k == NEFES_H3_FWD_KEY(MODE, ENC, W, NTR, TRAIN, FH))                                                       \
+            return launch_h3<NEFES_FIELD_##MODE, NEFES_XYZ_##ENC, W, NTR, TRAIN != 0, FH != 0>(a, st);                 \
+    }
+    NEFES_H3_FWD_INSTANCES(X)
+#undef X
+    return NEFES_E_UNSUPPORTED;
+}
+#define X(part, MODE, ENC, W, NTR, TRAIN, FH) int NEFES_H3_FWD_PART_FN(part)(const NefesH3FwdKey&, const FieldFwdH3Args&, hipStream_t);
+NEFES_H3_FWD_INSTANCES(X)
+#undef X
+int NEFES_H3_FWD_PART_FN(NEFES_TU_PART)(const NefesH3FwdKey& k, const FieldFwdH3Args& a, hipStream_t st) {
+    return h3_fwd_launch_rows<NEFES_TU_PART>(k, a, st);
+}
 
-#if NEFES_TU_PART == 1
-int nefes_fwd_h3_launch_part1(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    switch (which) {
-        case H3_EXT_SIGMA: return launch_h3<NEFES_FIELD_SIGMA, NEFES_XYZ_EXTERNAL32>(a, st);
-        case H3_EXT_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_EXTERNAL32>(a, st);
-        case H3_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 256, 1>(a, st);    // static head alone, inference (round 5)
-        case H3_HG_SIGMA: return launch_h3<NEFES_FIELD_SIGMA, NEFES_XYZ_HASHGRID_FUSED>(a, st);     // hash grid gathered in the prologue (round 5)
-        case H3_HG_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_HASHGRID_FUSED>(a, st);
+#if NEFES_TU_PART == 0
+struct H3FwdRow {
+    NefesH3FwdKey key;
+    const char* name;
+    int (*launch)(const NefesH3FwdKey&, const FieldFwdH3Args&, hipStream_t);
+};
+static const H3FwdRow h3_fwd_rows[] = {
+#define X(part, MODE, ENC, W, NTR, TRAIN, FH) \
+    {NEFES_H3_FWD_KEY(MODE, ENC, W, NTR, TRAIN, FH), "fwd p" #part " <" #MODE "," #ENC "," #W "," #NTR "," #TRAIN "," #FH ">", NEFES_H3_FWD_PART_FN(part)},
+    NEFES_H3_FWD_INSTANCES(X)
+#undef X
+};
+
+// Which row serves `desc` for a request: `mode` and the NEFES_H3_REQ_* flags say which entry point is asking.  Host arithmetic on the
+// descriptor only; the refusals and their order are the entry points' contract (tests/test_h3_instances.py replays them).
+struct H3FwdSel {
+    int rc;
+    const H3FwdRow* row;
+};
+static H3FwdSel h3_fwd_select(const NefesNetDesc* desc, int mode, unsigned req) {
+    const bool train = req & NEFES_H3_REQ_TRAIN, fh = req & NEFES_H3_REQ_FH, fused_grid = req & NEFES_H3_REQ_HASHGRID;
+    const bool ext = desc->xyz_encoding == NEFES_XYZ_EXTERNAL32, fold = desc->fold_final != 0;
+    const int cls = nefes_head_class(desc->feat_dim), w = desc->width;
+    // (the _hashgrid entry points take no network without a grid in front, the _fh ones have no argument for a supplied encoding)
+    if (fused_grid ? !ext : (fh && ext)) return {NEFES_E_BADARG, nullptr};
+    if ((req & NEFES_H3_REQ_ZROW) && desc->xyz_encoding != NEFES_XYZ_FREQ10) return {NEFES_E_UNSUPPORTED, nullptr};
+    if (mode != NEFES_FIELD_FULL && mode != NEFES_FIELD_STATIC && (train || mode != NEFES_FIELD_SIGMA)) return {NEFES_E_UNSUPPORTED, nullptr};
+    if (mode == NEFES_FIELD_FULL && !desc->has_transient) return {NEFES_E_BADARG, nullptr};
+    bool ok;
+    if (train) {
+        // train mode: the frequency embedding at both widths, a supplied encoding (the _ext entry points) at width 256; a folded
+        // pack is a frozen network's
+        ok = (req & NEFES_H3_REQ_EXT) ? (w == 256 && ext) : ((w == 256 || w == 128) && desc->xyz_encoding == NEFES_XYZ_FREQ10);
+        ok = ok && cls >= 0 && !fold;
+    } else {
+        // widths 128 / 256 x head classes 0 / 1 (layout.h) with the frequency embedding, width 256 with an external 32-feature
+        // embedding; the static head alone with the frequency embedding only.  A folded pack (NefesNetDesc.fold_final): folded
+        // rows exist for the full pass at width 256 with the frequency embedding; its sigma-only stream is the unfolded one, and
+        // no other kernel may read the folded head segments.
+        ok = (w == 256 || (w == 128 && !ext)) && cls >= 0 && (ext || desc->xyz_encoding == NEFES_XYZ_FREQ10);
+        ok = ok && !(mode == NEFES_FIELD_STATIC && ext);
+        ok = ok && !(fold && mode != NEFES_FIELD_SIGMA && !(mode == NEFES_FIELD_FULL && w == 256 && !ext && !fh));
+        // factored head: a network packed WITHOUT its feature rows (feat_dim 0: the 3-row colour head)
+        ok = ok && !(fh && (desc->feat_dim != 0 || w != 128 || ext || mode != NEFES_FIELD_FULL));
     }
-    return NEFES_E_UNSUPPORTED;
+    if (!ok) return {NEFES_E_UNSUPPORTED, nullptr};
+    const NefesH3FwdKey key = {fold && mode == NEFES_FIELD_FULL ? NEFES_FIELD_FULL_FOLD : mode,
+                               fused_grid ? NEFES_XYZ_HASHGRID_FUSED : desc->xyz_encoding, w,
+                               mode == NEFES_FIELD_SIGMA ? (w == 128 ? 5 : 1) : (cls == 0 ? 1 : 5), train, fh};
+    for (const H3FwdRow& r : h3_fwd_rows)
+        if (r.key == key) return {0, &r};
+    return {NEFES_E_UNSUPPORTED, nullptr};      // (e.g. the fused hash grid with head class 1: field_h3_instances.h)
 }
-#elif NEFES_TU_PART == 2
-// The Wd = 128 instances hold 2 x 4 accumulator tiles = 128 registers: with ~120 more for everything else the whole kernel fits
-// the 256 architectural VGPRs, and this object is built with -mllvm -amdgpu-mfma-vgpr-form (Makefile) so that the MFMAs
-// accumulate there.  Left to its heuristics hipcc parks the tiles in AGPRs and pays a v_accvgpr_read / _write for every value
-// the vector ALU touches (1.7 of the kernel's 6.3 VALU per MFMA: it is VALU-bound at this width): forward 0.85 -> 0.78 ms,
-// backward 0.77 -> 0.73 ms on the 80x60 refinement frame.
-int nefes_fwd_h3_launch_part2(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    switch (which) {
-        case H3_SIGMA: return launch_h3<NEFES_FIELD_SIGMA, NEFES_XYZ_FREQ10, 128, 5>(a, st);       // (the sigma-only pass has no rgb head: one instance per width)
-        case H3_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 128, 5>(a, st);
-        case H3_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 128, 5>(a, st);
+
+static int h3_fwd_stream(const NefesNetDesc* desc, const NefesH3FwdKey& k, NefesStreamInfo* si) {
+    NefesBlobInfo info;
+    int rc = nefes_blob_info(desc, &info);
+    if (rc) return rc;
+    *si = info.stream[k.mode == NEFES_FIELD_SIGMA ? NEFES_STREAM_FWD_SIGMA_H3
+                      : (k.mode == NEFES_FIELD_STATIC ? NEFES_STREAM_FWD_STATIC_H3 : NEFES_STREAM_FWD_FULL_H3)];
+    return si->n_slabs == 0 ? NEFES_E_UNSUPPORTED : 0;
+}
+
+// Everything of the kernel's arguments that follows from the row and the shape; `a` arrives with the entry point's pointers (and
+// z_row) set and the rest zero.
+static int h3_fwd_args(const NefesNetDesc* desc, const void* packed, const NefesH3FwdKey& k, int N, int S,
+                       const NefesHashGridDesc* grid, FieldFwdH3Args& a) {
+    NefesStreamInfo si;
+    int rc = h3_fwd_stream(desc, k, &si);
+    if (rc) return rc;
+    a.stream = (const char*)packed + si.slab_off;
+    a.bias = (const float*)((const char*)packed + si.bias_off);
+    a.n_slabs = si.n_slabs; a.bias_floats = si.bias_floats; a.scale_off = si.scale_off;
+    if (k.enc == NEFES_XYZ_HASHGRID_FUSED) {
+        rc = hg_geometry(grid, &a.hg, nullptr);
+        if (rc) return rc;
+        if (a.hg.n_levels != 16) return NEFES_E_UNSUPPORTED;       // sixteen levels x two features = the network's 32 inputs
     }
-    return NEFES_E_UNSUPPORTED;
+    // factored head: the raw output carries g = relu(dir_encoding) and a channel of ones where the feature channels would be:
+    // C' = W/2 + 1 "feature" channels
+    a.gout = k.fh ? k.w / 2 : 0;
+    a.N = N; a.S = S; a.C = k.fh ? a.gout + 1 : desc->feat_dim;
+    a.R = k.mode == NEFES_FIELD_SIGMA ? 1 : 3 + a.C + (k.mode == NEFES_FIELD_STATIC ? 1 : 6);
+    a.M = (long long)N * S;
+    if (a.M >= (1ll << 31) - 256) return NEFES_E_UNSUPPORTED;      // the kernel indexes samples with 32 bits
+    a.n_tiles = (int)((a.M + 127) / 128);
+    a.rows = k.train ? nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END) : 0;
+    magic_div((uint32_t)S, a.s_magic, a.s_shift);
+    return 0;
 }
-#elif NEFES_TU_PART == 3
-int nefes_fwd_h3_launch_part3(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    switch (which) {
-        case H3_TRAIN_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 256, 1, true>(a, st);
-        case H3_TRAIN_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 256, 1, true>(a, st);
-        // an external 32-feature encoding (a trainable hash grid): its features go to the E block in natural order (compact slot
-        // (s, h) = feature 2s + h = row 2s + h)
-        case H3_TRAIN_EXT_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_EXTERNAL32, 256, 1, true>(a, st);
-        case H3_TRAIN_EXT_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_EXTERNAL32, 256, 1, true>(a, st);
+
+// select -> args -> launch, behind the entry point's own pointer checks
+static int h3_fwd_run(const NefesNetDesc* desc, const void* packed, int mode, unsigned req, int N, int S,
+                      const NefesHashGridDesc* grid, FieldFwdH3Args& a, void* stream) {
+    const H3FwdSel s = h3_fwd_select(desc, mode, req);
+    if (s.rc) return s.rc;
+    const int rc = h3_fwd_args(desc, packed, s.row->key, N, S, grid, a);
+    return rc ? rc : s.row->launch(s.row->key, a, (hipStream_t)stream);
+}
+
+int nefes_h3_bwd_instance(const NefesNetDesc* desc, int mode, unsigned req, const char** name);      // field_bwd_h3.hip
+
+extern "C" int nefes_field_h3_instance(const NefesNetDesc* desc, int backward, int mode, unsigned request_flags, char* name, size_t cap) {
+    if (!desc || !name || cap == 0) return NEFES_E_BADARG;
+    name[0] = 0;
+    const unsigned kind = request_flags & ~(unsigned)NEFES_H3_REQ_EXT;     // the entry point families: at most one of them
+    if ((kind & (kind - 1)) || (request_flags >> 6) || ((request_flags & NEFES_H3_REQ_EXT) && kind != NEFES_H3_REQ_TRAIN) ||
+        (request_flags & (backward ? NEFES_H3_REQ_ZROW : NEFES_H3_REQ_STATIC_BWD)))
+        return NEFES_E_BADARG;
+    const char* text = nullptr;
+    int rc;
+    if (backward) {
+        rc = nefes_h3_bwd_instance(desc, mode, request_flags, &text);
+    } else {
+        const H3FwdSel s = h3_fwd_select(desc, mode, request_flags);
+        NefesStreamInfo si;
+        rc = s.rc ? s.rc : h3_fwd_stream(desc, s.row->key, &si);
+        if (!rc) text = s.row->name;
     }
-    return NEFES_E_UNSUPPORTED;
+    if (text) snprintf(name, cap, "%s", text);
+    return rc;
 }
-#elif NEFES_TU_PART == 4      // (built like part 2)
-int nefes_fwd_h3_launch_part4(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    switch (which) {
-        case H3_TRAIN_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 128, 5, true>(a, st);
-        case H3_TRAIN_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 128, 5, true>(a, st);
-    }
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 5
-int nefes_fwd_h3_launch_part5(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    if (which == H3_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 256, 5>(a, st);
-    if (which == H3_STATIC) return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 256, 5>(a, st);
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 6      // (built like part 2)
-int nefes_fwd_h3_launch_part6(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    if (which == H3_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 128, 1>(a, st);
-    if (which == H3_STATIC) return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 128, 1>(a, st);
-    if (which == H3_FH_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 128, 1, false, true>(a, st);      // factored head (round 5)
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 7
-int nefes_fwd_h3_launch_part7(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    switch (which) {
-        case H3_TRAIN_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 256, 5, true>(a, st);
-        case H3_TRAIN_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 256, 5, true>(a, st);
-    }
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 8      // (built like part 2)
-int nefes_fwd_h3_launch_part8(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    switch (which) {
-        case H3_TRAIN_STATIC: return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_FREQ10, 128, 1, true>(a, st);
-        case H3_TRAIN_FULL: return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10, 128, 1, true>(a, st);
-    }
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 9
-int nefes_fwd_h3_launch_part9(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    if (which == H3_FULL) return launch_h3<NEFES_FIELD_FULL_FOLD, NEFES_XYZ_FREQ10, 256, 1>(a, st);
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 11
-int nefes_fwd_h3_launch_part11(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    if (which == H3_FULL) return launch_h3<NEFES_FIELD_FULL_FOLD, NEFES_XYZ_FREQ10, 256, 5>(a, st);
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 13
-// The reference's FEATURE_DIM = 128 on a hash grid: the full pass with the five-tile rgb+feature head on a SUPPLIED encoding.  (The
-// sigma-only pass has no rgb head: part 1's H3_EXT_SIGMA / H3_HG_SIGMA serve both classes.)  No fused-gather instance of this class:
-// its forward <FULL, HASHGRID_FUSED, 256, 5> builds clean (256 + 256 registers, no scratch), its backward does not keep the house rules
-// (field_bwd_h3.hip part 13), and a forward alone would leave the pair's masks without a consumer -- DESIGN.md 4.8.
-// Experiments: make EXTRA_H3=-DNEFES_H3_HG_CLASS1 builds the pair and routes the class-1 full pass of the _hashgrid entry points to it
-// (re-check the registers with tools/kernel_resources.py and the moves with tools/hazard_lint.py after a compiler update).
-int nefes_fwd_h3_launch_part13(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    if (which == H3_EXT_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_EXTERNAL32, 256, 5>(a, st);
-#ifdef NEFES_H3_HG_CLASS1
-    if (which == H3_HG_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_HASHGRID_FUSED, 256, 5>(a, st);
-#endif
-    return NEFES_E_UNSUPPORTED;
-}
-#elif NEFES_TU_PART == 15
-int nefes_fwd_h3_launch_part15(int which, const FieldFwdH3Args& a, hipStream_t st) {
-    if (which == H3_TRAIN_EXT_STATIC) return launch_h3<NEFES_FIELD_STATIC, NEFES_XYZ_EXTERNAL32, 256, 5, true>(a, st);
-    if (which == H3_TRAIN_EXT_FULL) return launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_EXTERNAL32, 256, 5, true>(a, st);
-    return NEFES_E_UNSUPPORTED;
-}
-#else   // part 0
 
 // Train-mode forward on the fp16 pipe: as nefes_field_fwd_train (field_fwd.hip), same `acts` rows, same masks, same raw_t.
 extern "C" int nefes_field_fwd_train_h3(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
@@ -676,33 +699,9 @@ extern "C" int nefes_field_fwd_train_h3(const NefesNetDesc* desc, const void* pa
                                         float* raw_t, float* acts, uint32_t* masks, void* stream) {
     if (!desc || !packed || !raw_t || !acts || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
     if (!pts && !(rays_o && rays_d && z)) return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_UNSUPPORTED;
-    if (mode == NEFES_FIELD_FULL && !desc->has_transient) return NEFES_E_BADARG;
-    const int cls = nefes_head_class(desc->feat_dim);
-    if ((desc->width != 256 && desc->width != 128) || cls < 0 || desc->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;
-    if (desc->fold_final) return NEFES_E_UNSUPPORTED;               // (a folded pack is a frozen network's)
-    NefesBlobInfo info;
-    int rc = nefes_blob_info(desc, &info);
-    if (rc) return rc;
-    const NefesStreamInfo& si = info.stream[mode == NEFES_FIELD_STATIC ? NEFES_STREAM_FWD_STATIC_H3 : NEFES_STREAM_FWD_FULL_H3];
-    if (si.n_slabs == 0) return NEFES_E_UNSUPPORTED;
-    FieldFwdH3Args a;
-    a.stream = (const char*)packed + si.slab_off;
-    a.bias = (const float*)((const char*)packed + si.bias_off);
-    a.n_slabs = si.n_slabs; a.bias_floats = si.bias_floats; a.scale_off = si.scale_off;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.xyz_enc = nullptr; a.viewdirs = viewdirs; a.raw_t = raw_t; a.masks = masks;
-    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = 3 + a.C + (mode == NEFES_FIELD_STATIC ? 1 : 6);
-    a.M = (long long)N * S;
-    if (a.M >= (1ll << 31) - 256) return NEFES_E_UNSUPPORTED;      // the kernel indexes samples with 32 bits
-    a.n_tiles = (int)((a.M + 127) / 128);
-    a.acts = acts;
-    a.rows = nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END);
-    a.z_row = 0; a.gout = 0; a.hg_table = nullptr;
-    magic_div((uint32_t)S, a.s_magic, a.s_shift);
-    const int which = mode == NEFES_FIELD_STATIC ? H3_TRAIN_STATIC : H3_TRAIN_FULL;
-    hipStream_t st = (hipStream_t)stream;
-    if (desc->width == 256) return cls == 0 ? nefes_fwd_h3_launch_part3(which, a, st) : nefes_fwd_h3_launch_part7(which, a, st);
-    return cls == 1 ? nefes_fwd_h3_launch_part4(which, a, st) : nefes_fwd_h3_launch_part8(which, a, st);
+    FieldFwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.viewdirs = viewdirs; a.raw_t = raw_t; a.masks = masks; a.acts = acts;
+    return h3_fwd_run(desc, packed, mode, NEFES_H3_REQ_TRAIN, N, S, nullptr, a, stream);
 }
 
 // Train-mode forward of a NEFES_XYZ_EXTERNAL32 network on its caller-supplied encoding xyz_enc [N*S, 32] (a trainable hash grid):
@@ -710,114 +709,29 @@ extern "C" int nefes_field_fwd_train_h3(const NefesNetDesc* desc, const void* pa
 extern "C" int nefes_field_fwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* xyz_enc,
                                             const float* viewdirs, float* raw_t, float* acts, uint32_t* masks, void* stream) {
     if (!desc || !packed || !xyz_enc || !raw_t || !acts || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_UNSUPPORTED;
-    if (mode == NEFES_FIELD_FULL && !desc->has_transient) return NEFES_E_BADARG;
-    const int cls = nefes_head_class(desc->feat_dim);
-    if (desc->width != 256 || cls < 0 || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32) return NEFES_E_UNSUPPORTED;
-    if (desc->fold_final) return NEFES_E_UNSUPPORTED;
-    NefesBlobInfo info;
-    int rc = nefes_blob_info(desc, &info);
-    if (rc) return rc;
-    const NefesStreamInfo& si = info.stream[mode == NEFES_FIELD_STATIC ? NEFES_STREAM_FWD_STATIC_H3 : NEFES_STREAM_FWD_FULL_H3];
-    if (si.n_slabs == 0) return NEFES_E_UNSUPPORTED;
-    FieldFwdH3Args a;
-    a.stream = (const char*)packed + si.slab_off;
-    a.bias = (const float*)((const char*)packed + si.bias_off);
-    a.n_slabs = si.n_slabs; a.bias_floats = si.bias_floats; a.scale_off = si.scale_off;
-    a.rays_o = nullptr; a.rays_d = nullptr; a.z = nullptr; a.pts = nullptr; a.xyz_enc = xyz_enc; a.viewdirs = viewdirs; a.raw_t = raw_t;
-    a.masks = masks;
-    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = 3 + a.C + (mode == NEFES_FIELD_STATIC ? 1 : 6);
-    a.M = (long long)N * S;
-    if (a.M >= (1ll << 31) - 256) return NEFES_E_UNSUPPORTED;      // the kernel indexes samples with 32 bits
-    a.n_tiles = (int)((a.M + 127) / 128);
-    a.acts = acts;
-    a.rows = nefes_train_row(desc->width, desc->feat_dim, NEFES_TB_END);
-    a.z_row = 0; a.gout = 0; a.hg_table = nullptr;
-    magic_div((uint32_t)S, a.s_magic, a.s_shift);
-    const int which = mode == NEFES_FIELD_STATIC ? H3_TRAIN_EXT_STATIC : H3_TRAIN_EXT_FULL;
-    return cls == 0 ? nefes_fwd_h3_launch_part3(which, a, (hipStream_t)stream) : nefes_fwd_h3_launch_part15(which, a, (hipStream_t)stream);
+    FieldFwdH3Args a = {};
+    a.xyz_enc = xyz_enc; a.viewdirs = viewdirs; a.raw_t = raw_t; a.masks = masks; a.acts = acts;
+    return h3_fwd_run(desc, packed, mode, NEFES_H3_REQ_TRAIN | NEFES_H3_REQ_EXT, N, S, nullptr, a, stream);
 }
 
-static int field_fwd_h3_impl(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
-                             const float* rays_d, const float* z, int z_row, const float* pts, const float* xyz_enc,
-                             const float* viewdirs, float* raw_t, uint32_t* masks, void* stream,
-                             const NefesHashGridDesc* grid = nullptr, const float* table = nullptr, bool fh = false) {
-    if (!desc || !packed || !raw_t || N <= 0 || S <= 0) return NEFES_E_BADARG;
+// The inference entry points: `a` carries their pointers, `req` says which one is asking.
+static int field_fwd_h3_impl(const NefesNetDesc* desc, const void* packed, int mode, unsigned req, int N, int S,
+                             const NefesHashGridDesc* grid, FieldFwdH3Args& a, void* stream) {
+    if (!desc || !packed || !a.raw_t || N <= 0 || S <= 0) return NEFES_E_BADARG;
     const bool ext = desc->xyz_encoding == NEFES_XYZ_EXTERNAL32;
-    const bool fused_grid = ext && table != nullptr;            // the kernel gathers the 32 features itself (hashgrid.h)
-    if (fused_grid ? !(rays_o && rays_d && z && grid) : (ext ? !xyz_enc : (!pts && !(rays_o && rays_d && z)))) return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_SIGMA && mode != NEFES_FIELD_FULL && mode != NEFES_FIELD_STATIC) return NEFES_E_UNSUPPORTED;
-    if (mode == NEFES_FIELD_FULL && (!viewdirs || !desc->has_transient)) return NEFES_E_BADARG;
-    if (mode == NEFES_FIELD_STATIC && (!viewdirs || ext)) return ext ? NEFES_E_UNSUPPORTED : NEFES_E_BADARG;   // (frequency embedding only)
-    // compiled set: widths 128 / 256 x head classes 0 / 1 (layout.h) with the frequency embedding; width 256 x head classes 0 / 1 with
-    // an external 32-feature embedding (the hash grid gathered by the kernel itself: class 0, and the sigma-only pass of either class)
-    const int cls = nefes_head_class(desc->feat_dim);
-    const bool big = desc->width == 256, small = desc->width == 128 && !ext;
-    if (!(big || small) || cls < 0 || (desc->xyz_encoding != NEFES_XYZ_FREQ10 && !ext)) return NEFES_E_UNSUPPORTED;
-    // a folded pack (NefesNetDesc.fold_final): folded instances exist for the full pass at width 256 with the frequency embedding;
-    // its sigma-only stream is the unfolded one.  No other kernel may read the folded head segments.
-    const bool fold = desc->fold_final != 0;
-    if (fold && mode != NEFES_FIELD_SIGMA && !(mode == NEFES_FIELD_FULL && big && !ext && !fh)) return NEFES_E_UNSUPPORTED;
-    NefesBlobInfo info;
-    int rc = nefes_blob_info(desc, &info);
-    if (rc) return rc;
-    const NefesStreamInfo& si = info.stream[mode == NEFES_FIELD_SIGMA ? NEFES_STREAM_FWD_SIGMA_H3
-                                            : (mode == NEFES_FIELD_STATIC ? NEFES_STREAM_FWD_STATIC_H3 : NEFES_STREAM_FWD_FULL_H3)];
-    if (si.n_slabs == 0) return NEFES_E_UNSUPPORTED;
-    FieldFwdH3Args a;
-    a.stream = (const char*)packed + si.slab_off;
-    a.bias = (const float*)((const char*)packed + si.bias_off);
-    a.n_slabs = si.n_slabs; a.bias_floats = si.bias_floats; a.scale_off = si.scale_off;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.xyz_enc = xyz_enc; a.viewdirs = viewdirs; a.raw_t = raw_t; a.masks = masks;
-    a.acts = nullptr; a.rows = 0; a.z_row = z_row;
-    a.hg_table = (const float2*)table;
-    if (fused_grid) {
-        rc = hg_geometry(grid, &a.hg, nullptr);
-        if (rc) return rc;
-        if (a.hg.n_levels != 16) return NEFES_E_UNSUPPORTED;       // sixteen levels x two features = the network's 32 inputs
-    }
-    a.N = N; a.S = S; a.C = desc->feat_dim; a.R = mode == NEFES_FIELD_SIGMA ? 1 : 3 + a.C + (mode == NEFES_FIELD_STATIC ? 1 : 6);
-    a.gout = 0;
-    if (fh) {
-        // factored head: a network packed WITHOUT its feature rows (feat_dim 0: the 3-row colour head) whose raw output carries
-        // g = relu(dir_encoding) and a channel of ones where the feature channels would be: C' = W/2 + 1 "feature" channels
-        if (desc->feat_dim != 0 || desc->width != 128 || ext || mode != NEFES_FIELD_FULL) return NEFES_E_UNSUPPORTED;
-        a.gout = desc->width / 2;
-        a.C = a.gout + 1;
-        a.R = 3 + a.C + 6;
-    }
-    a.M = (long long)N * S;
-    if (a.M >= (1ll << 31) - 256) return NEFES_E_UNSUPPORTED;      // the kernel indexes samples with 32 bits
-    a.n_tiles = (int)((a.M + 127) / 128);
-    magic_div((uint32_t)S, a.s_magic, a.s_shift);
-    hipStream_t st = (hipStream_t)stream;
-    if (fh) return nefes_fwd_h3_launch_part6(H3_FH_FULL, a, st);
-    if (mode == NEFES_FIELD_STATIC) {
-        // The static head alone at inference (round 5): what a frozen coarse network runs when test_time is False (rendering.py:116-125)
-        // and a fine network with NeRFW off (nerfh_nff.py:217-231 with output_transient False) -- the TRAIN instances' kernel without
-        // the activation stores.
-        if (big) return cls == 0 ? nefes_fwd_h3_launch_part1(H3_STATIC, a, st) : nefes_fwd_h3_launch_part5(H3_STATIC, a, st);
-        return cls == 1 ? nefes_fwd_h3_launch_part2(H3_STATIC, a, st) : nefes_fwd_h3_launch_part6(H3_STATIC, a, st);
-    }
-    // (the sigma-only instances have no rgb head: one per encoding serves both head classes)
-    if (fused_grid && mode == NEFES_FIELD_SIGMA) return nefes_fwd_h3_launch_part1(H3_HG_SIGMA, a, st);
-    // (class 1: the separate launches -- part 13 answers NEFES_E_UNSUPPORTED unless built with NEFES_H3_HG_CLASS1)
-    if (fused_grid) return cls == 0 ? nefes_fwd_h3_launch_part1(H3_HG_FULL, a, st) : nefes_fwd_h3_launch_part13(H3_HG_FULL, a, st);
-    if (ext && mode == NEFES_FIELD_SIGMA) return nefes_fwd_h3_launch_part1(H3_EXT_SIGMA, a, st);
-    if (ext) return cls == 0 ? nefes_fwd_h3_launch_part1(H3_EXT_FULL, a, st) : nefes_fwd_h3_launch_part13(H3_EXT_FULL, a, st);
-    if (small) {
-        if (mode == NEFES_FIELD_SIGMA) return nefes_fwd_h3_launch_part2(H3_SIGMA, a, st);
-        return cls == 1 ? nefes_fwd_h3_launch_part2(H3_FULL, a, st) : nefes_fwd_h3_launch_part6(H3_FULL, a, st);
-    }
-    if (mode == NEFES_FIELD_SIGMA) return launch_h3<NEFES_FIELD_SIGMA, NEFES_XYZ_FREQ10>(a, st);
-    if (fold) return cls == 0 ? nefes_fwd_h3_launch_part9(H3_FULL, a, st) : nefes_fwd_h3_launch_part11(H3_FULL, a, st);
-    return cls == 0 ? launch_h3<NEFES_FIELD_FULL, NEFES_XYZ_FREQ10>(a, st) : nefes_fwd_h3_launch_part5(H3_FULL, a, st);
+    const bool fused_grid = ext && a.hg_table != nullptr;       // the kernel gathers the 32 features itself (hashgrid.h)
+    if (fused_grid ? !(a.rays_o && a.rays_d && a.z && grid) : (ext ? !a.xyz_enc : (!a.pts && !(a.rays_o && a.rays_d && a.z)))) return NEFES_E_BADARG;
+    // (a mode that is none of the three, and the static head of an external encoding, are the selector's to refuse)
+    if (!a.viewdirs && (mode == NEFES_FIELD_FULL || (mode == NEFES_FIELD_STATIC && !ext))) return NEFES_E_BADARG;
+    return h3_fwd_run(desc, packed, mode, req, N, S, grid, a, stream);
 }
 
 extern "C" int nefes_field_fwd_h3(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
                                   const float* rays_d, const float* z, const float* pts, const float* xyz_enc,
                                   const float* viewdirs, float* raw_t, uint32_t* masks, void* stream) {
-    return field_fwd_h3_impl(desc, packed, mode, N, S, rays_o, rays_d, z, 0, pts, xyz_enc, viewdirs, raw_t, masks, stream);
+    FieldFwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.xyz_enc = xyz_enc; a.viewdirs = viewdirs; a.raw_t = raw_t; a.masks = masks;
+    return field_fwd_h3_impl(desc, packed, mode, 0, N, S, nullptr, a, stream);
 }
 
 // A NEFES_XYZ_EXTERNAL32 network whose 32 features are a multiresolution hash grid of pts = o + d z (BASELINE configs[3]:
@@ -828,8 +742,10 @@ extern "C" int nefes_field_fwd_h3_hashgrid(const NefesNetDesc* desc, const void*
                                            const float* z, int z_is_row, const float* viewdirs, float* raw_t, uint32_t* masks,
                                            void* stream) {
     if (!desc || desc->xyz_encoding != NEFES_XYZ_EXTERNAL32 || !grid || !table) return NEFES_E_BADARG;
-    return field_fwd_h3_impl(desc, packed, mode, N, S, rays_o, rays_d, z, z_is_row ? 1 : 0, nullptr, nullptr, viewdirs, raw_t, masks, stream,
-                             grid, table);
+    FieldFwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.z_row = z_is_row ? 1 : 0; a.viewdirs = viewdirs; a.raw_t = raw_t; a.masks = masks;
+    a.hg_table = (const float2*)table;
+    return field_fwd_h3_impl(desc, packed, mode, NEFES_H3_REQ_HASHGRID, N, S, grid, a, stream);
 }
 
 // Factored head (see the kernel's FH parameter): `desc` / `packed` describe the network WITHOUT its feature rows (feat_dim 0);
@@ -838,7 +754,9 @@ extern "C" int nefes_field_fwd_h3_fh(const NefesNetDesc* desc, const void* packe
                                      const float* rays_d, const float* z, const float* viewdirs, float* raw_t, uint32_t* masks,
                                      void* stream) {
     if (!rays_o || !rays_d || !z) return NEFES_E_BADARG;
-    return field_fwd_h3_impl(desc, packed, mode, N, S, rays_o, rays_d, z, 0, nullptr, nullptr, viewdirs, raw_t, masks, stream, nullptr, nullptr, true);
+    FieldFwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.viewdirs = viewdirs; a.raw_t = raw_t; a.masks = masks;
+    return field_fwd_h3_impl(desc, packed, mode, NEFES_H3_REQ_FH, N, S, nullptr, a, stream);
 }
 
 // The same pass with ONE row of S depths shared by every ray (`z_row` [S]): the coarse pass at test time with scalar near / far
@@ -847,7 +765,9 @@ extern "C" int nefes_field_fwd_h3_zrow(const NefesNetDesc* desc, const void* pac
                                        const float* rays_d, const float* z_row, const float* viewdirs, float* raw_t, uint32_t* masks,
                                        void* stream) {
     if (!rays_o || !rays_d || !z_row) return NEFES_E_BADARG;
-    if (desc && desc->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;
-    return field_fwd_h3_impl(desc, packed, mode, N, S, rays_o, rays_d, z_row, 1, nullptr, nullptr, viewdirs, raw_t, masks, stream);
+    if (desc && desc->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;     // (ahead of the null checks below, as ever)
+    FieldFwdH3Args a = {};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z_row; a.z_row = 1; a.viewdirs = viewdirs; a.raw_t = raw_t; a.masks = masks;
+    return field_fwd_h3_impl(desc, packed, mode, NEFES_H3_REQ_ZROW, N, S, nullptr, a, stream);
 }
-#endif   // NEFES_TU_PART
+#endif   // NEFES_TU_PART == 0

@@ -37,11 +37,12 @@ class NefesHashGridDesc(C.Structure):
                 ("base_resolution", C.c_int32), ("per_level_scale", C.c_float), ("bound", C.c_float)]
 
 
-ABI_VERSION = 18       # NEFES_ABI_VERSION of include/nefes_hip.h
+ABI_VERSION = 19       # NEFES_ABI_VERSION of include/nefes_hip.h
 STREAM_FWD_SIGMA, STREAM_FWD_STATIC, STREAM_FWD_FULL, STREAM_BWD_FULL, STREAM_FWD_SIGMA_X6, STREAM_FWD_FULL_X6, STREAM_BWD_FULL_X6, STREAM_BWD_STATIC = 0, 1, 2, 3, 4, 5, 6, 7
 STREAM_FWD_SIGMA_H3, STREAM_FWD_FULL_H3, STREAM_BWD_FULL_H3, STREAM_FWD_STATIC_H3, STREAM_BWD_STATIC_H3 = 8, 9, 10, 11, 12
 FIELD_SIGMA, FIELD_STATIC, FIELD_FULL = 0, 1, 2
 XYZ_FREQ10, XYZ_EXTERNAL32 = 0, 1
+H3_REQ_TRAIN, H3_REQ_EXT, H3_REQ_HASHGRID, H3_REQ_FH, H3_REQ_ZROW, H3_REQ_STATIC_BWD = 1, 2, 4, 8, 16, 32
 (TB_E, TB_DV, TB_L1, TB_FINAL, TB_DIR, TB_T0, TB_T1, TB_T2, TB_RGB, TB_SIG, TB_TH, TB_END) = (0, 1, 2, 10, 11, 12, 13, 14, 15, 16,
                                                                                               17, 18)
 COMP_TRANSIENT, COMP_STATIC_ONLY, COMP_SIGMA_ONLY, COMP_WHITE_BKGD, COMP_FEAT_WEIGHTS_ONLY = 1, 2, 4, 8, 16
@@ -99,6 +100,7 @@ SIGNATURES = {
     "nefes_field_fwd_x6": (_i, [_desc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_field_bwd_h3": (_i, [_desc, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_field_bwd_static_h3": (_i, [_desc, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_field_h3_instance": (_i, [_desc, _i, _i, C.c_uint, C.c_char_p, _sz]),
     "nefes_feat_head_fwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
     "nefes_feat_head_bwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
     "nefes_field_fwd_h3_fh": (_i, [_desc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),

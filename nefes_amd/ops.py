@@ -399,7 +399,7 @@ def h3_serves(pk):
 
 
 def static_h3(pk):
-    """The static-head instances of the fp16 two-part kernels apply (csrc/field_fwd_h3.hip H3_STATIC, nefes_field_bwd_static_h3;
+    """The static-head instances of the fp16 two-part kernels apply (the STATIC rows of csrc/field_h3_instances.h, nefes_field_bwd_static_h3;
     the train-mode instances too: train.fp16_pipe): every compiled (width, head class) pair with the frequency embedding."""
     return h3_serves(pk) and pk.xyz_encoding == L.XYZ_FREQ10
 
@@ -427,7 +427,7 @@ def require_instance(pk, what):
 
 
 def fold_shape(width, feat_dim, xyz_encoding=L.XYZ_FREQ10):
-    """Shapes with folded instances (csrc/field_fwd_h3.hip parts 9 / 11): width 256, both head classes, frequency embedding, full pass."""
+    """Shapes with folded instances (the FULL_FOLD rows of csrc/field_h3_instances.h): width 256, both head classes, frequency embedding, full pass."""
     return width == 256 and head_class(feat_dim) >= 0 and xyz_encoding == L.XYZ_FREQ10
 
 
@@ -448,7 +448,8 @@ def is_generic(pk):
 
 def hashgrid_fused_ok(pk, grid):
     """The fp16 two-part field kernels can gather this hash grid themselves: width 256, head class 0, sixteen levels x two features.
-    (Head class 1 -- the 128-channel feature head -- has instances on a SUPPLIED encoding only, csrc/field_bwd_h3.hip part 13: its
+    (Head class 1 -- the 128-channel feature head -- has instances on a SUPPLIED encoding only -- csrc/field_h3_instances.h, the note
+    at the backward's <256, 9, EXTERNAL32> row: its
     renders take HashGridEncode + FieldFromEncoding, and with them the four-launch coarse pass.)"""
     return (FUSED_HASHGRID and isinstance(grid, HashGrid) and h3_serves(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32
             and head_class(pk.feat_dim) == 0 and grid.desc.n_levels == 16 and grid.desc.n_features == 2)

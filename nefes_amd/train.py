@@ -153,7 +153,7 @@ def fp16_pipe(pk):
 
 def ext_pipe(pk):
     """The train-mode instances of a network on an external 32-feature encoding (a hash grid): fp16 two-part pipe, width 256, either
-    head class (csrc/field_fwd_h3.hip H3_TRAIN_EXT_*, parts 3 / 15)."""
+    head class (the TRAIN rows with EXTERNAL32 of csrc/field_h3_instances.h)."""
     return ops.h3_serves(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32        # (h3_shape: width 256 is the external encoding's only width)
 
 

@@ -1,6 +1,6 @@
 """Hash-grid fields with the reference's 128-channel feature head: width 256, NEFES_XYZ_EXTERNAL32, head class 1 (30 <= C <= 141).
 
-The instances under test (csrc/field_fwd_h3.hip / field_bwd_h3.hip parts 13 and 15): the full pass on a supplied encoding, its
+The instances under test (csrc/field_h3_instances.h, the <..., EXTERNAL32, 256, 5, ...> / <256, 9, EXTERNAL32, ...> rows): the full pass on a supplied encoding, its
 backward-to-inputs, and the train-mode pair; the sigma-only instances are the class-0 ones, reached for class 1 too.  No instance of
 this class gathers the hash grid itself (the backward did not keep the accumulator tiles in place), so renders take
 HashGridEncode + FieldFromEncoding -- the routing is asserted, and the composition is checked against the oracle through the grid.
@@ -232,7 +232,7 @@ def _ray_inputs(N, S, seed):
 
 @pytest.mark.parametrize("C,N,S", [(30, 7, 33), (128, 41, 24), (141, 7, 33)])
 def test_class1_takes_the_separate_launches_and_is_correct(C, N, S):
-    """No fused-gather instance of head class 1 is built (csrc/field_bwd_h3.hip part 13): hashgrid_fused_ok and
+    """No fused-gather instance of head class 1 is built (csrc/field_h3_instances.h, the note at the backward's <256, 9, EXTERNAL32> row): hashgrid_fused_ok and
     fused_coarse_pass_ok say no, the fused entry point refuses the full pass loudly, and rays -> HashGridEncode -> FieldFromEncoding
     gives raw outputs within max(3e-6, 3 e_ref) of the float64 oracle and ray gradients branch-pinned within max(1e-4, 1.5 e_ref).
     The sigma-only gather instance has no rgb head and serves either class: bit-identical to the separate launches, also on one shared

@@ -1,35 +1,162 @@
-"""Digest of the fp16 two-part field kernels' outputs on fixed inputs, for A/B builds that must not change a bit.
-    NEFES_HIP_LIB=<lib> python tools/ab_identical.py [Wd C]
-prints one sha256 per output of the forward kernels (sigma-only raw; full raw + ReLU masks).  Run it once per
-library (tools/ab_h3.sh builds side libraries) and compare the lines: a re-scheduling of the same arithmetic gives the same digests."""
+"""Digests of what the fp16 two-part field kernels write, on fixed inputs, for A/B builds that must not change a bit.
+    NEFES_HIP_LIB=<lib> python tools/ab_identical.py
+prints one sha256 per output of every public fp16 entry point at every row of csrc/field_h3_instances.h it can reach: forward raw_t
+and ReLU masks (TRAIN rows: `acts` too), backward g_pts / g_xyz_enc and g_viewdirs_s (TRAIN rows: `dacts` too).  3 rays x 50 samples =
+one full 128-sample tile and a ragged one, S a multiple of nothing; one shared-depth-row case for _zrow and _hashgrid; fixed seeds.
+Run it once per library and compare the lines that do not start with '#': a re-arrangement of the host code, or a re-scheduling of the
+same arithmetic, gives the same digests.  Only entry points that older libraries export as well are called, and an older library's
+ABI number is accepted, so the same script runs on both sides."""
+import ctypes as C
 import hashlib, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from nefes_amd import lib as L, ops
-from nefes_amd.field import NeRFH_NFF
+from nefes_amd import lib as L
 
+_raw = C.CDLL(L.LIB_PATH)                      # A/B against a library of an earlier commit: bind what it has, under its own ABI number
+L.SIGNATURES = {k: v for k, v in L.SIGNATURES.items() if hasattr(_raw, k)}
+L.ABI_VERSION = _raw.nefes_version()
+from nefes_amd import ops
+
+lib = L.load()
 dev = torch.device('cuda')
-Wd, C = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (256, 16)
-N, S = 1000, 77                       # a ragged last tile, S not a multiple of anything
-torch.manual_seed(0)
-fine = NeRFH_NFF('fine', W=Wd, f_dim=C, encode_appearance=True, encode_transient=True).to(dev)
-with torch.no_grad():                 # spread the activations over a few octaves so that the exponent picks differ per sample
-    for i, p in enumerate(fine.parameters()):
-        p.mul_(1.0 + 0.5 * ((i * 7) % 5))
-pk = fine.packed()
+N, S = 3, 50
+M = N * S
+SIGMA, STATIC, FULL = L.FIELD_SIGMA, L.FIELD_STATIC, L.FIELD_FULL
 g = torch.Generator(device='cpu').manual_seed(1)
-o = (torch.randn(N, 3, generator=g) * 0.3).to(dev)
-d = torch.nn.functional.normalize(torch.randn(N, 3, generator=g), dim=-1).to(dev)
+rnd = lambda *shape: torch.randn(*shape, generator=g)
+o = (rnd(N, 3) * 0.3).to(dev)
+d = torch.nn.functional.normalize(rnd(N, 3), dim=-1).to(dev)
 z = torch.sort(torch.rand(N, S, generator=g) * 4, -1)[0].to(dev)
+z_row = z[0].contiguous()
+enc = (rnd(M, 32) * 0.5).to(dev)
+grid = L.NefesHashGridDesc(16, 2, 14, 16, 1.3819, 8.0)
+table = (rnd(int(lib.nefes_hashgrid_table_entries(C.byref(grid))), 2) * 0.5).to(dev)
+P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+reached = set()
+
+
+def network(width, c, ext, fold):
+    """PackedField of a random network (the tensors of nerfh_nff.py:452-505); activations spread over a few octaves so that the
+    exponent picks differ per sample"""
+    gw = torch.Generator(device='cpu').manual_seed(width + c)
+    w2, k_in = width // 2, 32 if ext else 63
+    shapes = [(width, k_in)] + [(width, width)] * 3 + [(width, width + k_in)] + [(width, width)] * 3 + \
+             [(width, width), (w2, width + 27), (1, width), (3 + c, w2), (w2, width + 27), (w2, w2), (w2, w2), (1, w2), (3, w2), (1, w2)]
+    sd = {}
+    for i, (name, (n_out, n_in)) in enumerate(zip(ops.PackedField.LAYERS_FINE, shapes)):
+        s = (1.0 + 0.5 * ((i * 7) % 5)) / n_in ** 0.5
+        sd[name + ".weight"] = (torch.rand(n_out, n_in, generator=gw) * 2 - 1) * s * 1.7
+        sd[name + ".bias"] = (torch.rand(n_out, generator=gw) * 2 - 1) * 0.1
+    return ops.PackedField(sd, width, c, True, dev, xyz_encoding=L.XYZ_EXTERNAL32 if ext else L.XYZ_FREQ10, fold_final=fold)
 
 
 def dig(t):
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
 
 
-print("lib", os.environ.get("NEFES_HIP_LIB") or "shipped")
-raw, _ = ops.field_fwd_x6(pk, L.FIELD_SIGMA, N, S, rays_o=o, rays_d=d, z=z, viewdirs=d, want_masks=False)
-print("sigma raw  ", dig(raw))
-for mode, name in ((L.FIELD_FULL, "full"),):
-    raw, m = ops.field_fwd_x6(pk, mode, N, S, rays_o=o, rays_d=d, z=z, viewdirs=d, want_masks=True)
-    print(f"{name} raw   ", dig(raw), " masks", dig(m), " finite", bool(torch.isfinite(raw).all()))
+def note(pk, backward, mode, flags):
+    if "nefes_field_h3_instance" in L.SIGNATURES:
+        name = C.create_string_buffer(96)
+        assert lib.nefes_field_h3_instance(C.byref(pk.desc), backward, mode, flags, name, len(name)) == 0
+        reached.add(name.value.decode())
+        print("#", name.value.decode())
+
+
+def out(tag, **tensors):
+    torch.cuda.synchronize()
+    print(f"{tag:58s}", "  ".join(f"{k} {dig(t)}" for k, t in tensors.items()), flush=True)
+
+
+def buffers(pk, R, train):
+    raw = torch.zeros(N, R, S, device=dev)
+    masks = torch.zeros(pk.mask_bytes(M) // 4, dtype=torch.int32, device=dev)
+    acts = torch.zeros((M + 127) // 128, int(lib.nefes_train_rows(C.byref(pk.desc))), 128, device=dev) if train else None
+    return raw, masks, acts
+
+
+def run(pk, what):
+    """every entry point that serves this network: forward, then the backward of its outputs"""
+    ds, blob, c, tag = C.byref(pk.desc), P(pk.blob), pk.feat_dim, f"W{pk.width} C{pk.feat_dim} {what}"
+    ext = pk.xyz_encoding == L.XYZ_EXTERNAL32
+    upstream = lambda R: (torch.randn(N, R, S, generator=torch.Generator(device='cpu').manual_seed(R)) * 0.1).to(dev)
+    grads = lambda: (torch.zeros(M, 32 if ext else 3, device=dev), torch.zeros(M, 3, device=dev))
+    if what == "fh":
+        R = 3 + (pk.width // 2 + 1) + 6
+        raw, masks, _ = buffers(pk, R, False)
+        note(pk, 0, FULL, L.H3_REQ_FH)
+        L.check(lib.nefes_field_fwd_h3_fh(ds, blob, FULL, N, S, P(o), P(d), P(z), P(d), P(raw), P(masks), None), tag)
+        out(tag + " fwd_h3_fh", raw=raw, masks=masks)
+        note(pk, 1, FULL, L.H3_REQ_FH)
+        gmap = (torch.randn(N, pk.width // 2 + 1, generator=torch.Generator(device='cpu').manual_seed(5)) * 0.1).to(dev)
+        for name, gm in (("bwd_h3_fh", None), ("bwd_h3_fh gmap", gmap)):
+            gx, gv = grads()
+            L.check(lib.nefes_field_bwd_h3_fh(ds, blob, N, S, P(o), P(d), P(z), P(d), P(raw), P(upstream(R)), P(gm), P(masks), P(gx), P(gv), None), tag)
+            out(f"{tag} {name}", g_pts=gx, g_viewdirs_s=gv)
+        return
+    modes = (FULL,) if what == "fold" else ((SIGMA, FULL) if ext else (SIGMA, STATIC, FULL))
+    for mode in modes:
+        R = 1 if mode == SIGMA else 3 + c + (1 if mode == STATIC else 6)
+        raw, masks, _ = buffers(pk, R, False)
+        note(pk, 0, mode, 0)
+        L.check(lib.nefes_field_fwd_h3(ds, blob, mode, N, S, None if ext else P(o), None if ext else P(d), None if ext else P(z), None,
+                                       P(enc) if ext else None, P(d), P(raw), P(masks), None), tag)
+        out(f"{tag} fwd_h3 mode {mode}", raw=raw, masks=masks)
+        if mode == SIGMA:
+            continue
+        gx, gv = grads()
+        if mode == FULL:
+            note(pk, 1, mode, 0)
+            L.check(lib.nefes_field_bwd_h3(ds, blob, N, S, P(o), P(d), P(z), None, P(d), P(raw), P(upstream(R)), P(masks),
+                                           None if ext else P(gx), P(gx) if ext else None, P(gv), None), tag)
+            out(f"{tag} bwd_h3", **{"g_xyz_enc" if ext else "g_pts": gx, "g_viewdirs_s": gv})
+        else:
+            note(pk, 1, mode, L.H3_REQ_STATIC_BWD)
+            L.check(lib.nefes_field_bwd_static_h3(ds, blob, N, S, P(o), P(d), P(z), None, P(d), P(raw), P(upstream(R)), P(masks), P(gx), P(gv), None), tag)
+            out(f"{tag} bwd_static_h3", g_pts=gx, g_viewdirs_s=gv)
+    if what == "fold":
+        return
+    if what == "zrow":                          # one row of depths shared by every ray
+        raw, masks, _ = buffers(pk, 1, False)
+        note(pk, 0, SIGMA, L.H3_REQ_ZROW)
+        L.check(lib.nefes_field_fwd_h3_zrow(ds, blob, SIGMA, N, S, P(o), P(d), P(z_row), P(d), P(raw), P(masks), None), tag)
+        out(f"{tag} fwd_h3_zrow mode {SIGMA}", raw=raw, masks=masks)
+    if ext and c <= 29:                         # the hash grid gathered by the kernels themselves
+        for mode, row in ((SIGMA, 1), (SIGMA, 0), (FULL, 0)):
+            R = 1 if mode == SIGMA else 3 + c + 6
+            raw, masks, _ = buffers(pk, R, False)
+            note(pk, 0, mode, L.H3_REQ_HASHGRID)
+            L.check(lib.nefes_field_fwd_h3_hashgrid(ds, blob, C.byref(grid), P(table), mode, N, S, P(o), P(d), P(z_row if row else z), row, P(d),
+                                                    P(raw), P(masks), None), tag)
+            out(f"{tag} fwd_h3_hashgrid mode {mode} z_is_row {row}", raw=raw, masks=masks)
+        gx, gv = torch.zeros(M, 3, device=dev), torch.zeros(M, 3, device=dev)
+        note(pk, 1, FULL, L.H3_REQ_HASHGRID)
+        L.check(lib.nefes_field_bwd_h3_hashgrid(ds, blob, C.byref(grid), P(table), N, S, P(o), P(d), P(z), P(d), P(raw), P(upstream(R)), P(masks),
+                                                P(gx), P(gv), None), tag)
+        out(f"{tag} bwd_h3_hashgrid", g_pts=gx, g_viewdirs_s=gv)
+    for mode in (STATIC, FULL):                 # train mode
+        R = 3 + c + (1 if mode == STATIC else 6)
+        raw, masks, acts = buffers(pk, R, True)
+        dacts, (gx, gv) = torch.zeros_like(acts), grads()
+        flags = L.H3_REQ_TRAIN | (L.H3_REQ_EXT if ext else 0)
+        note(pk, 0, mode, flags)
+        note(pk, 1, mode, flags)
+        if ext:
+            L.check(lib.nefes_field_fwd_train_h3_ext(ds, blob, mode, N, S, P(enc), P(d), P(raw), P(acts), P(masks), None), tag)
+            out(f"{tag} fwd_train_h3_ext mode {mode}", raw=raw, masks=masks, acts=acts)
+            L.check(lib.nefes_field_bwd_train_h3_ext(ds, blob, mode, N, S, P(d), P(raw), P(upstream(R)), P(masks), P(dacts), P(gx), P(gv), None), tag)
+            out(f"{tag} bwd_train_h3_ext mode {mode}", g_xyz_enc=gx, g_viewdirs_s=gv, dacts=dacts)
+        else:
+            L.check(lib.nefes_field_fwd_train_h3(ds, blob, mode, N, S, P(o), P(d), P(z), None, P(d), P(raw), P(acts), P(masks), None), tag)
+            out(f"{tag} fwd_train_h3 mode {mode}", raw=raw, masks=masks, acts=acts)
+            L.check(lib.nefes_field_bwd_train_h3(ds, blob, mode, N, S, P(o), P(d), P(z), P(d), P(raw), P(upstream(R)), P(masks), P(dacts),
+                                                 P(gx), P(gv), None), tag)
+            out(f"{tag} bwd_train_h3 mode {mode}", g_pts=gx, g_viewdirs_s=gv, dacts=dacts)
+
+
+print("# lib", os.environ.get("NEFES_HIP_LIB") or "shipped", "ABI", L.ABI_VERSION)
+for width, c, ext, fold, what in ((256, 16, 0, 0, "zrow"), (256, 128, 0, 0, "freq"), (128, 16, 0, 0, "freq"), (128, 128, 0, 0, "freq"),
+                                  (128, 0, 0, 0, "fh"), (256, 16, 0, 1, "fold"), (256, 128, 0, 1, "fold"), (256, 16, 1, 0, "ext"),
+                                  (256, 128, 1, 0, "ext")):
+    run(network(width, c, bool(ext), bool(fold)), what)
+if reached:
+    print(f"# table rows reached: {len(reached)}")
