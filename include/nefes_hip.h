@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define NEFES_ABI_VERSION 19
+#define NEFES_ABI_VERSION 20
 /* layout version of the blob nefes_pack_weights writes (second header word): moves when that layout does, not with every new call */
 #define NEFES_BLOB_FORMAT 17
 
@@ -320,24 +320,30 @@ int nefes_field_h3_instance(const NefesNetDesc* desc, int backward, int mode, un
  * pair of untuned kernels (nefes_amd/csrc/field_generic.hip): strict fp32 on v_mfma_f32_32x32x2_f32, shape as run-time arguments,
  * frequency embedding (63 / 27 features) computed in the kernel, frozen weights (backward to the inputs only).
  * width: a multiple of 32 in 32..512; depth 1..8; skip: index (0-based, 1 <= skip < depth) of the layer that takes
- * [embedding, h] (the reference's skips=[4] when depth > 4), or -1; 0 < feat_dim <= 141.  NEFES_E_UNSUPPORTED otherwise. */
+ * [embedding, h] (the reference's skips=[4] when depth > 4), or -1; 0 < feat_dim <= 141; xyz_encoding: NEFES_XYZ_FREQ10 (0, what a
+ * description made of the first five fields means) or NEFES_XYZ_EXTERNAL32: the xyz embedding is 32 features SUPPLIED per sample
+ * (a hash grid: nefes_hashgrid_fwd), served by the _ext calls below.  NEFES_E_UNSUPPORTED otherwise. */
 typedef struct NefesGenericNetDesc {
     int32_t width;
     int32_t depth;
     int32_t skip;
     int32_t feat_dim;
     int32_t has_transient;
+    int32_t xyz_encoding;
 } NefesGenericNetDesc;
 /* bytes of the packed blob; 0 for an unsupported description */
 size_t nefes_generic_blob_bytes(const NefesGenericNetDesc* desc);
 /* Host-side packing: `tensors` as for nefes_pack_weights with xyz_encoding_1..depth in front (2 * (depth + 4) pointers, 2 * (depth + 10)
  * with the transient head).  Blob = per layer (xyz_encoding_1..depth, final, static_sigma, dir_encoding, static_rgb [, transient_encoding
  * .0/.2/.4, transient rgb|sigma|beta as one 5-row layer]) three plain fp32 arrays back to back: wt[Kp][Mp] (transposed), wb[Mp][Kp],
- * bias[Mp]; Mp = outputs rounded up to 32, Kp = inputs with a 63-feature embedding padded to 64 and a 27-feature one to 32 (zeros). */
+ * bias[Mp]; Mp = outputs rounded up to 32, Kp = inputs with a 63-feature embedding padded to 64 and a 27-feature one to 32 (zeros).
+ * NEFES_XYZ_EXTERNAL32: the same tensor list with xyz_encoding_1.weight [W, 32] and the skip layer's [W, 32 + W]; the 32 features are
+ * not padded (Kp = 32 and 32 + W). */
 int nefes_generic_pack(const NefesGenericNetDesc* desc, const float* const* tensors, int n_tensors, void* blob, size_t blob_bytes);
 /* ReLU mask words of M samples: uint32 [tiles][words][64 lanes], tiles of 64 samples (32 above width 256); 0 = unsupported */
 size_t nefes_generic_mask_bytes(const NefesGenericNetDesc* desc, int64_t M);
-/* nefes_field_fwd's arguments and raw_t layout (no external encoding); masks nullable (needed by the backward). */
+/* nefes_field_fwd's arguments and raw_t layout (no external encoding: NEFES_E_UNSUPPORTED for a NEFES_XYZ_EXTERNAL32 description, here
+ * and in the three calls below that take positions); masks nullable (needed by the backward). */
 int nefes_field_fwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
                             const float* rays_d, const float* z, const float* pts, const float* viewdirs, float* raw_t,
                             uint32_t* masks, void* stream);
@@ -346,6 +352,16 @@ int nefes_field_fwd_generic(const NefesGenericNetDesc* desc, const void* packed,
 int nefes_field_bwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
                             const float* rays_d, const float* z, const float* pts, const float* viewdirs, const float* raw_t,
                             const float* g_raw_t, const uint32_t* masks, float* g_pts, float* g_viewdirs_s, void* stream);
+/* The same pair for a NEFES_XYZ_EXTERNAL32 description (NEFES_E_UNSUPPORTED for a NEFES_XYZ_FREQ10 one): the forward reads the caller's
+ * encoding xyz_enc [N*S, 32] (16-byte aligned) and no positions; the backward (mode NEFES_FIELD_FULL or NEFES_FIELD_STATIC) writes
+ * g_xyz_enc [N*S, 32] = d loss / d xyz_enc (16-byte aligned) and g_viewdirs_s [N*S, 3].  Same raw_t layout and mask words; the gather
+ * of a hash grid stays in nefes_hashgrid_fwd / _bwd_x / _bwd_table.  No train-mode instances: nefes_generic_train_rows is 0 and
+ * nefes_generic_train_row_offset NEFES_E_UNSUPPORTED for such a description. */
+int nefes_field_fwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* xyz_enc,
+                                const float* viewdirs, float* raw_t, uint32_t* masks, void* stream);
+int nefes_field_bwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* viewdirs,
+                                const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* g_xyz_enc, float* g_viewdirs_s,
+                                void* stream);
 /* The same scatter as nefes_generic_pack from DEVICE tensors (`tensors`: a host array of device pointers, same order and shapes) into
  * a device blob that was zeroed once: plain stores, the padding is never written.  One small launch per tensor pair. */
 int nefes_generic_pack_device(const NefesGenericNetDesc* desc, const float* const* tensors, int n_tensors, void* blob,

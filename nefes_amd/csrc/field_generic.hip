@@ -17,6 +17,11 @@
 // backward's transposed product leaves the gradient of a layer's output in exactly the accumulator that produced it, so it tests the
 // same bit -- no recomputation of the forward (which would double the backward's matrix work) and 1 bit per activation of traffic.
 //
+// External encoding (nefes_field_fwd_generic_ext / nefes_field_bwd_generic_ext, NEFES_XYZ_EXTERNAL32): a third inclusion of the two
+// bodies with GEN_ARGS::ext set.  The E region is the caller's 32 features per sample (a hash grid's, gathered by the launches of
+// hashgrid.hip) instead of the 63-feature frequency embedding: 32 rows, no padding row, Kp = 32 for layer 1 and 32 + W for the skip
+// layer; the backward stores d loss / d encoding where the other instances apply the embedding's chain rule.  No train instances.
+//
 // Train mode (nefes_field_fwd_train_generic / nefes_field_bwd_train_generic): the same two bodies with TRAIN set also copy, from the
 // LDS buffers they sit in anyway, every weight-gradient operand to the train-layout buffers of csrc/train.hip (layout.h
 // nefes_train_off): the forward the embeddings and every hidden layer's OUTPUT (after ReLU) to `acts`, the backward the gradient
@@ -32,6 +37,7 @@
 
 #define GEN_MAX_LAYERS 16
 #define GEN_E_ROWS 64      /* xyz embedding: 63 features + a zero row */
+#define GEN_X_ROWS 32      /* ... of a NEFES_XYZ_EXTERNAL32 network: the supplied features, unpadded */
 #define GEN_DV_ROWS 32     /* direction embedding: 27 features + zero rows */
 #define GEN_HEAD_ROWS 160  /* rgb + features: 3 + 141 rounded up to 32 */
 
@@ -79,6 +85,7 @@ struct GenLayout {
     long long total_floats;
     int mask_words;              // words per lane and tile
     int slot_off[12];            // first row block of hidden layer slot (L1..LD, DIR, T0, T1, T2) in a tile's mask words
+    int e_rows;                  // rows of the E region: GEN_E_ROWS or GEN_X_ROWS (host side only; it sits in the struct's tail padding)
 };
 
 static bool gen_desc_ok(const NefesGenericNetDesc* d) {
@@ -87,6 +94,7 @@ static bool gen_desc_ok(const NefesGenericNetDesc* d) {
     if (d->depth < 1 || d->depth > 8) return false;
     if (d->skip != -1 && (d->skip < 1 || d->skip >= d->depth)) return false;
     if (d->feat_dim < 1 || d->feat_dim > 141) return false;
+    if (d->xyz_encoding != NEFES_XYZ_FREQ10 && d->xyz_encoding != NEFES_XYZ_EXTERNAL32) return false;
     return d->has_transient == 0 || d->has_transient == 1;
 }
 
@@ -95,6 +103,7 @@ static int gen_layout(const NefesGenericNetDesc* d, GenLayout* g) {
     memset(g, 0, sizeof(*g));
     const int W = d->width, D = d->depth, H = W / 2;
     g->W = W; g->D = D; g->skip = d->skip; g->C = d->feat_dim; g->fine = d->has_transient;
+    const int ER = g->e_rows = d->xyz_encoding == NEFES_XYZ_EXTERNAL32 ? GEN_X_ROWS : GEN_E_ROWS;
     int n = 0;
     long long off = 0;
     auto add = [&](int M, int Kp) {
@@ -105,7 +114,7 @@ static int gen_layout(const NefesGenericNetDesc* d, GenLayout* g) {
         l.bias = off; off += l.Mp;
         return n++;
     };
-    for (int i = 0; i < D; ++i) add(W, i == 0 ? GEN_E_ROWS : (i == d->skip ? GEN_E_ROWS + W : W));
+    for (int i = 0; i < D; ++i) add(W, i == 0 ? ER : (i == d->skip ? ER + W : W));
     g->iFINAL = add(W, W);
     g->iSIGMA = add(1, W);
     g->iDIR = add(H, W + GEN_DV_ROWS);
@@ -147,10 +156,12 @@ __host__ __device__ static inline int gen_put_k(const GenPut& p, int c) { return
 template <class F>
 static void gen_for_each_put(const GenLayout& g, F f) {
     const int W = g.W, D = g.D, H = W / 2;
+    const bool ext = g.e_rows == GEN_X_ROWS;      // the supplied encoding: 32 source columns, 32 rows, nothing to pad
+    const int e_src = ext ? GEN_X_ROWS : 63, e_emb = ext ? 0 : 63, e_pad = ext ? 0 : GEN_E_ROWS;
     int t = 0;
     for (int i = 0; i < D; ++i, t += 2) {
-        if (i == 0) f(GenPut{i, 0, W, t, 63, 63, 0, GEN_E_ROWS});
-        else if (i == g.skip) f(GenPut{i, 0, W, t, 63 + W, 63, 0, GEN_E_ROWS});
+        if (i == 0) f(GenPut{i, 0, W, t, e_src, e_emb, 0, e_pad});
+        else if (i == g.skip) f(GenPut{i, 0, W, t, e_src + W, e_emb, 0, e_pad});
         else f(GenPut{i, 0, W, t, W, 0, 0, 0});
     }
     f(GenPut{g.iFINAL, 0, W, t, W, 0, 0, 0}); t += 2;
@@ -169,7 +180,7 @@ static void gen_for_each_put(const GenLayout& g, F f) {
 
 // tensors: (weight, bias) per layer: xyz_encoding_1..D, xyz_encoding_final, dir_encoding.0, static_sigma.0, static_rgb.0
 // [, transient_encoding.0/.2/.4, transient_sigma.0, transient_rgb.0, transient_beta.0]; torch layout [out, in], embeddings at their
-// full 63 / 27 features.
+// full 63 / 27 features (NEFES_XYZ_EXTERNAL32: 32 in the place of the 63).
 extern "C" int nefes_generic_pack(const NefesGenericNetDesc* desc, const float* const* tensors, int n_tensors, void* blob,
                                   size_t blob_bytes) {
     GenLayout g;
@@ -237,7 +248,7 @@ extern "C" int nefes_generic_pack_device(const NefesGenericNetDesc* desc, const 
 // network without that head) are empty; every block is a multiple of 32 rows.
 struct GenTrainMap { int off[NEFES_TB_END + 1]; };
 static int gen_train_map(const NefesGenericNetDesc* d, GenTrainMap* m) {
-    if (!gen_desc_ok(d)) return NEFES_E_UNSUPPORTED;
+    if (!gen_desc_ok(d) || d->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;      // (no train instances on a supplied encoding)
     const int W = d->width, Hp = (W / 2 + 31) / 32 * 32, fine = d->has_transient;
     int r = 0;
     for (int b = 0; b <= NEFES_TB_END; ++b) {
@@ -270,6 +281,7 @@ extern "C" int nefes_generic_train_row_offset(const NefesGenericNetDesc* desc, i
 // ---------------------------------------------------------------------------------------------------------------------------
 struct GenArgs {
     static constexpr bool train = false;
+    static constexpr bool ext = false;
     GenLayout g;
     const float* blob;
     const float *rays_o, *rays_d, *z, *pts, *viewdirs;
@@ -335,6 +347,31 @@ __device__ __forceinline__ float gen_coord(const GenArgs& a, long long m, int ax
     return add_rn(a.rays_o[n * 3 + axis], mul_rn(a.rays_d[n * 3 + axis], a.z[m]));
 }
 
+// The direction embedding alone, for the instances on a supplied encoding: the second half of gen_embed and the second half of the
+// frequency backward's last loop (gen_dir_grad).  Those two keep their own copies: calling these from them compiles to different
+// instructions in the inference and TRAIN kernels, whose code adding this family must not move (tools/kernels_identical.py).
+template <int NCB>
+__device__ __forceinline__ void gen_embed_dir(const GenArgs& a, long long m0, float* DV) {
+    constexpr int TS = 32 * NCB;
+    const int tid = threadIdx.x;
+    if (a.viewdirs) {
+        for (int i = tid; i < 3 * TS; i += 256) {
+            const int s = i % TS, axis = i / TS;
+            const long long m = m0 + s;
+            const float x = m < a.M ? a.viewdirs[(m / a.S) * 3 + axis] : 0.f;
+            uint32_t hi, lo;
+            turns_fixed(x, hi, lo);
+            DV[axis * TS + s] = x;
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t ph = phase_of(hi, lo, k);
+                DV[(3 + 6 * k + axis) * TS + s] = sin_phase(ph);
+                DV[(6 + 6 * k + axis) * TS + s] = sin_phase(ph + 0x40000000u);
+            }
+        }
+        for (int i = tid; i < 5 * TS; i += 256) DV[27 * TS + i] = 0.f;
+    }
+}
+
 // rows of the frequency embedding in the reference's order (nerfh_nff.py:252-270): x (3), then per octave sin (3), cos (3)
 template <int NCB>
 __device__ __forceinline__ void gen_embed(const GenArgs& a, long long m0, float* E, float* DV) {
@@ -368,6 +405,67 @@ __device__ __forceinline__ void gen_embed(const GenArgs& a, long long m0, float*
             }
         }
         for (int i = tid; i < 5 * TS; i += 256) DV[27 * TS + i] = 0.f;
+    }
+}
+
+// through the direction embedding: d sin(f x) = f cos(f x), d cos(f x) = -f sin(f x)
+template <int TS>
+__device__ __forceinline__ float gen_dir_grad(const GenArgs& a, long long m, int axis, int s, const float* gDV) {
+    const float x = a.viewdirs[(m / a.S) * 3 + axis];
+    uint32_t hi, lo;
+    turns_fixed(x, hi, lo);
+    float gx = gDV[axis * TS + s];
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t ph = phase_of(hi, lo, k);
+        const float f = (float)(1 << k);
+        gx += gDV[(3 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x40000000u));
+        gx += gDV[(6 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x80000000u));
+    }
+    return gx;
+}
+
+// ---- a supplied 32-feature encoding in the place of the position (NEFES_XYZ_EXTERNAL32) -------------------------------------------
+struct GenArgsExt : GenArgs {
+    static constexpr bool ext = true;
+    const float* xyz_enc;      // [M][32]
+    float* g_enc;              // [M][32], backward
+};
+
+// E[f][s] = xyz_enc[m0 + s][f], columns of samples >= M as zeros.  A sample's 128 bytes go to eight consecutive lanes as 16-byte
+// loads (a wave reads 1 KiB of consecutive memory); the transpose is four scalar LDS stores per lane (the eight lanes of a sample
+// share a bank: an 8-way conflict on 4 TS / 32 stores per thread of a kernel that then runs D + 3 matrix products).
+template <int NCB>
+__device__ __forceinline__ void gen_embed(const GenArgsExt& a, long long m0, float* E, float* DV) {
+    constexpr int TS = 32 * NCB;
+    for (int i = threadIdx.x; i < TS * (GEN_X_ROWS / 4); i += 256) {
+        const int s = i / (GEN_X_ROWS / 4), q = i % (GEN_X_ROWS / 4);
+        const long long m = m0 + s;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (m < a.M) v = *(const float4*)(a.xyz_enc + m * GEN_X_ROWS + 4 * q);
+        E[(4 * q + 0) * TS + s] = v.x;
+        E[(4 * q + 1) * TS + s] = v.y;
+        E[(4 * q + 2) * TS + s] = v.z;
+        E[(4 * q + 3) * TS + s] = v.w;
+    }
+    gen_embed_dir<NCB>(a, m0, DV);
+}
+
+// the backward's last step: g_enc[m][f] = gE[f][s] of the live samples (the same lane <-> address map), d loss / d viewdirs per sample
+template <int NCB>
+__device__ __forceinline__ void gen_input_grads_ext(const GenArgsExt& a, long long m0, const float* gE, const float* gDV) {
+    constexpr int TS = 32 * NCB;
+    for (int i = threadIdx.x; i < TS * (GEN_X_ROWS / 4); i += 256) {
+        const int s = i / (GEN_X_ROWS / 4), q = i % (GEN_X_ROWS / 4);
+        const long long m = m0 + s;
+        if (m >= a.M) continue;
+        *(float4*)(a.g_enc + m * GEN_X_ROWS + 4 * q) = make_float4(gE[(4 * q + 0) * TS + s], gE[(4 * q + 1) * TS + s],
+                                                                    gE[(4 * q + 2) * TS + s], gE[(4 * q + 3) * TS + s]);
+    }
+    for (int i = threadIdx.x; i < 3 * TS; i += 256) {
+        const int s = i % TS, axis = i / TS;
+        const long long m = m0 + s;
+        if (m >= a.M) continue;
+        a.g_vs[m * 3 + axis] = gen_dir_grad<TS>(a, m, axis, s, gDV);
     }
 }
 
@@ -425,9 +523,14 @@ __device__ __forceinline__ const GenTrain* gen_train_of(const Args& a) {
 #include "field_generic_fwd.inc"
 #undef GEN_KERNEL
 #undef GEN_ARGS
+#define GEN_KERNEL gen_fwd_ext_kernel
+#define GEN_ARGS GenArgsExt
+#include "field_generic_fwd.inc"
+#undef GEN_KERNEL
+#undef GEN_ARGS
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// backward to the inputs: mode FULL or STATIC.  TRAIN: also every layer's pre-activation gradient to `dacts`
+// backward to the inputs: mode FULL or STATIC.  TRAIN: also every layer's pre-activation gradient to `dacts`.  ext: to the encoding
 #define GEN_KERNEL gen_bwd_kernel
 #define GEN_ARGS GenArgs
 #include "field_generic_bwd.inc"
@@ -435,6 +538,11 @@ __device__ __forceinline__ const GenTrain* gen_train_of(const Args& a) {
 #undef GEN_ARGS
 #define GEN_KERNEL gen_bwd_train_kernel
 #define GEN_ARGS GenArgsTrain
+#include "field_generic_bwd.inc"
+#undef GEN_KERNEL
+#undef GEN_ARGS
+#define GEN_KERNEL gen_bwd_ext_kernel
+#define GEN_ARGS GenArgsExt
 #include "field_generic_bwd.inc"
 #undef GEN_KERNEL
 #undef GEN_ARGS
@@ -449,9 +557,11 @@ static int gen_launch(K k, const Args& a, size_t lds, long long n_tiles, hipStre
     return (int)hipGetLastError();
 }
 
-static int gen_fill(GenArgs& a, const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S) {
+static int gen_fill(GenArgs& a, const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                    int xyz_encoding = NEFES_XYZ_FREQ10) {
     int rc = gen_layout(desc, &a.g);
     if (rc) return rc;
+    if (desc->xyz_encoding != xyz_encoding) return NEFES_E_UNSUPPORTED;      // each entry point serves one encoding
     if (mode != NEFES_FIELD_SIGMA && mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
     if (mode == NEFES_FIELD_FULL && !desc->has_transient) return NEFES_E_BADARG;
     a.blob = (const float*)packed;
@@ -502,6 +612,48 @@ extern "C" int nefes_field_bwd_generic(const NefesGenericNetDesc* desc, const vo
     const long long n_tiles = (a.M + TS - 1) / TS;
     if (TS == 64) return gen_launch(gen_bwd_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
     return gen_launch(gen_bwd_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+}
+
+// ---- a supplied encoding -----------------------------------------------------------------------------------------------------------
+// (the E region is GEN_X_ROWS rows: the GEN_E_ROWS - GEN_X_ROWS rows it does not have are not requested)
+extern "C" int nefes_field_fwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                           const float* xyz_enc, const float* viewdirs, float* raw_t, uint32_t* masks, void* stream) {
+    if (!desc || !packed || !xyz_enc || !raw_t || N <= 0 || S <= 0) return NEFES_E_BADARG;
+    if (mode != NEFES_FIELD_SIGMA && !viewdirs) return NEFES_E_BADARG;
+    GenArgsExt a;
+    memset(&a, 0, sizeof(a));
+    int rc = gen_fill(a, desc, packed, mode, N, S, NEFES_XYZ_EXTERNAL32);
+    if (rc) return rc;
+    if ((uintptr_t)xyz_enc & 15) return NEFES_E_BADARG;
+    a.xyz_enc = xyz_enc;
+    a.viewdirs = mode == NEFES_FIELD_SIGMA ? nullptr : viewdirs;
+    a.raw_t = raw_t; a.masks = masks;
+    const int TS = gen_tile(a.g.W);
+    const size_t lds = (size_t)(GEN_X_ROWS + GEN_DV_ROWS + 2 * a.g.W) * TS * 4;
+    const long long n_tiles = (a.M + TS - 1) / TS;
+    if (TS == 64) return gen_launch(gen_fwd_ext_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_launch(gen_fwd_ext_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+}
+
+extern "C" int nefes_field_bwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                           const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
+                                           float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
+    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !g_xyz_enc || !g_viewdirs_s || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
+    if (mode == NEFES_FIELD_SIGMA) return NEFES_E_BADARG;
+    GenArgsExt a;
+    memset(&a, 0, sizeof(a));
+    int rc = gen_fill(a, desc, packed, mode, N, S, NEFES_XYZ_EXTERNAL32);
+    if (rc) return rc;
+    if ((uintptr_t)g_xyz_enc & 15) return NEFES_E_BADARG;
+    a.viewdirs = viewdirs;
+    a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
+    a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
+    const int TS = gen_tile(a.g.W);
+    const int RB = a.g.W > GEN_HEAD_ROWS ? a.g.W : GEN_HEAD_ROWS;
+    const size_t lds = (size_t)(GEN_X_ROWS + GEN_DV_ROWS + 2 * RB + 1) * TS * 4;
+    const long long n_tiles = (a.M + TS - 1) / TS;
+    if (TS == 64) return gen_launch(gen_bwd_ext_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_launch(gen_bwd_ext_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
 }
 
 // ---- train mode ------------------------------------------------------------------------------------------------------------------

@@ -1,16 +1,18 @@
-// The body of the generic backward kernel; field_generic.hip includes it twice: GEN_KERNEL / GEN_ARGS = gen_bwd_kernel / GenArgs (the
-// inference instance) and gen_bwd_train_kernel / GenArgsTrain (TRAIN: the same code plus the copies to the train buffer).
+// The body of the generic backward kernel; field_generic.hip includes it three times: GEN_KERNEL / GEN_ARGS = gen_bwd_kernel / GenArgs
+// (the inference instance), gen_bwd_train_kernel / GenArgsTrain (TRAIN: the same code plus the copies to the train buffer) and
+// gen_bwd_ext_kernel / GenArgsExt (a supplied 32-feature encoding: gE has ER = 32 rows and is stored as it is, no chain rule).
 template <int NCB>
 __global__ __launch_bounds__(256, 1) void GEN_KERNEL(GEN_ARGS a) {
     constexpr int TS = 32 * NCB;
     constexpr bool TRAIN = GEN_ARGS::train;
+    constexpr int ER = GEN_ARGS::ext ? GEN_X_ROWS : GEN_E_ROWS;      // rows of the E region
     const GenTrain* const tr = gen_train_of(a);
     extern __shared__ __attribute__((aligned(16))) float gen_smem[];
     const GenLayout& g = a.g;
     const int W = g.W, D = g.D, H = W / 2, C = g.C;
     const int RB = W > GEN_HEAD_ROWS ? W : GEN_HEAD_ROWS;
     float* gE = gen_smem;
-    float* gDV = gE + GEN_E_ROWS * TS;
+    float* gDV = gE + ER * TS;
     float* A = gDV + GEN_DV_ROWS * TS;
     float* B = A + RB * TS;
     float* dsig = B + RB * TS;
@@ -138,18 +140,22 @@ __global__ __launch_bounds__(256, 1) void GEN_KERNEL(GEN_ARGS a) {
     const bool have_skip = g.skip > 0 && g.skip < D;
     for (int i = D - 1; i >= 1; --i) {
         const GenLayer& l = g.L[i];
-        const int hoff = i == g.skip ? GEN_E_ROWS : 0;
+        const int hoff = i == g.skip ? ER : 0;
         gen_layer<NCB>(blob + l.wb + hoff, cur, W, nullptr, nullptr, 0, l.Kp, W, W / 32, nullptr, masked(oth, i - 1, W, nullptr));
         if (i == g.skip)
-            gen_layer<NCB>(blob + l.wb, cur, W, nullptr, nullptr, 0, l.Kp, GEN_E_ROWS, GEN_E_ROWS / 32, nullptr, plain(gE, GEN_E_ROWS, false));
+            gen_layer<NCB>(blob + l.wb, cur, W, nullptr, nullptr, 0, l.Kp, ER, ER / 32, nullptr, plain(gE, ER, false));
         float* t = cur; cur = oth; oth = t;
         __syncthreads();
         if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_L1 + i - 1, cur, W, W);
     }
     {
         const GenLayer& l = g.L[0];
-        gen_layer<NCB>(blob + l.wb, cur, W, nullptr, nullptr, 0, l.Kp, GEN_E_ROWS, GEN_E_ROWS / 32, nullptr, plain(gE, GEN_E_ROWS, have_skip));
+        gen_layer<NCB>(blob + l.wb, cur, W, nullptr, nullptr, 0, l.Kp, ER, ER / 32, nullptr, plain(gE, ER, have_skip));
         __syncthreads();
+    }
+    if constexpr (GEN_ARGS::ext) {
+        gen_input_grads_ext<NCB>(a, m0, gE, gDV);
+        return;
     }
     // through the embeddings: d sin(f x) = f cos(f x), d cos(f x) = -f sin(f x)
     for (int i = tid; i < 3 * TS; i += 256) {

@@ -1,15 +1,17 @@
-// The body of the generic forward kernel; field_generic.hip includes it twice: GEN_KERNEL / GEN_ARGS = gen_fwd_kernel / GenArgs (the
-// inference instance) and gen_fwd_train_kernel / GenArgsTrain (TRAIN: the same code plus the copies to the train buffer).
+// The body of the generic forward kernel; field_generic.hip includes it three times: GEN_KERNEL / GEN_ARGS = gen_fwd_kernel / GenArgs
+// (the inference instance), gen_fwd_train_kernel / GenArgsTrain (TRAIN: the same code plus the copies to the train buffer) and
+// gen_fwd_ext_kernel / GenArgsExt (a supplied 32-feature encoding in the E region: ER = 32 rows, gen_embed's other overload).
 template <int NCB>
 __global__ __launch_bounds__(256, 1) void GEN_KERNEL(GEN_ARGS a) {
     constexpr int TS = 32 * NCB;
     constexpr bool TRAIN = GEN_ARGS::train;
+    constexpr int ER = GEN_ARGS::ext ? GEN_X_ROWS : GEN_E_ROWS;      // rows of the E region
     const GenTrain* const tr = gen_train_of(a);
     extern __shared__ __attribute__((aligned(16))) float gen_smem[];
     const GenLayout& g = a.g;
     const int W = g.W, D = g.D, H = W / 2;
     float* E = gen_smem;
-    float* DV = E + GEN_E_ROWS * TS;
+    float* DV = E + ER * TS;
     float* X = DV + GEN_DV_ROWS * TS;
     float* Y = X + W * TS;
     const long long tile = blockIdx.x, m0 = tile * TS;
@@ -26,7 +28,7 @@ __global__ __launch_bounds__(256, 1) void GEN_KERNEL(GEN_ARGS a) {
     gen_embed<NCB>(a, m0, E, DV);
     __syncthreads();
     if constexpr (TRAIN) {
-        gen_train_store<TS>(*tr, m0, NEFES_TB_E, E, GEN_E_ROWS, GEN_E_ROWS);
+        gen_train_store<TS>(*tr, m0, NEFES_TB_E, E, ER, ER);
         gen_train_store<TS>(*tr, m0, NEFES_TB_DV, DV, GEN_DV_ROWS, GEN_DV_ROWS);
     }
 
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256, 1) void GEN_KERNEL(GEN_ARGS a) {
     float *cur = X, *oth = Y;
     {
         const GenLayer& l = g.L[0];
-        gen_layer<NCB>(blob + l.wt, E, GEN_E_ROWS, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, hidden(cur, 0));
+        gen_layer<NCB>(blob + l.wt, E, ER, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, hidden(cur, 0));
     }
     __syncthreads();
     // TRAIN: a layer's output is complete behind its barrier and its buffer is next written behind the following barrier: copy it out here
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(256, 1) void GEN_KERNEL(GEN_ARGS a) {
     for (int i = 1; i < D; ++i) {
         const GenLayer& l = g.L[i];
         if (i == g.skip)
-            gen_layer<NCB>(blob + l.wt, E, GEN_E_ROWS, blob + l.wt + (long long)GEN_E_ROWS * l.Mp, cur, W, l.Mp, l.Mp, W / 32,
+            gen_layer<NCB>(blob + l.wt, E, ER, blob + l.wt + (long long)ER * l.Mp, cur, W, l.Mp, l.Mp, W / 32,
                            blob + l.bias, hidden(oth, i));
         else
             gen_layer<NCB>(blob + l.wt, cur, W, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, hidden(oth, i));

@@ -262,6 +262,12 @@ class NeRFH_NFF(nn.Module):
         return (ops.generic_shape_ok(self.W, self.D, self.skips, self.W_features) and self.out_ch_size != 3
                 and self.in_channels_xyz in range(3, 64, 6) and self.in_channels_dir in range(3, 28, 6))
 
+    def _generic_ext_supported(self):
+        """The generic kernels' instances on a SUPPLIED 32-feature encoding (a hash grid in front: nefes_field_fwd_generic_ext) serve
+        this network: the shapes of _generic_supported with in_channels_xyz == 32.  Frozen weights only (render refuses the rest)."""
+        return (ops.generic_shape_ok(self.W, self.D, self.skips, self.W_features) and self.out_ch_size != 3
+                and self.in_channels_xyz == 32 and self.in_channels_dir in range(3, 28, 6))
+
     def _shape(self):
         return (f"D={self.D}, skips={self.skips}, W={self.W}, f_dim={self.W_features}, in_channels_xyz={self.in_channels_xyz}, "
                 f"in_channels_dir={self.in_channels_dir}")
@@ -269,7 +275,8 @@ class NeRFH_NFF(nn.Module):
     def packed_generic(self) -> ops.PackedGeneric:
         """The network packed for the generic kernels; cached and invalidated like packed(): packed on the host once, re-packed on the
         device when only the versions of a trainable network's parameters changed."""
-        if not self._generic_supported():
+        ext = self._generic_ext_supported()
+        if not ext and not self._generic_supported():
             raise RuntimeError(f"nefes_amd: no field kernel serves {self._shape()}.  Compiled: {ops.COMPILED_SET}")
         sd, prm, key = self._path_params(ops.PackedGeneric.layer_names(self.D, self.encode_transient))
         kernel_sd = lambda: self._kernel_params({n: p.detach() for n, p in sd.items()})
@@ -284,7 +291,8 @@ class NeRFH_NFF(nn.Module):
         elif self._pk_gen is None or key != old:
             dev = prm[0].device if prm[0].is_cuda else torch.device("cuda")
             skip = 4 if (4 in self.skips and self.D > 4) else -1
-            self._pk_gen = ops.PackedGeneric(kernel_sd(), self.W, self.D, skip, self.W_features, self.encode_transient, dev)
+            self._pk_gen = ops.PackedGeneric(kernel_sd(), self.W, self.D, skip, self.W_features, self.encode_transient, dev,
+                                             L.XYZ_EXTERNAL32 if ext else L.XYZ_FREQ10)
             self._pk_gen_key = key
         return self._pk_gen
 
@@ -300,7 +308,8 @@ class NeRFH_NFF(nn.Module):
 
     def require_frozen_for_generic(self, what):
         raise NotImplementedError(f"nefes_amd: {what} is not built for the generic field kernels ({self._shape()}); they serve frozen "
-                                  f"weights with the frequency embedding only.  Their train-mode instances are opt-in: set "
+                                  f"weights (behind an external / hash-grid encoding: frozen weights only, the table may train).  "
+                                  f"Their train-mode instances, on the frequency embedding, are opt-in: set "
                                   f"NEFES_GENERIC_TRAIN=1 (ops.GENERIC_TRAIN).  Tuned instances: {ops.COMPILED_SET}")
 
     def invalidate_packed(self):

@@ -20,7 +20,9 @@ class NefesNetDesc(C.Structure):
 
 
 class NefesGenericNetDesc(C.Structure):
-    _fields_ = [("width", C.c_int32), ("depth", C.c_int32), ("skip", C.c_int32), ("feat_dim", C.c_int32), ("has_transient", C.c_int32)]
+    # xyz_encoding is the last field: a description made of the first five values is XYZ_FREQ10 (0), what it always meant
+    _fields_ = [("width", C.c_int32), ("depth", C.c_int32), ("skip", C.c_int32), ("feat_dim", C.c_int32), ("has_transient", C.c_int32),
+                ("xyz_encoding", C.c_int32)]
 
 
 class NefesStreamInfo(C.Structure):
@@ -37,7 +39,7 @@ class NefesHashGridDesc(C.Structure):
                 ("base_resolution", C.c_int32), ("per_level_scale", C.c_float), ("bound", C.c_float)]
 
 
-ABI_VERSION = 19       # NEFES_ABI_VERSION of include/nefes_hip.h
+ABI_VERSION = 20       # NEFES_ABI_VERSION of include/nefes_hip.h
 STREAM_FWD_SIGMA, STREAM_FWD_STATIC, STREAM_FWD_FULL, STREAM_BWD_FULL, STREAM_FWD_SIGMA_X6, STREAM_FWD_FULL_X6, STREAM_BWD_FULL_X6, STREAM_BWD_STATIC = 0, 1, 2, 3, 4, 5, 6, 7
 STREAM_FWD_SIGMA_H3, STREAM_FWD_FULL_H3, STREAM_BWD_FULL_H3, STREAM_FWD_STATIC_H3, STREAM_BWD_STATIC_H3 = 8, 9, 10, 11, 12
 FIELD_SIGMA, FIELD_STATIC, FIELD_FULL = 0, 1, 2
@@ -121,6 +123,8 @@ SIGNATURES = {
     "nefes_generic_mask_bytes": (_sz, [_gdesc, C.c_int64]),
     "nefes_field_fwd_generic": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_field_bwd_generic": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_field_fwd_generic_ext": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "nefes_field_bwd_generic_ext": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_generic_pack_device": (_i, [_gdesc, C.POINTER(_p), _i, _p, _sz, _p]),
     "nefes_generic_train_rows": (_sz, [_gdesc]),
     "nefes_generic_train_row_offset": (_i, [_gdesc, _i]),
@@ -176,7 +180,8 @@ def load():
 COMPILED_SET = ("fp16 two-part instances (default): widths 128 / 256 x feature heads of 0..29 or 30..141 channels with the frequency "
                 "embedding, width 256 x 0..29 or 30..141 channels with an external 32-feature embedding (hash grid); bf16x6 and fp32-MFMA instances "
                 "(NEFES_SPLIT=x6 / f32): width 256 x 16 channels and width 128 x 128 channels only")
-GENERIC_SET = ("generic fp32-MFMA kernels (frequency embedding; frozen weights, or train mode with NEFES_GENERIC_TRAIN=1): any width that is "
+GENERIC_SET = ("generic fp32-MFMA kernels (frequency embedding: frozen weights, or train mode with NEFES_GENERIC_TRAIN=1; an external "
+               "32-feature embedding (hash grid): frozen weights only, the table may train): any width that is "
                "a multiple of 32 from 32 to 512, depth 1..8 with skips=[4] (or none when depth <= 4), feature heads of 1..141 channels")
 COMPILED_SET += ".  Other shapes (NeRFH_NFF.packed_generic): " + GENERIC_SET
 

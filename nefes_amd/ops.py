@@ -472,7 +472,11 @@ def field_route(pk, mode, backward=False, kind="rays", M=0, override=None):
 
     * hashgrid / zrow: fp16 two-part instances only, M below H3_MAX_SAMPLES; no static head.  Whether they serve the pack at all is
       the caller's question (hashgrid_fused_ok, fused_coarse_pass_ok) and is not asked again here.
-    * a generic pack (NeRFH_NFF.packed_generic): nefes_field_fwd_generic / nefes_field_bwd_generic, every mode, any M.
+    * a generic pack (NeRFH_NFF.packed_generic): nefes_field_fwd_generic / nefes_field_bwd_generic, every mode, any M -- on the
+      frequency embedding, for rays or points.  Packed for a supplied encoding (xyz_encoding == XYZ_EXTERNAL32) it takes kind "enc"
+      alone, on nefes_field_fwd_generic_ext / nefes_field_bwd_generic_ext (g_enc on the backward, FULL or STATIC).  Either pack with
+      a kind of the other one is refused, naming the shape; so is a pack for a supplied encoding with kind hashgrid / zrow (the callers
+      ask hashgrid_fused_ok / fused_coarse_pass_ok first, which say no: h3_valid is False).
     * forward, switches decide: the split route when USE_X6, SPLIT != "f32" and x6_supported(pk, mode) -- and, for POINTS input,
       only with the frequency embedding.  Otherwise the strict route.
     * forward, split route: fp16 two-part when h3_serves(pk) and M < H3_MAX_SAMPLES.  Otherwise the STATIC head falls to the strict
@@ -492,6 +496,11 @@ def field_route(pk, mode, backward=False, kind="rays", M=0, override=None):
     d = "bwd" if backward else "fwd"
     switched = USE_X6 and SPLIT != "f32"
     route = lambda entry, key, g_enc=False: Route(entry, key, entry, g_enc)
+    gen_ext = is_generic(pk) and pk.xyz_encoding == L.XYZ_EXTERNAL32
+    if is_generic(pk) and (kind == "enc") != gen_ext:
+        raise RuntimeError(f"nefes_amd: the generic field kernels of W={pk.width}, D={pk.depth}, f_dim={pk.feat_dim} were packed for "
+                           f"{'a supplied 32-feature encoding' if gen_ext else 'the frequency embedding'} (xyz_encoding={pk.xyz_encoding}) "
+                           f"and cannot take input of kind '{kind}'")
     if kind in ("hashgrid", "zrow"):
         if M >= H3_MAX_SAMPLES:
             raise RuntimeError("nefes_amd: too many samples for one launch of the fp16 two-part kernels (32-bit sample index)")
@@ -503,6 +512,8 @@ def field_route(pk, mode, backward=False, kind="rays", M=0, override=None):
             raise NotImplementedError("nefes_amd: the hash-grid field kernels evaluate the sigma-only or the full head")
         return route("nefes_field_fwd_h3_hashgrid", f"field_fwd[{name},h3,hashgrid]")
     if is_generic(pk):
+        if gen_ext:
+            return route(f"nefes_field_{d}_generic_ext", f"field_{d}[{name},generic,ext]", backward)
         return route(f"nefes_field_{d}_generic", f"field_{d}[{name},generic]")
     fold = getattr(pk, "fold", False)
     if not backward:
@@ -577,6 +588,8 @@ def _field_fwd(pk, mode, N, S, rays_o=None, rays_d=None, z=None, pts=None, xyz_e
     o, d, zz, v = _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs")
     if rt.entry == "nefes_field_fwd_generic":
         args = (mode, N, S, o, d, zz, _chk(pts, "pts"), v)
+    elif rt.entry == "nefes_field_fwd_generic_ext":
+        args = (mode, N, S, _chk(xyz_enc, "xyz_enc"), v)
     elif rt.entry == "nefes_field_fwd_h3_hashgrid":
         args = (grid.desc, _chk(grid.table, "table"), mode, N, S, o, d, zz, 1 if z.dim() == 1 else 0, v)
     elif rt.entry == "nefes_field_fwd_h3_zrow":
@@ -590,16 +603,18 @@ def _field_fwd(pk, mode, N, S, rays_o=None, rays_d=None, z=None, pts=None, xyz_e
     return raw_t, masks
 
 
-def _field_bwd(pk, mode, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, grid=None):
+def _field_bwd(pk, mode, N, S, raw_t, g_raw_t, masks, rays_o=None, rays_d=None, z=None, pts=None, viewdirs=None, grid=None, enc=False):
     """THE backward launcher: the kernel field_route names -> (d loss / d pts [N*S,3] -- or d loss / d encoding [N*S,32] for a pack on
-    an external encoding --, d loss / d viewdirs per sample [N*S,3])."""
-    rt = field_route(pk, mode, True, _input_kind(z, pts, None, grid), N * S)
+    an external encoding --, d loss / d viewdirs per sample [N*S,3]).  enc: the forward's input was a supplied encoding."""
+    rt = field_route(pk, mode, True, _input_kind(z, pts, True if enc else None, grid), N * S)
     dev = pk.blob.device
     g_in, g_vs = torch.empty(N * S, 32 if rt.g_enc else 3, device=dev), torch.empty(N * S, 3, device=dev)
     o, d, zz, v = _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(z, "z"), _chk(viewdirs, "viewdirs")
     out = (_chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"), _chk(masks, "masks", torch.int32))
     if rt.entry == "nefes_field_bwd_generic":
         args = (mode, N, S, o, d, zz, _chk(pts, "pts"), v, *out, _chk(g_in, "g_pts"))
+    elif rt.entry == "nefes_field_bwd_generic_ext":
+        args = (mode, N, S, v, *out, _chk(g_in, "g_enc"))
     elif rt.entry == "nefes_field_bwd_h3_hashgrid":
         args = (grid.desc, _chk(grid.table, "table"), N, S, o, d, zz, v, *out, _chk(g_in, "g_pts"))
     elif rt.entry.startswith("nefes_field_bwd_static"):       # nefes_field_bwd_static, nefes_field_bwd_static_h3
@@ -867,7 +882,6 @@ class PackedGeneric:
 
     generic = True
     h3_valid = False             # (never on the fp16 two-part instances: fused_coarse_pass_ok and friends say no)
-    xyz_encoding = L.XYZ_FREQ10
 
     @staticmethod
     def layer_names(depth, has_transient):
@@ -876,14 +890,16 @@ class PackedGeneric:
             names += PackedField.LAYERS_FINE[len(PackedField.LAYERS_COARSE):]
         return names
 
-    def __init__(self, state_dict, width, depth, skip, feat_dim, has_transient, device):
+    def __init__(self, state_dict, width, depth, skip, feat_dim, has_transient, device, xyz_encoding=L.XYZ_FREQ10):
         lib = L.load()
-        self.desc = L.NefesGenericNetDesc(int(width), int(depth), int(skip), int(feat_dim), 1 if has_transient else 0)
+        self.desc = L.NefesGenericNetDesc(int(width), int(depth), int(skip), int(feat_dim), 1 if has_transient else 0, int(xyz_encoding))
+        self.xyz_encoding = int(xyz_encoding)      # XYZ_EXTERNAL32: xyz_encoding_1 / the skip layer take 32 supplied features, unpadded
         self.width, self.depth, self.skip = int(width), int(depth), int(skip)
         self.feat_dim, self.has_transient = int(feat_dim), bool(has_transient)
         n = int(lib.nefes_generic_blob_bytes(self.desc))
         if n == 0:
-            raise RuntimeError(f"nefes_amd: no field kernel serves W={width}, D={depth}, skip={skip}, f_dim={feat_dim}.  "
+            raise RuntimeError(f"nefes_amd: no field kernel serves W={width}, D={depth}, skip={skip}, f_dim={feat_dim}, "
+                               f"xyz_encoding={xyz_encoding}.  "
                                f"Compiled: {COMPILED_SET}")
         host = []
         for name in self.layer_names(self.depth, self.has_transient):
@@ -919,6 +935,8 @@ class PackedGeneric:
 
     def train_rows(self):
         """(rows per tile, first row of block L.TB_*) of the train-mode acts / dacts buffers (nefes_generic_train_row_offset)."""
+        if self.xyz_encoding != L.XYZ_FREQ10:
+            raise RuntimeError("nefes_amd: the generic kernels have no train-mode instances on a supplied encoding")
         lib = L.load()
         return int(lib.nefes_generic_train_rows(self.desc)), [int(lib.nefes_generic_train_row_offset(self.desc, b)) for b in range(L.TB_END + 1)]
 
@@ -937,16 +955,18 @@ def field_from_points(pts, viewdirs, pk, mode):
 
 class FieldFromEncoding(torch.autograd.Function):
     """Field MLP on a caller-supplied 32-feature xyz embedding (hash grid, BASELINE config 4): enc [N,S,32], viewdirs [N,3]
-    -> raw_t [N,R,S]; backward to enc and viewdirs."""
+    -> raw_t [N,R,S]; backward to enc and viewdirs: FULL mode on a tuned pack, FULL and STATIC on a generic one (packed_generic of a
+    network with in_channels_xyz=32: any width / depth)."""
 
     @staticmethod
     def forward(ctx, enc, viewdirs, pk, mode):
         enc = _f32(enc)
         N, S = enc.shape[0], enc.shape[1]
         viewdirs = torch.zeros(N, 3, device=enc.device) if viewdirs is None else _f32(viewdirs)
-        need = mode == L.FIELD_FULL and any(ctx.needs_input_grad[:2])
+        # (the generic backward has a STATIC mode -- a coarse network with test_time False --, the tuned instances on an encoding do not)
+        need = (mode == L.FIELD_FULL or (mode == L.FIELD_STATIC and is_generic(pk))) and any(ctx.needs_input_grad[:2])
         raw_t, masks = _field_fwd(pk, mode, N, S, xyz_enc=enc.reshape(-1, 32), viewdirs=viewdirs, want_masks=need)
-        ctx.pk, ctx.have, ctx.pk_gen = pk, need, pk.generation
+        ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
         if need:
             ctx.save_for_backward(viewdirs, raw_t, masks)
             ctx.shape = (N, S)
@@ -959,7 +979,7 @@ class FieldFromEncoding(torch.autograd.Function):
         viewdirs, raw_t, masks = ctx.saved_tensors
         N, S = ctx.shape
         ctx.pk.check_generation(ctx.pk_gen)
-        g_enc, g_vs = _field_bwd(ctx.pk, L.FIELD_FULL, N, S, raw_t, _f32(g_raw_t), masks, viewdirs=viewdirs)
+        g_enc, g_vs = _field_bwd(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, viewdirs=viewdirs, enc=True)
         zeros = torch.zeros(N, S, device=raw_t.device)
         _, _, g_v = ray_grad_reduce(N, S, zeros, g_vs, g_vs)
         return g_enc.reshape(N, S, 32), g_v, None, None

@@ -113,9 +113,7 @@ def _field(pk, mode, rays_o, rays_d, viewdirs, z, xyz_encoder):
     """raw_t [N,R,S] for samples z along the rays; differentiable w.r.t. rays_o, rays_d, viewdirs in FULL mode."""
     if xyz_encoder is None:
         return ops.field_from_rays(rays_o, rays_d, viewdirs, z, pk, mode)
-    if ops.is_generic(pk):
-        raise NotImplementedError(f"nefes_amd: an external / hash-grid encoding is not built for the generic field kernels "
-                                  f"(W={pk.width}, D={pk.depth}, f_dim={pk.feat_dim})")
+    # (a generic pack -- any width / depth -- falls through to the separate launches: hashgrid_fused_ok is False for it)
     if (mode != L.FIELD_STATIC and ops.hashgrid_fused_ok(pk, xyz_encoder) and z.shape[0] * z.shape[1] < ops.H3_MAX_SAMPLES
             and not _grid_trainable(xyz_encoder)):
         # (a trainable table takes the separate launches below: they hand HashGridEncode the gradient of the encoding)
@@ -139,7 +137,8 @@ def _render_core(rays_o, rays_d, viewdirs, near, far, network_fn, network_fine, 
     def field(net, pk, mode, z_):
         # a trainable hash-grid table behind a frozen network: the static head (coarse pass, test_time False) has no backward on the
         # inference instances, so it runs on the train-mode ones too (without the weight gradients); the full head does (_field)
-        grid_static = mode == L.FIELD_STATIC and _grid_trainable(cfg.xyz_encoder)
+        # (the generic kernels' backward has the static head: such a pack stays on _field)
+        grid_static = mode == L.FIELD_STATIC and _grid_trainable(cfg.xyz_encoder) and not ops.is_generic(pk)
         if (trainable(net) or grid_static) and mode != L.FIELD_SIGMA:
             from . import train as T
             if ops.is_generic(pk):
