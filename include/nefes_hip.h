@@ -420,15 +420,18 @@ int nefes_field_fwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, i
 int nefes_field_bwd_train_h3_ext(const NefesNetDesc* desc, const void* packed, int mode, int N, int S, const float* viewdirs,
                                  const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* dacts, float* g_xyz_enc,
                                  float* g_viewdirs_s, void* stream);
-/* d raw_t [N][R][S] -> head pre-activation gradients in dacts blocks RGB, SIG (, TH); samples beyond N*S are zeroed. */
+/* d raw_t [N][R][S] -> head pre-activation gradients in dacts blocks RGB, SIG (, TH); samples beyond N*S and the padding rows of
+ * every block it writes (all tiles of the RGB block as nefes_train_row_offset lays it out) are zeroed. */
 int nefes_train_head_grad(const NefesNetDesc* desc, int mode, int N, int S, const float* raw_t, const float* g_raw_t,
                           float* dacts, void* stream);
 /* dacts_out[dst_row0 + i][s] (+)= sum_{o < n_out} wt[i][o] * dacts_in[g_row0 + o][s],  i < n_in (64, 128 or 256);
- * wt = TRANSPOSED weights [n_in][ldw] (n_out % 8 == 0, zero padded); mask: multiply by [acts[dst_row0 + i][s] > 0]. */
+ * wt = TRANSPOSED weights [n_in][ldw] (n_out % 8 == 0, zero padded); mask: multiply by [acts[dst_row0 + i][s] > 0].
+ * NEFES_E_BADARG unless both row ranges lie inside the tile (g_row0 + n_out <= rows, dst_row0 + n_in <= rows). */
 int nefes_train_dx(int64_t n_tiles, int rows, const float* dacts_in, int g_row0, int n_out, const float* wt, int ldw,
                    int n_in, const float* acts, int dst_row0, int accumulate, int mask, float* dacts_out, void* stream);
 /* partial[sp][o][i] = sum over the sp-th share of the sample tiles of dacts[g_row0 + o][s] * f(acts[x_row0 + i][s]),
- * f = ReLU if x_relu else identity; n_out, n_in multiples of 32; the caller sums the `splits` partials. */
+ * f = ReLU if x_relu else identity; n_out, n_in multiples of 32; the caller sums the `splits` partials.  The kernels address whole
+ * 32-row blocks: NEFES_E_BADARG unless g_row0, x_row0 and rows are multiples of 32 and g_row0 + n_out <= rows, x_row0 + n_in <= rows. */
 int nefes_train_dw(int64_t n_tiles, int rows, const float* dacts, int g_row0, int n_out, const float* acts, int x_row0,
                    int n_in, int x_relu, int splits, float* partial, void* stream);
 /* The same with the bias gradient riding along: partial[sp][o][n_in + 1], column n_in = sum over the share's samples of
