@@ -355,8 +355,9 @@ int nefes_field_bwd_generic(const NefesGenericNetDesc* desc, const void* packed,
 /* The same pair for a NEFES_XYZ_EXTERNAL32 description (NEFES_E_UNSUPPORTED for a NEFES_XYZ_FREQ10 one): the forward reads the caller's
  * encoding xyz_enc [N*S, 32] (16-byte aligned) and no positions; the backward (mode NEFES_FIELD_FULL or NEFES_FIELD_STATIC) writes
  * g_xyz_enc [N*S, 32] = d loss / d xyz_enc (16-byte aligned) and g_viewdirs_s [N*S, 3].  Same raw_t layout and mask words; the gather
- * of a hash grid stays in nefes_hashgrid_fwd / _bwd_x / _bwd_table.  No train-mode instances: nefes_generic_train_rows is 0 and
- * nefes_generic_train_row_offset NEFES_E_UNSUPPORTED for such a description. */
+ * of a hash grid stays in nefes_hashgrid_fwd / _bwd_x / _bwd_table.  Train mode: the _train_generic_ext pair and its own row map
+ * (nefes_generic_train_rows_ext) below; nefes_generic_train_rows is 0 and nefes_generic_train_row_offset NEFES_E_UNSUPPORTED for such
+ * a description. */
 int nefes_field_fwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* xyz_enc,
                                 const float* viewdirs, float* raw_t, uint32_t* masks, void* stream);
 int nefes_field_bwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* viewdirs,
@@ -382,6 +383,18 @@ int nefes_field_fwd_train_generic(const NefesGenericNetDesc* desc, const void* p
 int nefes_field_bwd_train_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* rays_o,
                                   const float* rays_d, const float* z, const float* viewdirs, const float* raw_t, const float* g_raw_t,
                                   const uint32_t* masks, float* dacts, float* g_pts, float* g_viewdirs_s, void* stream);
+/* Train mode for a NEFES_XYZ_EXTERNAL32 description (a hash grid in front; 0 / NEFES_E_UNSUPPORTED for a NEFES_XYZ_FREQ10 one).  The row
+ * map is the one above with E = the 32 supplied features in natural order: blocks up to E start where they do there, every later block
+ * 32 rows earlier.  The calls take the arguments of the _ext pair plus `acts` / `dacts` (16-byte aligned, like xyz_enc / g_xyz_enc);
+ * mode NEFES_FIELD_STATIC or NEFES_FIELD_FULL.  The backward also writes g_xyz_enc [N*S, 32] (feed nefes_hashgrid_bwd_table / _bwd_x)
+ * and g_viewdirs_s [N*S, 3]. */
+size_t nefes_generic_train_rows_ext(const NefesGenericNetDesc* desc);
+int nefes_generic_train_row_offset_ext(const NefesGenericNetDesc* desc, int block);
+int nefes_field_fwd_train_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, const float* xyz_enc,
+                                      const float* viewdirs, float* raw_t, float* acts, uint32_t* masks, void* stream);
+int nefes_field_bwd_train_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                      const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
+                                      float* dacts, float* g_xyz_enc, float* g_viewdirs_s, void* stream);
 
 /* ---- train mode: weight gradients (script/run_nefes.py:42-108 `loss.backward()` through models/nerfh_nff.py:525-576) ----
  * Buffers `acts` / `dacts`: fp32 [n_tiles = ceil(N*S/128)][rows x 128 samples], rows = nefes_train_rows(desc); inside a tile

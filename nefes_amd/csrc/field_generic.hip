@@ -20,13 +20,17 @@
 // External encoding (nefes_field_fwd_generic_ext / nefes_field_bwd_generic_ext, NEFES_XYZ_EXTERNAL32): a third inclusion of the two
 // bodies with GEN_ARGS::ext set.  The E region is the caller's 32 features per sample (a hash grid's, gathered by the launches of
 // hashgrid.hip) instead of the 63-feature frequency embedding: 32 rows, no padding row, Kp = 32 for layer 1 and 32 + W for the skip
-// layer; the backward stores d loss / d encoding where the other instances apply the embedding's chain rule.  No train instances.
+// layer; the backward stores d loss / d encoding where the other instances apply the embedding's chain rule.
 //
 // Train mode (nefes_field_fwd_train_generic / nefes_field_bwd_train_generic): the same two bodies with TRAIN set also copy, from the
 // LDS buffers they sit in anyway, every weight-gradient operand to the train-layout buffers of csrc/train.hip (layout.h
 // nefes_train_off): the forward the embeddings and every hidden layer's OUTPUT (after ReLU) to `acts`, the backward the gradient
 // with respect to every layer's pre-activation to `dacts`.  nefes_train_dw_bias then forms dW = G X^T unchanged; the block ->
-// first-row map is gen_train_rows (nefes_generic_train_row_offset).
+// first-row map is gen_train_map (nefes_generic_train_row_offset).
+//
+// Train mode on a supplied encoding (nefes_field_fwd_train_generic_ext / nefes_field_bwd_train_generic_ext): the fourth inclusion,
+// TRAIN and ext both set.  The E block of `acts` is the caller's 32 features in natural order, so every later block starts 32 rows
+// earlier than on the frequency map (nefes_generic_train_row_offset_ext).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -246,14 +250,15 @@ extern "C" int nefes_generic_pack_device(const NefesGenericNetDesc* desc, const 
 // ---- train-mode row map: first row of block NEFES_TB_* (layout.h: E, DV, L1..L8, FINAL, DIR, T0..T2, RGB, SIG, TH, END) in a tile of
 // the `acts` / `dacts` buffers of this network.  Blocks the network does not have (layers above its depth, the transient blocks of a
 // network without that head) are empty; every block is a multiple of 32 rows.
+// The E block is the kernels' E region: GEN_E_ROWS of the frequency embedding, GEN_X_ROWS of a supplied encoding.
 struct GenTrainMap { int off[NEFES_TB_END + 1]; };
-static int gen_train_map(const NefesGenericNetDesc* d, GenTrainMap* m) {
-    if (!gen_desc_ok(d) || d->xyz_encoding != NEFES_XYZ_FREQ10) return NEFES_E_UNSUPPORTED;      // (no train instances on a supplied encoding)
+static int gen_train_map(const NefesGenericNetDesc* d, int xyz_encoding, GenTrainMap* m) {
+    if (!gen_desc_ok(d) || d->xyz_encoding != xyz_encoding) return NEFES_E_UNSUPPORTED;      // each entry point serves one encoding
     const int W = d->width, Hp = (W / 2 + 31) / 32 * 32, fine = d->has_transient;
     int r = 0;
     for (int b = 0; b <= NEFES_TB_END; ++b) {
         m->off[b] = r;
-        if (b == NEFES_TB_E) r += GEN_E_ROWS;
+        if (b == NEFES_TB_E) r += xyz_encoding == NEFES_XYZ_EXTERNAL32 ? GEN_X_ROWS : GEN_E_ROWS;
         else if (b == NEFES_TB_DV) r += GEN_DV_ROWS;
         else if (b >= NEFES_TB_L1 && b < NEFES_TB_FINAL) r += b - NEFES_TB_L1 < d->depth ? W : 0;
         else if (b == NEFES_TB_FINAL) r += W;
@@ -266,16 +271,25 @@ static int gen_train_map(const NefesGenericNetDesc* d, GenTrainMap* m) {
     return 0;
 }
 
-extern "C" size_t nefes_generic_train_rows(const NefesGenericNetDesc* desc) {
+static size_t gen_train_rows(const NefesGenericNetDesc* desc, int xyz_encoding) {
     GenTrainMap m;
-    return gen_train_map(desc, &m) ? 0 : (size_t)m.off[NEFES_TB_END];
+    return gen_train_map(desc, xyz_encoding, &m) ? 0 : (size_t)m.off[NEFES_TB_END];
 }
 
-extern "C" int nefes_generic_train_row_offset(const NefesGenericNetDesc* desc, int block) {
+static int gen_train_row_offset(const NefesGenericNetDesc* desc, int xyz_encoding, int block) {
     GenTrainMap m;
     if (block < 0 || block > NEFES_TB_END) return NEFES_E_BADARG;
-    const int rc = gen_train_map(desc, &m);
+    const int rc = gen_train_map(desc, xyz_encoding, &m);
     return rc ? rc : m.off[block];
+}
+
+extern "C" size_t nefes_generic_train_rows(const NefesGenericNetDesc* desc) { return gen_train_rows(desc, NEFES_XYZ_FREQ10); }
+extern "C" int nefes_generic_train_row_offset(const NefesGenericNetDesc* desc, int block) {
+    return gen_train_row_offset(desc, NEFES_XYZ_FREQ10, block);
+}
+extern "C" size_t nefes_generic_train_rows_ext(const NefesGenericNetDesc* desc) { return gen_train_rows(desc, NEFES_XYZ_EXTERNAL32); }
+extern "C" int nefes_generic_train_row_offset_ext(const NefesGenericNetDesc* desc, int block) {
+    return gen_train_row_offset(desc, NEFES_XYZ_EXTERNAL32, block);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -507,6 +521,10 @@ struct GenArgsTrain : GenArgs {
     static constexpr bool train = true;
     GenTrain t;
 };
+struct GenArgsExtTrain : GenArgsExt {
+    static constexpr bool train = true;
+    GenTrain t;
+};
 template <class Args>
 __device__ __forceinline__ const GenTrain* gen_train_of(const Args& a) {
     if constexpr (Args::train) return &a.t;
@@ -528,6 +546,11 @@ __device__ __forceinline__ const GenTrain* gen_train_of(const Args& a) {
 #include "field_generic_fwd.inc"
 #undef GEN_KERNEL
 #undef GEN_ARGS
+#define GEN_KERNEL gen_fwd_ext_train_kernel
+#define GEN_ARGS GenArgsExtTrain
+#include "field_generic_fwd.inc"
+#undef GEN_KERNEL
+#undef GEN_ARGS
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // backward to the inputs: mode FULL or STATIC.  TRAIN: also every layer's pre-activation gradient to `dacts`.  ext: to the encoding
@@ -543,6 +566,11 @@ __device__ __forceinline__ const GenTrain* gen_train_of(const Args& a) {
 #undef GEN_ARGS
 #define GEN_KERNEL gen_bwd_ext_kernel
 #define GEN_ARGS GenArgsExt
+#include "field_generic_bwd.inc"
+#undef GEN_KERNEL
+#undef GEN_ARGS
+#define GEN_KERNEL gen_bwd_ext_train_kernel
+#define GEN_ARGS GenArgsExtTrain
 #include "field_generic_bwd.inc"
 #undef GEN_KERNEL
 #undef GEN_ARGS
@@ -657,9 +685,9 @@ extern "C" int nefes_field_bwd_generic_ext(const NefesGenericNetDesc* desc, cons
 }
 
 // ---- train mode ------------------------------------------------------------------------------------------------------------------
-static int gen_fill_train(GenTrain& t, const NefesGenericNetDesc* desc, float* buf) {
+static int gen_fill_train(GenTrain& t, const NefesGenericNetDesc* desc, float* buf, int xyz_encoding = NEFES_XYZ_FREQ10) {
     t.buf = buf;
-    const int rc = gen_train_map(desc, &t.map);
+    const int rc = gen_train_map(desc, xyz_encoding, &t.map);
     t.rows = t.map.off[NEFES_TB_END];
     return rc;
 }
@@ -712,4 +740,50 @@ extern "C" int nefes_field_bwd_train_generic(const NefesGenericNetDesc* desc, co
     const long long n_tiles = gen_train_tiles(a.M, TS);
     if (TS == 64) return gen_launch(gen_bwd_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
     return gen_launch(gen_bwd_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+}
+
+// ---- train mode on a supplied encoding: the checks of the _ext pair, the buffers and the launch of the train pair ------------------
+extern "C" int nefes_field_fwd_train_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                                 const float* xyz_enc, const float* viewdirs, float* raw_t, float* acts, uint32_t* masks,
+                                                 void* stream) {
+    if (!desc || !packed || !xyz_enc || !raw_t || !acts || !masks || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
+    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
+    GenArgsExtTrain a;
+    memset(&a, 0, sizeof(a));
+    int rc = gen_fill(a, desc, packed, mode, N, S, NEFES_XYZ_EXTERNAL32);
+    if (rc) return rc;
+    rc = gen_fill_train(a.t, desc, acts, NEFES_XYZ_EXTERNAL32);
+    if (rc) return rc;
+    if (((uintptr_t)xyz_enc | (uintptr_t)acts) & 15) return NEFES_E_BADARG;
+    a.xyz_enc = xyz_enc; a.viewdirs = viewdirs;
+    a.raw_t = raw_t; a.masks = masks;
+    const int TS = gen_tile(a.g.W);
+    const size_t lds = (size_t)(GEN_X_ROWS + GEN_DV_ROWS + 2 * a.g.W) * TS * 4;
+    const long long n_tiles = gen_train_tiles(a.M, TS);
+    if (TS == 64) return gen_launch(gen_fwd_ext_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_launch(gen_fwd_ext_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+}
+
+extern "C" int nefes_field_bwd_train_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                                 const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
+                                                 float* dacts, float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
+    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !dacts || !g_xyz_enc || !g_viewdirs_s || !viewdirs || N <= 0 || S <= 0)
+        return NEFES_E_BADARG;
+    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
+    GenArgsExtTrain a;
+    memset(&a, 0, sizeof(a));
+    int rc = gen_fill(a, desc, packed, mode, N, S, NEFES_XYZ_EXTERNAL32);
+    if (rc) return rc;
+    rc = gen_fill_train(a.t, desc, dacts, NEFES_XYZ_EXTERNAL32);
+    if (rc) return rc;
+    if (((uintptr_t)g_xyz_enc | (uintptr_t)dacts) & 15) return NEFES_E_BADARG;
+    a.viewdirs = viewdirs;
+    a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
+    a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
+    const int TS = gen_tile(a.g.W);
+    const int RB = a.g.W > GEN_HEAD_ROWS ? a.g.W : GEN_HEAD_ROWS;
+    const size_t lds = (size_t)(GEN_X_ROWS + GEN_DV_ROWS + 2 * RB + 1) * TS * 4;
+    const long long n_tiles = gen_train_tiles(a.M, TS);
+    if (TS == 64) return gen_launch(gen_bwd_ext_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_launch(gen_bwd_ext_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
 }

@@ -1,6 +1,7 @@
-// The body of the generic backward kernel; field_generic.hip includes it three times: GEN_KERNEL / GEN_ARGS = gen_bwd_kernel / GenArgs
-// (the inference instance), gen_bwd_train_kernel / GenArgsTrain (TRAIN: the same code plus the copies to the train buffer) and
-// gen_bwd_ext_kernel / GenArgsExt (a supplied 32-feature encoding: gE has ER = 32 rows and is stored as it is, no chain rule).
+// The body of the generic backward kernel; field_generic.hip includes it four times: GEN_KERNEL / GEN_ARGS = gen_bwd_kernel / GenArgs
+// (the inference instance), gen_bwd_train_kernel / GenArgsTrain (TRAIN: the same code plus the copies to the train buffer),
+// gen_bwd_ext_kernel / GenArgsExt (a supplied 32-feature encoding: gE has ER = 32 rows and is stored as it is, no chain rule) and
+// gen_bwd_ext_train_kernel / GenArgsExtTrain (both).
 template <int NCB>
 __global__ __launch_bounds__(256, 1) void GEN_KERNEL(GEN_ARGS a) {
     constexpr int TS = 32 * NCB;

@@ -1,6 +1,7 @@
-// The body of the generic forward kernel; field_generic.hip includes it three times: GEN_KERNEL / GEN_ARGS = gen_fwd_kernel / GenArgs
-// (the inference instance), gen_fwd_train_kernel / GenArgsTrain (TRAIN: the same code plus the copies to the train buffer) and
-// gen_fwd_ext_kernel / GenArgsExt (a supplied 32-feature encoding in the E region: ER = 32 rows, gen_embed's other overload).
+// The body of the generic forward kernel; field_generic.hip includes it four times: GEN_KERNEL / GEN_ARGS = gen_fwd_kernel / GenArgs
+// (the inference instance), gen_fwd_train_kernel / GenArgsTrain (TRAIN: the same code plus the copies to the train buffer),
+// gen_fwd_ext_kernel / GenArgsExt (a supplied 32-feature encoding in the E region: ER = 32 rows, gen_embed's other overload) and
+// gen_fwd_ext_train_kernel / GenArgsExtTrain (both: the E block of the train buffer is those 32 rows).
 template <int NCB>
 __global__ __launch_bounds__(256, 1) void GEN_KERNEL(GEN_ARGS a) {
     constexpr int TS = 32 * NCB;

@@ -264,7 +264,8 @@ class NeRFH_NFF(nn.Module):
 
     def _generic_ext_supported(self):
         """The generic kernels' instances on a SUPPLIED 32-feature encoding (a hash grid in front: nefes_field_fwd_generic_ext) serve
-        this network: the shapes of _generic_supported with in_channels_xyz == 32.  Frozen weights only (render refuses the rest)."""
+        this network: the shapes of _generic_supported with in_channels_xyz == 32.  Frozen weights, or train mode where
+        ops.GENERIC_TRAIN_EXT asks for it (render refuses the rest)."""
         return (ops.generic_shape_ok(self.W, self.D, self.skips, self.W_features) and self.out_ch_size != 3
                 and self.in_channels_xyz == 32 and self.in_channels_dir in range(3, 28, 6))
 
@@ -310,7 +311,8 @@ class NeRFH_NFF(nn.Module):
         raise NotImplementedError(f"nefes_amd: {what} is not built for the generic field kernels ({self._shape()}); they serve frozen "
                                   f"weights (behind an external / hash-grid encoding: frozen weights only, the table may train).  "
                                   f"Their train-mode instances, on the frequency embedding, are opt-in: set "
-                                  f"NEFES_GENERIC_TRAIN=1 (ops.GENERIC_TRAIN).  Tuned instances: {ops.COMPILED_SET}")
+                                  f"NEFES_GENERIC_TRAIN=1 (ops.GENERIC_TRAIN); behind an external encoding, "
+                                  f"NEFES_GENERIC_TRAIN_EXT=1 (ops.GENERIC_TRAIN_EXT).  Tuned instances: {ops.COMPILED_SET}")
 
     def invalidate_packed(self):
         """Force a re-pack on the next render.  The cache key is (data_ptr, _version, device) per parameter, which sees

@@ -130,6 +130,10 @@ SIGNATURES = {
     "nefes_generic_train_row_offset": (_i, [_gdesc, _i]),
     "nefes_field_fwd_train_generic": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_field_bwd_train_generic": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_generic_train_rows_ext": (_sz, [_gdesc]),
+    "nefes_generic_train_row_offset_ext": (_i, [_gdesc, _i]),
+    "nefes_field_fwd_train_generic_ext": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "nefes_field_bwd_train_generic_ext": (_i, [_gdesc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_train_rows": (_sz, [_desc]),
     "nefes_train_row_offset": (_i, [_desc, _i]),
     "nefes_field_fwd_train": (_i, [_desc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
@@ -181,7 +185,8 @@ COMPILED_SET = ("fp16 two-part instances (default): widths 128 / 256 x feature h
                 "embedding, width 256 x 0..29 or 30..141 channels with an external 32-feature embedding (hash grid); bf16x6 and fp32-MFMA instances "
                 "(NEFES_SPLIT=x6 / f32): width 256 x 16 channels and width 128 x 128 channels only")
 GENERIC_SET = ("generic fp32-MFMA kernels (frequency embedding: frozen weights, or train mode with NEFES_GENERIC_TRAIN=1; an external "
-               "32-feature embedding (hash grid): frozen weights only, the table may train): any width that is "
+               "32-feature embedding (hash grid): frozen weights only, the table may train -- or train mode with "
+               "NEFES_GENERIC_TRAIN_EXT=1): any width that is "
                "a multiple of 32 from 32 to 512, depth 1..8 with skips=[4] (or none when depth <= 4), feature heads of 1..141 channels")
 COMPILED_SET += ".  Other shapes (NeRFH_NFF.packed_generic): " + GENERIC_SET
 

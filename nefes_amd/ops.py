@@ -865,6 +865,9 @@ class FieldFromPoints(torch.autograd.Function):
 # "1": a trainable network on the generic kernels trains (train.field_train_generic: their train-mode instances + the weight-gradient
 # kernels of csrc/train.hip).  Off by default: such a network is refused, as before the train-mode instances existed.
 GENERIC_TRAIN = os.environ.get("NEFES_GENERIC_TRAIN", "0") == "1"
+# "1": the same for a trainable network behind an xyz encoder (a hash grid; train.field_train_generic_encoded, the train-mode instances
+# on a supplied encoding).  A switch of its own, off by default and sufficient alone: GENERIC_TRAIN does not reach such a network.
+GENERIC_TRAIN_EXT = os.environ.get("NEFES_GENERIC_TRAIN_EXT", "0") == "1"
 GENERIC_SET = L.GENERIC_SET
 
 
@@ -934,11 +937,13 @@ class PackedGeneric:
         return L.load().nefes_generic_mask_bytes(self.desc, M)
 
     def train_rows(self):
-        """(rows per tile, first row of block L.TB_*) of the train-mode acts / dacts buffers (nefes_generic_train_row_offset)."""
-        if self.xyz_encoding != L.XYZ_FREQ10:
-            raise RuntimeError("nefes_amd: the generic kernels have no train-mode instances on a supplied encoding")
+        """(rows per tile, first row of block L.TB_*) of the train-mode acts / dacts buffers (nefes_generic_train_row_offset, or its
+        _ext twin for a pack on a supplied encoding: the E block is that encoding's 32 rows)."""
         lib = L.load()
-        return int(lib.nefes_generic_train_rows(self.desc)), [int(lib.nefes_generic_train_row_offset(self.desc, b)) for b in range(L.TB_END + 1)]
+        rows, offset = lib.nefes_generic_train_rows, lib.nefes_generic_train_row_offset
+        if self.xyz_encoding == L.XYZ_EXTERNAL32:
+            rows, offset = lib.nefes_generic_train_rows_ext, lib.nefes_generic_train_row_offset_ext
+        return int(rows(self.desc)), [int(offset(self.desc, b)) for b in range(L.TB_END + 1)]
 
     def n_raw(self, mode):
         return 1 if mode == L.FIELD_SIGMA else (3 + self.feat_dim + (1 if mode == L.FIELD_STATIC else 6))

@@ -142,6 +142,8 @@ def _render_core(rays_o, rays_d, viewdirs, near, far, network_fn, network_fine, 
         if (trainable(net) or grid_static) and mode != L.FIELD_SIGMA:
             from . import train as T
             if ops.is_generic(pk):
+                if cfg.xyz_encoder is not None and ops.GENERIC_TRAIN_EXT:
+                    return T.field_train_generic_encoded(net, mode, cfg.xyz_encoder, rays_o, rays_d, viewdirs, z_)
                 if not ops.GENERIC_TRAIN or cfg.xyz_encoder is not None:
                     net.require_frozen_for_generic("train mode (weight gradients)")
                 return T.field_train_generic(net, mode, rays_o, rays_d, viewdirs, z_)

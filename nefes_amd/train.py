@@ -403,7 +403,8 @@ def field_train_encoded(net, mode, grid, rays_o, rays_d, viewdirs, z):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# Train mode on the generic kernels (csrc/field_generic.hip TRAIN instances): any --netwidth / --netdepth.  Opt-in: ops.GENERIC_TRAIN.
+# Train mode on the generic kernels (csrc/field_generic.hip TRAIN instances): any --netwidth / --netdepth.  Opt-in: ops.GENERIC_TRAIN,
+# and ops.GENERIC_TRAIN_EXT behind an xyz encoder (a hash grid).
 # ---------------------------------------------------------------------------------------------------------------------------------
 class _GenericPass(_Pass):
     """_Pass on the generic row map (nefes_generic_train_row_offset): same declarations, same launches."""
@@ -439,28 +440,22 @@ def _generic_buffers_fit(pk, N, S, dev):
                            f"{int(free / per_ray)} rays of {S} samples would fit: render fewer rays per step (chunk)")
 
 
-def weight_grads_generic(net, pk, mode, N, S, raw_t, g_raw_t, acts, o, d, v, zz, masks):
-    """weight_grads on the generic kernels: one fused backward launch (ray gradients + every layer's pre-activation gradient to
-    `dacts`), then dW = G X^T per layer on nefes_train_dw_bias.  `acts` holds layer OUTPUTS (after ReLU) and the embeddings in the
-    reference's order: x_relu = 0 everywhere, no slot permutation."""
-    lib = L.load()
+def _param_grads_generic(pk, mode, acts, dacts):
+    """dW = G X^T per layer on nefes_train_dw_bias from the buffers of a generic train-mode forward + backward, for either encoding:
+    the E block is the frequency embedding's 63 features in 64 rows, or a supplied encoding's 32 in 32 (pk.xyz_encoding).  `acts` holds
+    layer OUTPUTS (after ReLU) and the embeddings in the reference's order: x_relu = 0 everywhere, no slot permutation."""
     W, D, Cf, skip = pk.width, pk.depth, pk.feat_dim, pk.skip
     C3, H2 = 3 + Cf, W // 2
     full = mode == L.FIELD_FULL
-    dev = acts.device
-    dacts = torch.empty_like(acts)
-    g_pts, g_vs = torch.empty(N * S, 3, device=dev), torch.empty(N * S, 3, device=dev)
-    L.check(lib.nefes_field_bwd_train_generic(pk.desc, pk.blob.data_ptr(), mode, N, S, o.data_ptr(), d.data_ptr(), zz.data_ptr(), v.data_ptr(),
-                                              raw_t.data_ptr(), g_raw_t.data_ptr(), masks.data_ptr(), dacts.data_ptr(), g_pts.data_ptr(),
-                                              g_vs.data_ptr(), ops._stream()), "nefes_field_bwd_train_generic")
+    e_rows, n_e = (32, 32) if pk.xyz_encoding == L.XYZ_EXTERNAL32 else (64, EMB_XYZ)
     P = _GenericPass(pk, acts.shape[0], acts, dacts)
     TB = lambda l: L.TB_L1 + (l - 1)
-    h = {1: P.dw(TB(1), W, L.TB_E, 64, False)}
+    h = {1: P.dw(TB(1), W, L.TB_E, e_rows, False)}
     he = None
     for l in range(2, D + 1):
         h[l] = P.dw(TB(l), W, TB(l - 1), W, False)
         if l - 1 == skip:                                              # the layer that reads cat([embedding, h]); its bias once
-            he = P.dw(TB(l), W, L.TB_E, 64, False, bias=False)
+            he = P.dw(TB(l), W, L.TB_E, e_rows, False, bias=False)
     hsig, hfin = P.dw(L.TB_SIG, 1, TB(D), W, False), P.dw(L.TB_FINAL, W, TB(D), W, False)
     hdir, hdird = P.dw(L.TB_DIR, H2, L.TB_FINAL, W, False), P.dw(L.TB_DIR, H2, L.TB_DV, 32, False, bias=False)
     hrgb = P.dw(L.TB_RGB, C3, L.TB_DIR, H2, False)
@@ -469,11 +464,11 @@ def weight_grads_generic(net, pk, mode, N, S, raw_t, g_raw_t, acts, o, d, v, zz,
         ht1, ht2 = P.dw(L.TB_T1, H2, L.TB_T0, H2, False), P.dw(L.TB_T2, H2, L.TB_T1, H2, False)
         hth = P.dw(L.TB_TH, 5, L.TB_T2, H2, False)
     P.run()
-    g = {"xyz_encoding_1.0.weight": h[1].v[:W, :EMB_XYZ]}
+    g = {"xyz_encoding_1.0.weight": h[1].v[:W, :n_e]}
     for l in range(2, D + 1):
         dh = h[l].v[:W, :W]
         if l - 1 == skip:
-            dh = torch.cat([he.v[:W, :EMB_XYZ], dh], 1)
+            dh = torch.cat([he.v[:W, :n_e], dh], 1)
         g[f"xyz_encoding_{l}.0.weight"] = dh
     g["static_sigma.0.weight"] = hsig.v[:1, :W]
     g["xyz_encoding_final.weight"] = hfin.v[:W, :W]
@@ -495,7 +490,34 @@ def weight_grads_generic(net, pk, mode, N, S, raw_t, g_raw_t, acts, o, d, v, zz,
         g["transient_encoding.4.bias"] = blk(L.TB_T2, H2)
     if DEBUG is not None:
         DEBUG.update(acts=rows_view(acts), dacts=rows_view(dacts), rows=P.rows, off={b: P.off(b) for b in range(L.TB_END + 1)})
+    return g
+
+
+def weight_grads_generic(net, pk, mode, N, S, raw_t, g_raw_t, acts, o, d, v, zz, masks):
+    """weight_grads on the generic kernels: one fused backward launch (ray gradients + every layer's pre-activation gradient to
+    `dacts`), then the weight gradients of _param_grads_generic."""
+    dev = acts.device
+    dacts = torch.empty_like(acts)
+    g_pts, g_vs = torch.empty(N * S, 3, device=dev), torch.empty(N * S, 3, device=dev)
+    L.check(L.load().nefes_field_bwd_train_generic(pk.desc, pk.blob.data_ptr(), mode, N, S, o.data_ptr(), d.data_ptr(), zz.data_ptr(),
+                                                   v.data_ptr(), raw_t.data_ptr(), g_raw_t.data_ptr(), masks.data_ptr(), dacts.data_ptr(),
+                                                   g_pts.data_ptr(), g_vs.data_ptr(), ops._stream()), "nefes_field_bwd_train_generic")
+    g = _param_grads_generic(pk, mode, acts, dacts)
     g["__rays__"] = (g_pts, g_vs)
+    return g
+
+
+def weight_grads_generic_encoded(net, pk, mode, N, S, raw_t, g_raw_t, acts, v, masks, want_w=True):
+    """weight_grads_generic for a pack on a supplied encoding: "__rays__" holds (d encoding [N*S, 32], d viewdirs per sample).
+    want_w=False: the backward launch alone (no parameter gradients)."""
+    dev = acts.device
+    dacts = torch.empty_like(acts)
+    g_enc, g_vs = torch.empty(N * S, 32, device=dev), torch.empty(N * S, 3, device=dev)
+    L.check(L.load().nefes_field_bwd_train_generic_ext(pk.desc, pk.blob.data_ptr(), mode, N, S, v.data_ptr(), raw_t.data_ptr(),
+                                                       g_raw_t.data_ptr(), masks.data_ptr(), dacts.data_ptr(), g_enc.data_ptr(),
+                                                       g_vs.data_ptr(), ops._stream()), "nefes_field_bwd_train_generic_ext")
+    g = _param_grads_generic(pk, mode, acts, dacts) if want_w else {}
+    g["__rays__"] = (g_enc, g_vs)
     return g
 
 
@@ -551,3 +573,65 @@ def field_train_generic(net, mode, rays_o, rays_d, viewdirs, z):
         net.require_frozen_for_generic("train mode (weight gradients)")
     sd = dict(net.named_parameters())
     return FieldTrainGeneric.apply(rays_o, rays_d, viewdirs, z, net, mode, *[sd[n] for n in param_names_generic(net, mode)])
+
+
+class FieldTrainGenericEncoded(torch.autograd.Function):
+    """FieldTrainEncoded on the generic kernels (net.packed_generic() of a network with in_channels_xyz=32: any width / depth): raw_t
+    [N,R,S] from enc [N,S,32] and viewdirs [N,3], differentiable w.r.t. enc (-> the grid's table and the sample positions,
+    HashGridEncode), viewdirs and the network parameters (*params in `param_names_generic` order)."""
+
+    @staticmethod
+    def forward(ctx, enc, viewdirs, net, mode, *params):
+        pk = net.packed_generic()
+        lib = L.load()
+        if mode not in (L.FIELD_STATIC, L.FIELD_FULL):
+            raise ValueError("nefes_amd: train mode evaluates the static or the full head")
+        if mode == L.FIELD_FULL and not pk.has_transient:
+            raise ValueError("nefes_amd: the full head of a network without a transient head")
+        if pk.xyz_encoding != L.XYZ_EXTERNAL32:
+            raise RuntimeError(f"nefes_amd: train mode on a supplied encoding needs a network with in_channels_xyz=32; got {net._shape()}")
+        N, S = enc.shape[0], enc.shape[1]
+        e, v = ops._f32(enc).reshape(N * S, 32), ops._f32(viewdirs)
+        _generic_buffers_fit(pk, N, S, e.device)
+        rows, off = pk.train_rows()
+        raw_t = torch.empty(N, pk.n_raw(mode), S, device=e.device)
+        acts = torch.empty((N * S + 127) // 128, rows, 128, device=e.device)
+        masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=e.device)
+        with ops._timed("field_fwd_train[generic,ext]"):
+            L.check(lib.nefes_field_fwd_train_generic_ext(pk.desc, pk.blob.data_ptr(), mode, N, S, ops._chk(e, "enc"), ops._chk(v, "viewdirs"),
+                                                          raw_t.data_ptr(), acts.data_ptr(), masks.data_ptr(), ops._stream()),
+                    "nefes_field_fwd_train_generic_ext")
+        ops._tap("masks_generic", (masks, N, S, pk, mode))
+        ctx.save_for_backward(raw_t, acts, v, masks)
+        if DEBUG is not None:
+            DEBUG.update(acts=rows_view(acts), rows=rows, off=dict(enumerate(off)))
+        ctx.net, ctx.pk, ctx.mode, ctx.NS, ctx.pk_gen = net, pk, mode, (N, S), pk.generation
+        return raw_t
+
+    @staticmethod
+    def backward(ctx, g_raw_t):
+        ctx.pk.check_generation(ctx.pk_gen)
+        raw_t, acts, v, masks = ctx.saved_tensors
+        N, S = ctx.NS
+        want_w = any(ctx.needs_input_grad[4:])
+        with ops._timed("field_bwd_train[generic,ext]"):
+            g = weight_grads_generic_encoded(ctx.net, ctx.pk, ctx.mode, N, S, raw_t, ops._f32(g_raw_t), acts, v, masks, want_w=want_w)
+        g_enc, g_vs = g.pop("__rays__")
+        g_v = None
+        if ctx.needs_input_grad[1]:
+            _, _, g_v = ops.ray_grad_reduce(N, S, torch.zeros(N, S, device=v.device), g_vs, g_vs)
+        g_params = (None,) * (len(ctx.needs_input_grad) - 4)
+        if want_w:
+            g = ctx.net.shrink_grads(g)
+            g_params = tuple(g[n].contiguous() if need else None
+                             for n, need in zip(param_names_generic(ctx.net, ctx.mode), ctx.needs_input_grad[4:]))
+        return (g_enc.reshape(N, S, 32) if ctx.needs_input_grad[0] else None, g_v, None, None) + g_params
+
+
+def field_train_generic_encoded(net, mode, grid, rays_o, rays_d, viewdirs, z):
+    """field_train_encoded for a network of any width / depth (ops.GENERIC_TRAIN_EXT): pts = o + d z -> grid(pts) ->
+    FieldTrainGenericEncoded.  Gradients reach the network's parameters, the grid's table (if it requires grad) and the rays in one
+    backward."""
+    pts = rays_o[:, None, :] + rays_d[:, None, :] * z[..., None]
+    sd = dict(net.named_parameters())
+    return FieldTrainGenericEncoded.apply(grid(pts), viewdirs, net, mode, *[sd[n] for n in param_names_generic(net, mode)])
