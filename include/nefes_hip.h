@@ -464,6 +464,16 @@ int nefes_train_dw_bias(int64_t n_tiles, int rows, const float* dacts, int g_row
  * w.r.t. a layer's input is this call on the flipped, transposed weights (W'[ci][co][ty][tx] = W[co][ci][K-1-ty][K-1-tx]). */
 int nefes_conv2d_same(int B, int Cin, int Cout, int H, int W, int ksize, const float* x, const float* mask, const float* w_packed,
                       const float* bias, int relu, float* y, void* stream);
+/* Weight and bias gradient of that convolution (training FusionNet): g_w dev [Cout,Cin,ksize,ksize] (torch's layout) and g_bias dev [Cout]
+ * (nullable), both OVERWRITTEN:  g_w[co][ci][ty][tx] = sum_b sum_p gm[b][co][p] x[b][ci][p + (ty - pad, tx - pad)],  g_bias[co] = sum_b sum_p
+ * gm[b][co][p],  gm = g_y, zero where mask <= 0 (mask nullable, g_y's shape: this layer's forward OUTPUT after ReLU).  fp32 MFMA, no
+ * atomics: the pixels of the batch are cut into chunks of 256 whose partial results go to `workspace` (dev,
+ * nefes_conv2d_wgrad_workspace bytes, a function of the shape alone; contents irrelevant before, undefined after) and are added in
+ * ascending chunk order: two calls on the same inputs return the same bits.  NEFES_E_UNSUPPORTED (workspace 0) for another ksize, a batch
+ * of 2^31 pixels or more, or an image too wide for the staged tile (W above 111 at 5x5, 224 at 3x3). */
+size_t nefes_conv2d_wgrad_workspace(int B, int Cin, int Cout, int H, int W, int ksize);
+int nefes_conv2d_wgrad(int B, int Cin, int Cout, int H, int W, int ksize, const float* x, const float* g_y, const float* mask, float* g_w,
+                       float* g_bias, void* workspace, void* stream);
 
 /* ---- bicubic up-sampling of the fused feature image (script/dm/DFM_APR_refine.py:114,118: torch.nn.Upsample(size,
  *      mode='bicubic'), align_corners=False, A=-0.75) ---- */
@@ -495,6 +505,10 @@ int nefes_bn_train_fwd(int B, int C, int64_t P, int per_image, const float* x, c
                        void* stream);
 int nefes_bn_train_bwd(int B, int C, int64_t P, int per_image, const float* x, const float* weight, const double* save, const float* g_y,
                        float* g_x, void* stream);
+/* The backward for TRAINABLE affine parameters, per_image = 0 only (save of nefes_bn_train_fwd(per_image = 0)): also writes g_weight[c] =
+ * sum g_y xhat and g_bias[c] = sum g_y (dev [C], overwritten; the float64 sums the input gradient is made of).  g_x nullable. */
+int nefes_bn_train_bwd_affine(int B, int C, int64_t P, const float* x, const float* weight, const double* save, const float* g_y,
+                              float* g_x, float* g_weight, float* g_bias, void* stream);
 /* svd_reg (dm/DFM_pose_refine.py:119-129): pose dev [n,3,4] -> out dev [n,3,4] with the 3x3 block replaced by U V^T of its SVD (its
  * orthogonal polar factor), translation column copied.  float64 inside (one-sided Jacobi).  save: dev [n,21] doubles (U, V, sigma) for the
  * backward, or NULL.  The backward is the polar factor's derivative d A = U [(H - H^T) o K] V^T, H = U^T G V, K_ij = 1 / (s_i + s_j):

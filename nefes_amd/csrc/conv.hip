@@ -171,3 +171,201 @@ extern "C" int nefes_conv2d_same(int B, int Cin, int Cout, int H, int W, int ksi
     else hipLaunchKernelGGL((conv2d_kernel<5, true>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
+
+namespace {
+
+// ---- weight and bias gradient of the same convolution (training FusionNet: script/run_nefes.py:78-108,150-160) ------------------------
+//     g_w[co][ci][ty][tx] = sum_b sum_p gm[b][co][p] x[b][ci][p + (ty - pad, tx - pad)],   g_bias[co] = sum_b sum_p gm[b][co][p],
+//     gm = g_y, zero where mask (the layer's own output after ReLU) <= 0.
+// Implicit GEMM on v_mfma_f32_32x32x2_f32: M = 32 output channels (A operand: gm), N = 32 input channels (B operand: x at the tap's
+// shift), K = pixels, two per MFMA, one accumulator tile per tap.  The pixels of the batch are numbered through, q = b H W + p, and cut
+// into chunks of WG_CHUNK; one workgroup per (chunk, co tile, ci tile) stages gm[32][chunk] and x[32][chunk + halo on either side]
+// (halo = pad W + pad) in LDS from coalesced loads -- every element with its own (b, p), so a chunk may straddle images -- and one word
+// per pixel whose bit `tap` says whether the tap lies inside THAT pixel's image (zero padding is per image).  The taps are split over the
+// four waves (tap = wave + 4 j: at most 7 accumulator tiles).  Partial tiles go to the workspace in g_w's own layout,
+// ws[chunk][Cout*Cin*k*k + Cout], and conv2d_wgrad_sum_kernel adds them in ascending chunk order: no atomics, the same bits every call.
+constexpr int WG_CHUNK = 256;                         // pixels per workgroup = its thread count (one pixel column per thread when staging)
+constexpr int WG_SG = WG_CHUNK + 2;                   // LDS row strides = 2 mod 64: the 64 lanes of an operand read (row n, pixel kh) hit 64 banks
+constexpr size_t WG_LDS_MAX = 128 * 1024;
+
+struct WgradArgs {
+    const float* x;      // [B][Cin][H][W]
+    const float* gy;     // [B][Cout][H][W]
+    const float* mask;   // [B][Cout][H][W] or null
+    float* ws;           // [chunks][Cout*Cin*KS*KS + Cout]
+    int B, Cin, Cout, H, W, Q, chunks, halo, sx;      // Q = B H W;  sx = LDS row stride of the x tile
+};
+
+__host__ __device__ inline int wgrad_sx(int halo) { return (WG_CHUNK + 2 * halo + 61) / 64 * 64 + 2; }      // >= chunk + 2 halo, = 2 mod 64
+
+template <int KS>
+__global__ __launch_bounds__(256) void conv2d_wgrad_kernel(WgradArgs a) {
+    constexpr int PAD = KS / 2, TAPS = KS * KS, NT = (TAPS + 3) / 4;
+    extern __shared__ __attribute__((aligned(16))) float wg_smem[];
+    __shared__ float bsum[8][32];
+    float* gL = wg_smem;                              // [32][WG_SG]
+    float* xL = gL + 32 * WG_SG;                      // [32][sx]: column c = pixel q0 - halo + c
+    uint32_t* vL = (uint32_t*)(xL + 32 * a.sx);       // [WG_CHUNK]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n = lane & 31, kh = lane >> 5;
+    const int HW = a.H * a.W, co_tiles = (a.Cout + 31) / 32;
+    int bid = blockIdx.x;
+    const int chunk = bid % a.chunks;
+    bid /= a.chunks;
+    const int cot = bid % co_tiles, cit = bid / co_tiles;
+    const int q0 = chunk * WG_CHUNK;
+    const int npx = min(WG_CHUNK, a.Q - q0);          // pixels of this chunk (the last one may be short)
+    {   // gm tile and the validity words: thread = pixel column
+        const int q = q0 + tid;
+        const bool in = q < a.Q;
+        const int b = in ? q / HW : 0, p = in ? q - b * HW : 0;
+        const int py = p / a.W, px = p - py * a.W;
+        uint32_t v = 0;
+#pragma unroll
+        for (int tap = 0; tap < TAPS; ++tap) {
+            const int iy = py + tap / KS - PAD, ix = px + tap % KS - PAD;
+            if (in && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v |= 1u << tap;
+        }
+        vL[tid] = v;
+        const size_t base = (size_t)b * a.Cout * HW + p;
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) {
+            const int co = cot * 32 + r;
+            float g = 0.f;
+            if (in && co < a.Cout) {
+                const size_t o = base + (size_t)co * HW;
+                g = a.gy[o];
+                if (a.mask) g = a.mask[o] > 0.f ? g : 0.f;
+            }
+            gL[r * WG_SG + tid] = g;
+        }
+    }
+    const int xcols = npx + 2 * a.halo;               // columns the MFMAs can read (pixel q0 - halo .. q0 + npx + halo - 1)
+    for (int c = tid; c < xcols; c += 256) {
+        const int q = q0 - a.halo + c;
+        const bool in = q >= 0 && q < a.Q;
+        const int b = in ? q / HW : 0, p = in ? q - b * HW : 0;
+        const size_t base = (size_t)b * a.Cin * HW + p;
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) {
+            const int ci = cit * 32 + r;
+            xL[r * a.sx + c] = in && ci < a.Cin ? a.x[base + (size_t)ci * HW] : 0.f;
+        }
+    }
+    __syncthreads();
+    if (cit == 0) {                                   // (block-uniform) the chunk's share of the bias gradient: eight runs of 32 pixels per row
+        float sum = 0.f;
+        const float* row = gL + (tid & 31) * WG_SG + (tid >> 5) * 32;
+#pragma unroll 8
+        for (int p = 0; p < 32; ++p) sum += row[p];    // (pixels past the chunk's last hold zeros)
+        bsum[tid >> 5][tid & 31] = sum;
+    }
+
+    f32x16 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    // wave-uniform: the tap's bit and its shift in the numbered-through pixels.  A wave with fewer than NT taps repeats the last tap
+    // into a tile nobody stores: no branch inside the K loop (a conditional MFMA there costs a copy of its 16 accumulators per step)
+    int tbit[NT], toff[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        tbit[j] = min(wave + 4 * j, TAPS - 1);
+        toff[j] = a.halo + (tbit[j] / KS - PAD) * a.W + (tbit[j] % KS - PAD);
+    }
+    const float* gp = gL + n * WG_SG + kh;
+    const float* xp = xL + n * a.sx + kh;
+    const uint32_t* vp = vL + kh;
+    const int steps = (npx + 1) / 2;                  // (an odd count: the upper half's last pixel has gm = 0 and no tap bit)
+    for (int s = 0; s < steps; ++s) {
+        const float g = gp[2 * s];
+        const uint32_t v = vp[2 * s];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const float xv = xp[2 * s + toff[j]];
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(g, (v >> tbit[j]) & 1u ? xv : 0.f, acc[j], 0, 0, 0);
+        }
+    }
+    const size_t nw = (size_t)a.Cout * a.Cin * TAPS;
+    float* wsc = a.ws + (size_t)chunk * (nw + a.Cout);
+    const int ci = cit * 32 + n;
+    if (ci < a.Cin) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int tap = wave + 4 * j;
+            if (tap < TAPS) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = cot * 32 + nefes_rho(kh, r);
+                    if (co < a.Cout) wsc[((size_t)co * a.Cin + ci) * TAPS + tap] = acc[j][r];
+                }
+            }
+        }
+    }
+    if (cit == 0) {
+        __syncthreads();
+        if (tid < 32 && cot * 32 + tid < a.Cout) {    // the eight runs added in ascending pixel order
+            float sum = bsum[0][tid];
+#pragma unroll
+            for (int k = 1; k < 8; ++k) sum += bsum[k][tid];
+            wsc[nw + cot * 32 + tid] = sum;
+        }
+    }
+}
+
+// g_w / g_bias = the chunks' partial results added in ascending chunk order
+__global__ __launch_bounds__(256) void conv2d_wgrad_sum_kernel(const float* __restrict__ ws, int chunks, long nw, int Cout, float* __restrict__ g_w,
+                                                               float* __restrict__ g_bias) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x, tot = nw + Cout;
+    if (i >= tot) return;
+    float s = 0.f;
+    for (int c = 0; c < chunks; ++c) s += ws[(long)c * tot + i];
+    if (i < nw) g_w[i] = s;
+    else if (g_bias) g_bias[i - nw] = s;
+}
+
+// chunks (0 = unsupported) and the dynamic LDS bytes of one workgroup
+int wgrad_plan(int B, int H, int W, int ksize, size_t* lds) {
+    if (ksize != 3 && ksize != 5) return 0;
+    const long long Q = (long long)B * H * W;
+    if (Q > 0x7fffffffll - 2 * WG_CHUNK || W > (1 << 20)) return 0;      // (pixel numbers and the halo are ints)
+    const int halo = (ksize / 2) * W + ksize / 2;
+    const size_t bytes = ((size_t)32 * WG_SG + (size_t)32 * wgrad_sx(halo) + WG_CHUNK) * 4;
+    if (bytes > WG_LDS_MAX) return 0;
+    if (lds) *lds = bytes;
+    return (int)((Q + WG_CHUNK - 1) / WG_CHUNK);
+}
+
+}  // namespace
+
+extern "C" size_t nefes_conv2d_wgrad_workspace(int B, int Cin, int Cout, int H, int W, int ksize) {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
+    const int chunks = wgrad_plan(B, H, W, ksize, nullptr);
+    return (size_t)chunks * ((size_t)Cout * Cin * ksize * ksize + Cout) * sizeof(float);
+}
+
+extern "C" int nefes_conv2d_wgrad(int B, int Cin, int Cout, int H, int W, int ksize, const float* x, const float* g_y, const float* mask,
+                                  float* g_w, float* g_bias, void* workspace, void* stream) {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || !x || !g_y || !g_w || !workspace) return NEFES_E_BADARG;
+    if (ksize != 3 && ksize != 5) return NEFES_E_UNSUPPORTED;
+    size_t lds = 0;
+    const int chunks = wgrad_plan(B, H, W, ksize, &lds);
+    if (chunks <= 0) return NEFES_E_UNSUPPORTED;
+    const long long blocks = (long long)chunks * ((Cout + 31) / 32) * ((Cin + 31) / 32);
+    const long long nw = (long long)Cout * Cin * ksize * ksize;
+    if (blocks > 0x7fffffffll || (nw + Cout + 255) / 256 > 0x7fffffffll) return NEFES_E_UNSUPPORTED;
+    WgradArgs a;
+    a.x = x; a.gy = g_y; a.mask = mask; a.ws = (float*)workspace;
+    a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.Q = B * H * W; a.chunks = chunks;
+    a.halo = (ksize / 2) * W + ksize / 2;
+    a.sx = wgrad_sx(a.halo);
+    hipStream_t st = (hipStream_t)stream;
+    const void* k = ksize == 3 ? (const void*)conv2d_wgrad_kernel<3> : (const void*)conv2d_wgrad_kernel<5>;
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    if (ksize == 3) hipLaunchKernelGGL((conv2d_wgrad_kernel<3>), dim3((unsigned)blocks), dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((conv2d_wgrad_kernel<5>), dim3((unsigned)blocks), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(conv2d_wgrad_sum_kernel, dim3((unsigned)((nw + Cout + 255) / 256)), dim3(256), 0, st, (const float*)workspace, chunks, (long)nw, Cout,
+                       g_w, g_bias);
+    return (int)hipGetLastError();
+}

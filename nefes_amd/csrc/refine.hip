@@ -241,6 +241,36 @@ __global__ __launch_bounds__(256) void bn_train_bwd_kernel(int B, int C, long P,
     }
 }
 
+// The same for TRAINABLE affine parameters (statistics over the whole batch only): the two float64 sums the input gradient needs are the
+// parameters' gradients, g_bias[c] = sum d y, g_weight[c] = sum d y xhat.  gx nullable (the input carries no gradient).
+__global__ __launch_bounds__(256) void bn_train_bwd_affine_kernel(int B, int C, long P, const float* __restrict__ x, const float* __restrict__ w,
+                                                                  const double* __restrict__ save, const float* __restrict__ gy, float* __restrict__ gx,
+                                                                  float* __restrict__ gw, float* __restrict__ gb) {
+    __shared__ double sh[2][4];
+    const int c = blockIdx.x;
+    const long n = (long)B * P;
+    const double mean = save[(long)c * 2 + 0], inv = save[(long)c * 2 + 1];
+    auto at = [&](long i) -> long { return ((i / P) * C + c) * P + i % P; };
+    double s1 = 0, s2 = 0;
+    for (long i = threadIdx.x; i < n; i += 256) {
+        const long o = at(i);
+        const double d = gy[o];
+        s1 += d;
+        s2 += d * ((double)x[o] - mean) * inv;
+    }
+    const double w1 = wave_sum(s1), w2 = wave_sum(s2);
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = w1; sh[1][threadIdx.x >> 6] = w2; }
+    __syncthreads();
+    const double t1 = ((sh[0][0] + sh[0][1]) + sh[0][2]) + sh[0][3], t2 = ((sh[1][0] + sh[1][1]) + sh[1][2]) + sh[1][3];
+    if (threadIdx.x == 0) { gb[c] = (float)t1; gw[c] = (float)t2; }
+    if (!gx) return;
+    const double m1 = t1 / (double)n, m2 = t2 / (double)n, k_ = (w ? (double)w[c] : 1.0) * inv;
+    for (long i = threadIdx.x; i < n; i += 256) {
+        const long o = at(i);
+        gx[o] = (float)(k_ * ((double)gy[o] - m1 - ((double)x[o] - mean) * inv * m2));
+    }
+}
+
 // ---- svd_reg (dm/DFM_pose_refine.py:119-129): the 3x3 block A of a regressed pose replaced by U V^T of its SVD ------------------------
 // = the orthogonal polar factor of A.  One thread per pose, float64 inside: one-sided Jacobi on the columns of A (B = A V, V a
 // product of plane rotations, until the columns are orthogonal; sigma_j = |B_j|, U_j = B_j / sigma_j).  U V^T does not depend on the
@@ -929,6 +959,14 @@ extern "C" int nefes_bn_train_bwd(int B, int C, int64_t P, int per_image, const 
     if (B <= 0 || C <= 0 || P <= 0 || !x || !save || !g_y || !g_x) return NEFES_E_BADARG;
     const int groups = per_image ? B : 1;
     hipLaunchKernelGGL(bn_train_bwd_kernel, dim3((unsigned)(groups * C)), dim3(256), 0, (hipStream_t)stream, B, C, (long)P, groups, x, weight, save, g_y, g_x);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nefes_bn_train_bwd_affine(int B, int C, int64_t P, const float* x, const float* weight, const double* save, const float* g_y,
+                                         float* g_x, float* g_weight, float* g_bias, void* stream) {
+    if (B <= 0 || C <= 0 || P <= 0 || !x || !save || !g_y || !g_weight || !g_bias) return NEFES_E_BADARG;
+    hipLaunchKernelGGL(bn_train_bwd_affine_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, B, C, (long)P, x, weight, save, g_y, g_x, g_weight,
+                       g_bias);
     return (int)hipGetLastError();
 }
 

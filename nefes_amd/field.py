@@ -23,7 +23,8 @@ FEATURE_DIM = 128        # nerfh_nff.py:21
 
 class FusionNet(nn.Module):
     """4-layer conv 'fusion' CNN on the rendered (rgb || feature) image (nerfh_nff.py:356-418).
-    Plain torch (MIOpen) where its weights train; in the refinement loop, where they are frozen and the net runs
+    Plain torch (MIOpen) where its weights train -- or, with ops.FUSION_TRAIN (opt-in), the weight-gradient kernels of
+    csrc/conv.hip and the BatchNorm backward of csrc/refine.hip (_use_hip_train); in the refinement loop, where they are frozen and the net runs
     on the 60x80 render every iteration, forward_parts takes the implicit-GEMM kernels of csrc/conv.hip."""
     mean = [0.485, 0.456, 0.406]
     std = [0.229, 0.224, 0.225]
@@ -47,7 +48,11 @@ class FusionNet(nn.Module):
     def forward(self, x):
         mean, std = self._mean_std(x)
         x[:, :3] = (x[:, :3] - mean[:, None, None]) / std[:, None, None]     # in place, as the reference does
-        out = self.net(x)
+        if self._use_hip_train(x):
+            out = self._convs_hip_train(x)
+            out = out if self.no_BN else self._bn(out, False)
+        else:
+            out = self.net(x)
         return x[:, 3:] + out if self.fusion_residule else out
 
     HIP_CONVS = True      # frozen weights on a GPU: the four convolutions as csrc/conv.hip launches (ops.frozen_conv2d)
@@ -65,6 +70,21 @@ class FusionNet(nn.Module):
         x = ops.frozen_conv2d(x, c2.weight, c2.bias, relu=True)
         return ops.frozen_conv2d(x, c3.weight, c3.bias, relu=False)
 
+    def _use_hip_train(self, x):
+        """Training the net on the library's kernels (ops.FUSION_TRAIN, opt-in): CUDA fp32 input and some convolution or BatchNorm
+        parameter requires grad -- the case _use_hip leaves to torch."""
+        from . import ops
+        return (ops.FUSION_TRAIN and self.HIP_CONVS and x.is_cuda and x.dtype == torch.float32
+                and any(p.requires_grad for p in self.net.parameters()))
+
+    def _convs_hip_train(self, x):
+        from . import ops
+        c0, c1, c2, c3 = self.net[0], self.net[2], self.net[4], self.net[6]
+        x = ops.conv2d_same_train(x, c0.weight, c0.bias, relu=True)
+        x = ops.conv2d_same_train(x, c1.weight, c1.bias, relu=True)
+        x = ops.conv2d_same_train(x, c2.weight, c2.bias, relu=True)
+        return ops.conv2d_same_train(x, c3.weight, c3.bias, relu=False)
+
     HIP_BATCHNORM = os.environ.get("NEFES_HIP_BATCHNORM", "1") != "0"   # the refinement loop's case (train mode, frozen affine parameters, GPU): csrc/refine.hip bn_train_* instead of MIOpen
 
     # False: train-mode BatchNorm calls leave the module's running statistics and batch counter alone (its outputs never depend on
@@ -77,6 +97,9 @@ class FusionNet(nn.Module):
         from . import ops
         bn = self.net[-1]
         per_image = bool(per_image_norm and y.shape[0] > 1 and bn.training)
+        if (self.HIP_BATCHNORM and not per_image and bn.training and bn.momentum is not None and bn.weight is not None and bn.bias is not None
+                and (bn.weight.requires_grad or bn.bias.requires_grad) and self._use_hip_train(y)):
+            return ops.batch_norm_train(y, bn, track_stats=self.track_bn_stats)      # (per image with trainable affine parameters: torch, below)
         if (self.HIP_BATCHNORM and self.HIP_CONVS and y.is_cuda and y.dtype == torch.float32 and bn.training and bn.momentum is not None
                 and not any(p is not None and p.requires_grad for p in (bn.weight, bn.bias))):
             return ops.batch_norm_train_frozen(y, bn, per_image, track_stats=self.track_bn_stats)
@@ -130,7 +153,7 @@ class FusionNet(nn.Module):
     def forward_prepared(self, x, per_image_norm=False):
         """forward_parts from the concatenated, colour-normalised input [B,3+C,H,W] on (ops.fusion_input builds it in one launch)."""
         feat_nchw = x[:, 3:]
-        convs = self._convs_hip if self._use_hip(x) else self.net[:7]
+        convs = self._convs_hip if self._use_hip(x) else self._convs_hip_train if self._use_hip_train(x) else self.net[:7]
         out = convs(x) if self.no_BN else self._bn(convs(x), per_image_norm)
         return feat_nchw + out if self.fusion_residule else out
 

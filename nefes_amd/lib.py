@@ -66,6 +66,7 @@ SIGNATURES = {
     "nefes_bicubic_gram": (_i, [_i, _i, _i, _i, _p, _p]),
     "nefes_bn_train_fwd": (_i, [_i, _i, C.c_int64, _i, _p, _p, _p, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p]),
     "nefes_bn_train_bwd": (_i, [_i, _i, C.c_int64, _i, _p, _p, _p, _p, _p, _p]),
+    "nefes_bn_train_bwd_affine": (_i, [_i, _i, C.c_int64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_svd_reg_fwd": (_i, [_i, _p, _p, _p, _p]),
     "nefes_svd_reg_bwd": (_i, [_i, _p, _p, _p, _p]),
     "nefes_regressed_pose_fwd": (_i, [_i, _p, _i, _f, _f, _f, _f, _p, _p, _p]),
@@ -113,6 +114,8 @@ SIGNATURES = {
     "nefes_field_fwd_h3_zrow": (_i, [_desc, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_coarse_sample": (_i, [_i, _i, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p]),
     "nefes_conv2d_same": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p]),
+    "nefes_conv2d_wgrad_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "nefes_conv2d_wgrad": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_probe_mfma_clock": (_i, [_i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _p]),
     "nefes_probe_store_hazard": (_i, [_p, C.c_int64, _i, _p]),
     "nefes_probe_pk_mul": (_i, [_p, C.c_int64, _i, _p]),

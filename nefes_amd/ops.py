@@ -358,6 +358,12 @@ FIELD_GENERIC = os.environ.get("NEFES_FIELD_GENERIC", "0") == "1"
 # nefes_field_bwd_h3_hashgrid); "0": the separate launches HashGridEncode + FieldFromEncoding (the tests compare the two)
 FUSED_HASHGRID = os.environ.get("NEFES_FUSED_HASHGRID", "1") != "0"
 
+# FusionNet with TRAINABLE weights on a GPU (the reference's third training stage, run_nefes.py:78-108,150-160) on the library's kernels:
+# the convolutions' weight / bias gradients (csrc/conv.hip conv2d_wgrad) and BatchNorm's affine gradients (csrc/refine.hip) instead of
+# torch / MIOpen -- deterministic, fp32 MFMA, a fixed summation order.  Opt-in (NEFES_HIP_FUSION_TRAIN=1): off, such a net runs on torch
+# as it always has.  Read at call time (field.FusionNet).
+FUSION_TRAIN = os.environ.get("NEFES_HIP_FUSION_TRAIN", "0") == "1"
+
 
 HEAD_MAX_C = 141          # csrc/layout.h NEFES_HEAD_MAX_C: the larger head class serves 3 + C <= 144
 COMPILED_SET = L.COMPILED_SET
@@ -1256,6 +1262,60 @@ def frozen_conv2d(x, weight, bias, relu=False):
     return FrozenConv2d.apply(x, weight, bias, relu)
 
 
+def _conv2d_wgrad(x, gy, mask, cout, ksize, want_bias):
+    """(g_w [cout, cin, k, k], g_bias [cout] or None) of nefes_conv2d_wgrad; mask: the layer's output after ReLU, or None."""
+    B, cin, H, W = x.shape
+    lib = L.load()
+    nbytes = lib.nefes_conv2d_wgrad_workspace(B, cin, cout, H, W, ksize)
+    if nbytes == 0:
+        L.check(-2, "nefes_conv2d_wgrad")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    g_w = torch.empty(cout, cin, ksize, ksize, device=x.device)
+    g_b = torch.empty(cout, device=x.device) if want_bias else None
+    with _timed("conv2d_wgrad"):
+        L.check(lib.nefes_conv2d_wgrad(B, cin, cout, H, W, ksize, _chk(x, "x"), _chk(gy, "g_y"), _chk(mask, "mask"), _chk(g_w, "g_w"),
+                                       _chk(g_b, "g_bias"), C.c_void_p(ws.data_ptr()), _stream()), "nefes_conv2d_wgrad")
+    return g_w, g_b
+
+
+class TrainConv2d(torch.autograd.Function):
+    """FrozenConv2d with TRAINABLE weight and bias (FusionNet in the reference's third training stage): the same forward and input
+    gradient launches, and the weight / bias gradients through nefes_conv2d_wgrad (csrc/conv.hip: fp32 MFMA, partial sums per pixel
+    chunk added in a fixed order -- no atomics, bit-identical from call to call).  The ReLU derivative comes from the saved output."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        xc = _f32(x)
+        k = weight.shape[-1]
+        y = _conv2d_same(xc, _pack_conv(weight, False), weight.shape[0], k, None if bias is None else _f32(bias), relu)
+        ctx.weight, ctx.relu, ctx.has_bias = weight, relu, bias is not None
+        ctx.save_for_backward(xc, *([y] if relu else []))
+        if relu:
+            _tap("conv_relu", y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        w = ctx.weight
+        xc = ctx.saved_tensors[0]
+        y = ctx.saved_tensors[1] if ctx.relu else None
+        gf = _f32(g)
+        gx = g_w = g_b = None
+        if ctx.needs_input_grad[0]:
+            gx = _conv2d_same(gf, _pack_conv(w, True), w.shape[1], w.shape[-1], None, False, mask=y)
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_b:
+            g_w, g_b = _conv2d_wgrad(xc, gf, y, w.shape[0], w.shape[-1], want_b)
+            if not ctx.needs_input_grad[1]:
+                g_w = None
+        return gx, g_w, g_b, None
+
+
+def conv2d_same_train(x, weight, bias, relu=False):
+    """Conv2d(stride 1, "same" zero padding, 3x3 or 5x5) [+ ReLU], differentiable w.r.t. input, weight and bias (TrainConv2d)."""
+    return TrainConv2d.apply(x, weight, bias, relu)
+
+
 class BicubicUpsample(torch.autograd.Function):
     """torch.nn.Upsample(size=(OH, OW), mode='bicubic') on a contiguous [B,C,h,w] image (DFM_APR_refine.py:114,118), optionally
     only the window `crop` pixels inside every border (the loop's `[:, :, 10:-10, 10:-10]`, :115,119: the cropped-away pixels are
@@ -1379,6 +1439,53 @@ def batch_norm_train_frozen(x, bn, per_image=False, track_stats=True):
     if not bn.training or any(p is not None and p.requires_grad for p in (bn.weight, bn.bias)):
         raise ValueError("nefes_amd: batch_norm_train_frozen is for a BatchNorm in train mode with frozen affine parameters")
     return BatchNormTrainFrozen.apply(x, bn, bool(per_image), bool(track_stats))
+
+
+class BatchNormTrain(torch.autograd.Function):
+    """BatchNormTrainFrozen for TRAINABLE affine parameters, statistics over the whole batch: the same forward (running statistics,
+    momentum, batch counter), and a backward that also returns the gradients of bn.weight and bn.bias (nefes_bn_train_bwd_affine: the
+    two float64 sums the input gradient is made of)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, track_stats):
+        xf = _f32(x)
+        B, Cc = xf.shape[0], xf.shape[1]
+        P = xf.numel() // (B * Cc)
+        y = torch.empty_like(xf)
+        save = torch.empty(Cc * 2, dtype=torch.float64, device=xf.device)
+        w, b = _f32(weight), _f32(bias)
+        track = bool(track_stats) and bn.track_running_stats and bn.running_mean is not None
+        momentum = 0.1
+        if track:
+            if bn.momentum is None:
+                raise NotImplementedError("nefes_amd: BatchNorm with momentum=None (cumulative average) takes the torch module")
+            momentum = float(bn.momentum)
+        L.check(L.load().nefes_bn_train_fwd(B, Cc, P, 0, _chk(xf, "x"), _chk(w, "weight"), _chk(b, "bias"), float(bn.eps), momentum,
+                                            _chk(bn.running_mean, "running_mean") if track else None, _chk(bn.running_var, "running_var") if track else None,
+                                            _chk(bn.num_batches_tracked, "num_batches_tracked", torch.int64) if track and bn.num_batches_tracked is not None else None,
+                                            _chk(y, "y"), _chk(save, "save", torch.float64), _stream()), "nefes_bn_train_fwd")
+        ctx.save_for_backward(xf, save, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        xf, save, w = ctx.saved_tensors
+        gf = _f32(g)
+        B, Cc = xf.shape[0], xf.shape[1]
+        g_x = torch.empty_like(xf) if ctx.needs_input_grad[0] else None
+        g_w, g_b = torch.empty_like(w), torch.empty_like(w)
+        L.check(L.load().nefes_bn_train_bwd_affine(B, Cc, xf.numel() // (B * Cc), _chk(xf, "x"), _chk(w, "weight"), _chk(save, "save", torch.float64),
+                                                   _chk(gf, "g_y"), _chk(g_x, "g_x"), _chk(g_w, "g_weight"), _chk(g_b, "g_bias"), _stream()),
+                "nefes_bn_train_bwd_affine")
+        return g_x, g_w if ctx.needs_input_grad[1] else None, g_b if ctx.needs_input_grad[2] else None, None, None
+
+
+def batch_norm_train(x, bn, track_stats=True):
+    """bn(x) for a torch.nn.BatchNorm2d in train mode with affine parameters, differentiable w.r.t. x, bn.weight and bn.bias
+    (BatchNormTrain; batch statistics over all images).  track_stats as in batch_norm_train_frozen."""
+    if not bn.training or bn.weight is None or bn.bias is None:
+        raise ValueError("nefes_amd: batch_norm_train is for a BatchNorm in train mode with affine parameters")
+    return BatchNormTrain.apply(x, bn.weight, bn.bias, bn, bool(track_stats))
 
 
 class SvdReg(torch.autograd.Function):
