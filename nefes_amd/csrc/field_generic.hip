@@ -17,20 +17,21 @@
 // backward's transposed product leaves the gradient of a layer's output in exactly the accumulator that produced it, so it tests the
 // same bit -- no recomputation of the forward (which would double the backward's matrix work) and 1 bit per activation of traffic.
 //
-// External encoding (nefes_field_fwd_generic_ext / nefes_field_bwd_generic_ext, NEFES_XYZ_EXTERNAL32): a third inclusion of the two
-// bodies with GEN_ARGS::ext set.  The E region is the caller's 32 features per sample (a hash grid's, gathered by the launches of
+// One kernel template per direction, gen_fwd_kernel<NCB, Args> / gen_bwd_kernel<NCB, Args>: NCB = TS / 32, Args = one of four
+// argument structs whose two constants select what the body compiles in (eight entry points, sixteen instances):
+//   GenArgs          nefes_field_{fwd,bwd}_generic             the frequency embedding of the position, inference
+//   GenArgsExt       nefes_field_{fwd,bwd}_generic_ext         ext
+//   GenArgsTrain     nefes_field_{fwd,bwd}_train_generic       train
+//   GenArgsExtTrain  nefes_field_{fwd,bwd}_train_generic_ext   ext and train
+// ext (NEFES_XYZ_EXTERNAL32): the E region is the caller's 32 features per sample (a hash grid's, gathered by the launches of
 // hashgrid.hip) instead of the 63-feature frequency embedding: 32 rows, no padding row, Kp = 32 for layer 1 and 32 + W for the skip
-// layer; the backward stores d loss / d encoding where the other instances apply the embedding's chain rule.
-//
-// Train mode (nefes_field_fwd_train_generic / nefes_field_bwd_train_generic): the same two bodies with TRAIN set also copy, from the
-// LDS buffers they sit in anyway, every weight-gradient operand to the train-layout buffers of csrc/train.hip (layout.h
-// nefes_train_off): the forward the embeddings and every hidden layer's OUTPUT (after ReLU) to `acts`, the backward the gradient
-// with respect to every layer's pre-activation to `dacts`.  nefes_train_dw_bias then forms dW = G X^T unchanged; the block ->
-// first-row map is gen_train_map (nefes_generic_train_row_offset).
-//
-// Train mode on a supplied encoding (nefes_field_fwd_train_generic_ext / nefes_field_bwd_train_generic_ext): the fourth inclusion,
-// TRAIN and ext both set.  The E block of `acts` is the caller's 32 features in natural order, so every later block starts 32 rows
-// earlier than on the frequency map (nefes_generic_train_row_offset_ext).
+// layer; the backward stores d loss / d encoding where the other instances apply the embedding's chain rule (gen_embed's overload,
+// gen_input_grads_ext).
+// train: the kernels also copy, from the LDS buffers they sit in anyway, every weight-gradient operand to the train-layout buffers
+// of csrc/train.hip (layout.h nefes_train_off): the forward the embeddings and every hidden layer's OUTPUT (after ReLU) to `acts`,
+// the backward the gradient with respect to every layer's pre-activation to `dacts`.  nefes_train_dw_bias then forms dW = G X^T
+// unchanged; the block -> first-row map is gen_train_map (nefes_generic_train_row_offset).  With ext the E block of `acts` is the
+// caller's 32 features in natural order, so every later block starts 32 rows earlier (nefes_generic_train_row_offset_ext).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -362,8 +363,10 @@ __device__ __forceinline__ float gen_coord(const GenArgs& a, long long m, int ax
 }
 
 // The direction embedding alone, for the instances on a supplied encoding: the second half of gen_embed and the second half of the
-// frequency backward's last loop (gen_dir_grad).  Those two keep their own copies: calling these from them compiles to different
-// instructions in the inference and TRAIN kernels, whose code adding this family must not move (tools/kernels_identical.py).
+// frequency backward's last loop (gen_dir_grad).  Those two keep their own copies.  Calling these from them gives the same bits
+// (same operations, same order, -ffp-contract=off) and the same register counts, but the compiler then lays out all eight backward
+// kernels differently from their first instructions on, and their times move: -15 % on the frequency embedding at (256, 8), +19 %
+// on a supplied encoding (profiles/generic_one_template/README.md).  Merge them together with a tuning of these kernels, not before.
 template <int NCB>
 __device__ __forceinline__ void gen_embed_dir(const GenArgs& a, long long m0, float* DV) {
     constexpr int TS = 32 * NCB;
@@ -531,49 +534,355 @@ __device__ __forceinline__ const GenTrain* gen_train_of(const Args& a) {
     else return nullptr;
 }
 
-#define GEN_KERNEL gen_fwd_kernel
-#define GEN_ARGS GenArgs
-#include "field_generic_fwd.inc"
-#undef GEN_KERNEL
-#undef GEN_ARGS
-#define GEN_KERNEL gen_fwd_train_kernel
-#define GEN_ARGS GenArgsTrain
-#include "field_generic_fwd.inc"
-#undef GEN_KERNEL
-#undef GEN_ARGS
-#define GEN_KERNEL gen_fwd_ext_kernel
-#define GEN_ARGS GenArgsExt
-#include "field_generic_fwd.inc"
-#undef GEN_KERNEL
-#undef GEN_ARGS
-#define GEN_KERNEL gen_fwd_ext_train_kernel
-#define GEN_ARGS GenArgsExtTrain
-#include "field_generic_fwd.inc"
-#undef GEN_KERNEL
-#undef GEN_ARGS
+// The forward kernel, one instance per argument struct and tile size.  Args::train: the same code plus the copies to the train
+// buffer; Args::ext: a supplied 32-feature encoding in the E region (ER = 32 rows, gen_embed's other overload).
+template <int NCB, class Args>
+__global__ __launch_bounds__(256, 1) void gen_fwd_kernel(Args a) {
+    constexpr int TS = 32 * NCB;
+    constexpr bool TRAIN = Args::train;
+    constexpr int ER = Args::ext ? GEN_X_ROWS : GEN_E_ROWS;      // rows of the E region
+    const GenTrain* const tr = gen_train_of(a);
+    extern __shared__ __attribute__((aligned(16))) float gen_smem[];
+    const GenLayout& g = a.g;
+    const int W = g.W, D = g.D, H = W / 2;
+    float* E = gen_smem;
+    float* DV = E + ER * TS;
+    float* X = DV + GEN_DV_ROWS * TS;
+    float* Y = X + W * TS;
+    const long long tile = blockIdx.x, m0 = tile * TS;
+    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
+    const float* blob = a.blob;
+    uint32_t* mk = a.masks ? a.masks + (tile * g.mask_words) * 64 + lane : nullptr;
+    if constexpr (TRAIN) {
+        if (m0 >= a.M) {      // (no mask words, no raw_t: neither buffer has room for this tile)
+            gen_train_zero<TS>(*tr, m0, 0, tr->map.off[NEFES_TB_RGB]);
+            return;
+        }
+    }
+
+    gen_embed<NCB>(a, m0, E, DV);
+    __syncthreads();
+    if constexpr (TRAIN) {
+        gen_train_store<TS>(*tr, m0, NEFES_TB_E, E, ER, ER);
+        gen_train_store<TS>(*tr, m0, NEFES_TB_DV, DV, GEN_DV_ROWS, GEN_DV_ROWS);
+    }
+
+    // hidden layer: ReLU, mask word, activations to LDS (rows beyond m_real are zero rows of the blob: relu(0) = 0)
+    auto hidden = [&](float* out, int slot) {
+        const int so = g.slot_off[slot];
+        return [=](int rb, f32x16(&acc)[NCB]) {
+            uint32_t bits = 0u;
+#pragma unroll
+            for (int c = 0; c < NCB; ++c)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float v = acc[c][r];
+                    bits |= (v > 0.f ? 1u : 0u) << (16 * c + r);
+                    out[(rb * 32 + gen_rho(half, r)) * TS + 32 * c + l31] = v > 0.f ? v : 0.f;
+                }
+            if (mk) mk[(so + rb) * 64] = bits;
+        };
+    };
+    auto linear = [&](float* out) {
+        return [=](int rb, f32x16(&acc)[NCB]) {
+#pragma unroll
+            for (int c = 0; c < NCB; ++c)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) out[(rb * 32 + gen_rho(half, r)) * TS + 32 * c + l31] = acc[c][r];
+        };
+    };
+    // raw_t[n][ch][s] of this lane's samples
+    long long base[NCB];
+    bool live[NCB];
+#pragma unroll
+    for (int c = 0; c < NCB; ++c) {
+        const long long m = m0 + 32 * c + l31;
+        live[c] = m < a.M;
+        base[c] = live[c] ? (m / a.S) * a.R * a.S + m % a.S : 0;
+    }
+    // head: kind 0 identity, 1 softplus, 2 transient (rows 0..2 sigmoid, 3..4 softplus)
+    float* const raw = a.raw_t;
+    const long long S64 = a.S;
+    auto head = [&](int ch0, int m_real, int kind) {
+        return [=](int rb, f32x16(&acc)[NCB]) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rb * 32 + gen_rho(half, r);
+                if (row >= m_real) continue;
+#pragma unroll
+                for (int c = 0; c < NCB; ++c) {
+                    if (!live[c]) continue;
+                    float v = acc[c][r];
+                    if (kind == 1 || (kind == 2 && row >= 3)) v = softplus_ref(v);
+                    else if (kind == 2) v = sigmoid_ref(v);
+                    raw[base[c] + (long long)(ch0 + row) * S64] = v;
+                }
+            }
+        };
+    };
+
+    float *cur = X, *oth = Y;
+    {
+        const GenLayer& l = g.L[0];
+        gen_layer<NCB>(blob + l.wt, E, ER, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, hidden(cur, 0));
+    }
+    __syncthreads();
+    // TRAIN: a layer's output is complete behind its barrier and its buffer is next written behind the following barrier: copy it out here
+    if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_L1, cur, W, W);
+    for (int i = 1; i < D; ++i) {
+        const GenLayer& l = g.L[i];
+        if (i == g.skip)
+            gen_layer<NCB>(blob + l.wt, E, ER, blob + l.wt + (long long)ER * l.Mp, cur, W, l.Mp, l.Mp, W / 32,
+                           blob + l.bias, hidden(oth, i));
+        else
+            gen_layer<NCB>(blob + l.wt, cur, W, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, hidden(oth, i));
+        float* t = cur; cur = oth; oth = t;
+        __syncthreads();
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_L1 + i, cur, W, W);
+    }
+    {
+        const GenLayer& l = g.L[g.iSIGMA];
+        const int ch = a.mode == NEFES_FIELD_SIGMA ? 0 : 3 + g.C;
+        gen_layer<NCB>(blob + l.wt, cur, W, nullptr, nullptr, 0, l.Mp, l.Mp, 1, blob + l.bias, head(ch, 1, 1));
+    }
+    if (a.mode == NEFES_FIELD_SIGMA) return;
+    {
+        const GenLayer& l = g.L[g.iFINAL];
+        gen_layer<NCB>(blob + l.wt, cur, W, nullptr, nullptr, 0, l.Mp, l.Mp, W / 32, blob + l.bias, linear(oth));
+    }
+    __syncthreads();
+    float *fin = oth, *gbuf = cur;
+    if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_FINAL, fin, W, W);
+    {
+        const GenLayer& l = g.L[g.iDIR];
+        gen_layer<NCB>(blob + l.wt, fin, W, blob + l.wt + (long long)W * l.Mp, DV, GEN_DV_ROWS, l.Mp, l.Mp, l.Mp / 32, blob + l.bias,
+                       hidden(gbuf, D));
+    }
+    __syncthreads();
+    if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_DIR, gbuf, g.L[g.iDIR].Mp, g.L[g.iDIR].Mp);
+    {
+        const GenLayer& l = g.L[g.iRGB];
+        gen_layer<NCB>(blob + l.wt, gbuf, H, nullptr, nullptr, 0, l.Mp, l.Mp, l.Mp / 32, blob + l.bias, head(0, 3 + g.C, 0));
+    }
+    if (a.mode != NEFES_FIELD_FULL) return;
+    __syncthreads();
+    {
+        const GenLayer& l = g.L[g.iT0];
+        gen_layer<NCB>(blob + l.wt, fin, W, blob + l.wt + (long long)W * l.Mp, DV, GEN_DV_ROWS, l.Mp, l.Mp, l.Mp / 32, blob + l.bias,
+                       hidden(gbuf, D + 1));
+    }
+    __syncthreads();
+    if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_T0, gbuf, g.L[g.iDIR].Mp, g.L[g.iDIR].Mp);
+    {
+        const GenLayer& l = g.L[g.iT1];
+        gen_layer<NCB>(blob + l.wt, gbuf, H, nullptr, nullptr, 0, l.Mp, l.Mp, l.Mp / 32, blob + l.bias, hidden(fin, D + 2));
+    }
+    __syncthreads();
+    if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_T1, fin, g.L[g.iDIR].Mp, g.L[g.iDIR].Mp);
+    {
+        const GenLayer& l = g.L[g.iT2];
+        gen_layer<NCB>(blob + l.wt, fin, H, nullptr, nullptr, 0, l.Mp, l.Mp, l.Mp / 32, blob + l.bias, hidden(gbuf, D + 3));
+    }
+    __syncthreads();
+    if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_T2, gbuf, g.L[g.iDIR].Mp, g.L[g.iDIR].Mp);
+    {
+        const GenLayer& l = g.L[g.iTH];
+        gen_layer<NCB>(blob + l.wt, gbuf, H, nullptr, nullptr, 0, l.Mp, l.Mp, 1, blob + l.bias, head(3 + g.C + 1, 5, 2));
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// backward to the inputs: mode FULL or STATIC.  TRAIN: also every layer's pre-activation gradient to `dacts`.  ext: to the encoding
-#define GEN_KERNEL gen_bwd_kernel
-#define GEN_ARGS GenArgs
-#include "field_generic_bwd.inc"
-#undef GEN_KERNEL
-#undef GEN_ARGS
-#define GEN_KERNEL gen_bwd_train_kernel
-#define GEN_ARGS GenArgsTrain
-#include "field_generic_bwd.inc"
-#undef GEN_KERNEL
-#undef GEN_ARGS
-#define GEN_KERNEL gen_bwd_ext_kernel
-#define GEN_ARGS GenArgsExt
-#include "field_generic_bwd.inc"
-#undef GEN_KERNEL
-#undef GEN_ARGS
-#define GEN_KERNEL gen_bwd_ext_train_kernel
-#define GEN_ARGS GenArgsExtTrain
-#include "field_generic_bwd.inc"
-#undef GEN_KERNEL
-#undef GEN_ARGS
+// The backward to the inputs: mode FULL or STATIC.  Args::train: also every layer's pre-activation gradient to `dacts`; Args::ext:
+// gE has ER = 32 rows and is stored as it is, no chain rule (gen_input_grads_ext).
+template <int NCB, class Args>
+__global__ __launch_bounds__(256, 1) void gen_bwd_kernel(Args a) {
+    constexpr int TS = 32 * NCB;
+    constexpr bool TRAIN = Args::train;
+    constexpr int ER = Args::ext ? GEN_X_ROWS : GEN_E_ROWS;      // rows of the E region
+    const GenTrain* const tr = gen_train_of(a);
+    extern __shared__ __attribute__((aligned(16))) float gen_smem[];
+    const GenLayout& g = a.g;
+    const int W = g.W, D = g.D, H = W / 2, C = g.C;
+    const int RB = W > GEN_HEAD_ROWS ? W : GEN_HEAD_ROWS;
+    float* gE = gen_smem;
+    float* gDV = gE + ER * TS;
+    float* A = gDV + GEN_DV_ROWS * TS;
+    float* B = A + RB * TS;
+    float* dsig = B + RB * TS;
+    const long long tile = blockIdx.x, m0 = tile * TS;
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+    const float* blob = a.blob;
+    const uint32_t* mk = a.masks + (tile * g.mask_words) * 64 + lane;
+    const bool full = a.mode == NEFES_FIELD_FULL;
+    if constexpr (TRAIN) {
+        if (m0 >= a.M) {      // (past the masks and the ray-gradient buffers: zeros for the weight-gradient sums, nothing else)
+            gen_train_zero<TS>(*tr, m0, tr->map.off[NEFES_TB_L1], tr->map.off[NEFES_TB_END]);
+            return;
+        }
+    }
+
+    // this thread's sample column for the cooperative loads (256 % TS == 0: the same for every row it touches)
+    const int s_ld = tid % TS, row_ld = tid / TS;
+    const long long m_ld = m0 + s_ld;
+    const bool live_ld = m_ld < a.M;
+    const long long base_ld = live_ld ? (m_ld / a.S) * a.R * a.S + m_ld % a.S : 0;
+    // rows [0, rows_p) of `dst` = d loss / d (pre-activation) of head channels ch0 .. ch0 + m_real - 1; kind as in the forward
+    auto load_head = [&](float* dst, int ch0, int m_real, int rows_p, int kind) {
+        for (int row = row_ld; row < rows_p; row += 256 / TS) {
+            float v = 0.f;
+            if (live_ld && row < m_real) {
+                const long long at = base_ld + (long long)(ch0 + row) * a.S;
+                v = a.g_raw_t[at];
+                if (kind == 1 || (kind == 2 && row >= 3)) v *= 1.f - expf(-a.raw_in[at]);
+                else if (kind == 2) { const float y = a.raw_in[at]; v *= y * (1.f - y); }
+            }
+            dst[row * TS + s_ld] = v;
+        }
+    };
+    // gradient of a hidden layer's output: keep where the forward's pre-activation was positive; rows < m_real only
+    auto masked = [&](float* out, int slot, int m_real, const float* wsig) {
+        const int so = g.slot_off[slot];
+        return [=](int rb, f32x16(&acc)[NCB]) {
+            const uint32_t bits = mk[(so + rb) * 64];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rb * 32 + gen_rho(half, r);
+                if (row >= m_real) continue;
+                const float ws = wsig ? wsig[row] : 0.f;
+#pragma unroll
+                for (int c = 0; c < NCB; ++c) {
+                    float v = acc[c][r];
+                    if (wsig) v += ws * dsig[32 * c + l31];
+                    out[row * TS + 32 * c + l31] = ((bits >> (16 * c + r)) & 1u) ? v : 0.f;
+                }
+            }
+        };
+    };
+    auto plain = [&](float* out, int m_real, bool accumulate) {
+        return [=](int rb, f32x16(&acc)[NCB]) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = rb * 32 + gen_rho(half, r);
+                if (row >= m_real) continue;
+#pragma unroll
+                for (int c = 0; c < NCB; ++c) {
+                    float* p = out + row * TS + 32 * c + l31;
+                    *p = accumulate ? *p + acc[c][r] : acc[c][r];
+                }
+            }
+        };
+    };
+    const int HB = (H + 31) / 32;
+
+    if (tid < TS) {      // d loss / d (static density's pre-activation): a rank-1 term of the trunk's last gradient
+        float v = 0.f;
+        if (live_ld) {
+            const long long at = base_ld + (long long)(3 + C) * a.S;
+            v = a.g_raw_t[at] * (1.f - expf(-a.raw_in[at]));
+        }
+        dsig[tid] = v;
+    }
+    if (full) {
+        const GenLayer &th = g.L[g.iTH], &t2 = g.L[g.iT2], &t1 = g.L[g.iT1];
+        load_head(A, 3 + C + 1, 5, 32, 2);
+        __syncthreads();
+        // TRAIN: a gradient block is final behind its barrier and its buffer is next written behind the following one: copy it out here
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_TH, A, 32, 32);
+        gen_layer<NCB>(blob + th.wb, A, 32, nullptr, nullptr, 0, th.Kp, H, HB, nullptr, masked(B, D + 3, H, nullptr));
+        __syncthreads();
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_T2, B, H, 32 * HB);
+        gen_layer<NCB>(blob + t2.wb, B, H, nullptr, nullptr, 0, t2.Kp, H, HB, nullptr, masked(A, D + 2, H, nullptr));
+        __syncthreads();
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_T1, A, H, 32 * HB);
+        gen_layer<NCB>(blob + t1.wb, A, H, nullptr, nullptr, 0, t1.Kp, H, HB, nullptr, masked(B, D + 1, H, nullptr));
+        __syncthreads();
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_T0, B, H, 32 * HB);
+    }
+    {
+        const GenLayer& rgb = g.L[g.iRGB];
+        load_head(A, 0, 3 + C, rgb.Mp, 0);
+        __syncthreads();
+        if constexpr (TRAIN) {
+            gen_train_store<TS>(*tr, m0, NEFES_TB_RGB, A, rgb.Mp, rgb.Mp);
+            gen_train_store<TS>(*tr, m0, NEFES_TB_SIG, dsig, 1, 32);
+        }
+        gen_layer<NCB>(blob + rgb.wb, A, rgb.Mp, nullptr, nullptr, 0, rgb.Kp, H, HB, nullptr, masked(B + H * TS, D, H, nullptr));
+        __syncthreads();
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_DIR, B + H * TS, H, 32 * HB);
+    }
+    {
+        // d loss / d [final, direction embedding] = DIR^T g_g (+ T0^T g_t0)
+        const GenLayer& dir = g.L[g.iDIR];
+        const float* w0 = blob + dir.wb;
+        const float* in0 = B + H * TS;
+        const float *w1 = nullptr, *in1 = nullptr;
+        int K1 = 0;
+        if (full) { w1 = blob + g.L[g.iT0].wb; in1 = B; K1 = H; }
+        gen_layer<NCB>(w0, in0, H, w1, in1, K1, dir.Kp, W, W / 32, nullptr, plain(A, W, false));
+        gen_layer<NCB>(w0 + W, in0, H, w1 ? w1 + W : nullptr, in1, K1, dir.Kp, GEN_DV_ROWS, 1, nullptr, plain(gDV, GEN_DV_ROWS, false));
+        __syncthreads();
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_FINAL, A, W, W);
+    }
+    {
+        const GenLayer &fin = g.L[g.iFINAL], &sg = g.L[g.iSIGMA];
+        gen_layer<NCB>(blob + fin.wb, A, W, nullptr, nullptr, 0, fin.Kp, W, W / 32, nullptr, masked(B, D - 1, W, blob + sg.wb));
+        __syncthreads();
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_L1 + D - 1, B, W, W);
+    }
+    float *cur = B, *oth = A;
+    const bool have_skip = g.skip > 0 && g.skip < D;
+    for (int i = D - 1; i >= 1; --i) {
+        const GenLayer& l = g.L[i];
+        const int hoff = i == g.skip ? ER : 0;
+        gen_layer<NCB>(blob + l.wb + hoff, cur, W, nullptr, nullptr, 0, l.Kp, W, W / 32, nullptr, masked(oth, i - 1, W, nullptr));
+        if (i == g.skip)
+            gen_layer<NCB>(blob + l.wb, cur, W, nullptr, nullptr, 0, l.Kp, ER, ER / 32, nullptr, plain(gE, ER, false));
+        float* t = cur; cur = oth; oth = t;
+        __syncthreads();
+        if constexpr (TRAIN) gen_train_store<TS>(*tr, m0, NEFES_TB_L1 + i - 1, cur, W, W);
+    }
+    {
+        const GenLayer& l = g.L[0];
+        gen_layer<NCB>(blob + l.wb, cur, W, nullptr, nullptr, 0, l.Kp, ER, ER / 32, nullptr, plain(gE, ER, have_skip));
+        __syncthreads();
+    }
+    if constexpr (Args::ext) {
+        gen_input_grads_ext<NCB>(a, m0, gE, gDV);
+        return;
+    }
+    // through the embeddings: d sin(f x) = f cos(f x), d cos(f x) = -f sin(f x)
+    for (int i = tid; i < 3 * TS; i += 256) {
+        const int s = i % TS, axis = i / TS;
+        const long long m = m0 + s;
+        if (m >= a.M) continue;
+        {
+            const float x = gen_coord(a, m, axis);
+            uint32_t hi, lo;
+            turns_fixed(x, hi, lo);
+            float gx = gE[axis * TS + s];
+            for (int k = 0; k < 10; ++k) {
+                const uint32_t ph = phase_of(hi, lo, k);
+                const float f = (float)(1 << k);
+                gx += gE[(3 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x40000000u));
+                gx += gE[(6 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x80000000u));
+            }
+            a.g_pts[m * 3 + axis] = gx;
+        }
+        {
+            const float x = a.viewdirs[(m / a.S) * 3 + axis];
+            uint32_t hi, lo;
+            turns_fixed(x, hi, lo);
+            float gx = gDV[axis * TS + s];
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t ph = phase_of(hi, lo, k);
+                const float f = (float)(1 << k);
+                gx += gDV[(3 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x40000000u));
+                gx += gDV[(6 + 6 * k + axis) * TS + s] * (f * sin_phase(ph + 0x80000000u));
+            }
+            a.g_vs[m * 3 + axis] = gx;
+        }
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 template <class K, class Args>
@@ -585,8 +894,7 @@ static int gen_launch(K k, const Args& a, size_t lds, long long n_tiles, hipStre
     return (int)hipGetLastError();
 }
 
-static int gen_fill(GenArgs& a, const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
-                    int xyz_encoding = NEFES_XYZ_FREQ10) {
+static int gen_fill(GenArgs& a, const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, int xyz_encoding) {
     int rc = gen_layout(desc, &a.g);
     if (rc) return rc;
     if (desc->xyz_encoding != xyz_encoding) return NEFES_E_UNSUPPORTED;      // each entry point serves one encoding
@@ -600,92 +908,7 @@ static int gen_fill(GenArgs& a, const NefesGenericNetDesc* desc, const void* pac
     return 0;
 }
 
-extern "C" int nefes_field_fwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
-                                       const float* rays_o, const float* rays_d, const float* z, const float* pts,
-                                       const float* viewdirs, float* raw_t, uint32_t* masks, void* stream) {
-    if (!desc || !packed || !raw_t || N <= 0 || S <= 0) return NEFES_E_BADARG;
-    if (!pts && !(rays_o && rays_d && z)) return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_SIGMA && !viewdirs) return NEFES_E_BADARG;
-    GenArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = gen_fill(a, desc, packed, mode, N, S);
-    if (rc) return rc;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts;
-    a.viewdirs = mode == NEFES_FIELD_SIGMA ? nullptr : viewdirs;
-    a.raw_t = raw_t; a.masks = masks;
-    const int TS = gen_tile(a.g.W);
-    const size_t lds = (size_t)(GEN_E_ROWS + GEN_DV_ROWS + 2 * a.g.W) * TS * 4;
-    const long long n_tiles = (a.M + TS - 1) / TS;
-    if (TS == 64) return gen_launch(gen_fwd_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
-    return gen_launch(gen_fwd_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
-}
-
-extern "C" int nefes_field_bwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
-                                       const float* rays_o, const float* rays_d, const float* z, const float* pts,
-                                       const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
-                                       float* g_pts, float* g_viewdirs_s, void* stream) {
-    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !g_pts || !g_viewdirs_s || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
-    if (!pts && !(rays_o && rays_d && z)) return NEFES_E_BADARG;
-    if (mode == NEFES_FIELD_SIGMA) return NEFES_E_BADARG;
-    GenArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = gen_fill(a, desc, packed, mode, N, S);
-    if (rc) return rc;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.viewdirs = viewdirs;
-    a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
-    a.g_pts = g_pts; a.g_vs = g_viewdirs_s;
-    const int TS = gen_tile(a.g.W);
-    const int RB = a.g.W > GEN_HEAD_ROWS ? a.g.W : GEN_HEAD_ROWS;
-    const size_t lds = (size_t)(GEN_E_ROWS + GEN_DV_ROWS + 2 * RB + 1) * TS * 4;
-    const long long n_tiles = (a.M + TS - 1) / TS;
-    if (TS == 64) return gen_launch(gen_bwd_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
-    return gen_launch(gen_bwd_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
-}
-
-// ---- a supplied encoding -----------------------------------------------------------------------------------------------------------
-// (the E region is GEN_X_ROWS rows: the GEN_E_ROWS - GEN_X_ROWS rows it does not have are not requested)
-extern "C" int nefes_field_fwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
-                                           const float* xyz_enc, const float* viewdirs, float* raw_t, uint32_t* masks, void* stream) {
-    if (!desc || !packed || !xyz_enc || !raw_t || N <= 0 || S <= 0) return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_SIGMA && !viewdirs) return NEFES_E_BADARG;
-    GenArgsExt a;
-    memset(&a, 0, sizeof(a));
-    int rc = gen_fill(a, desc, packed, mode, N, S, NEFES_XYZ_EXTERNAL32);
-    if (rc) return rc;
-    if ((uintptr_t)xyz_enc & 15) return NEFES_E_BADARG;
-    a.xyz_enc = xyz_enc;
-    a.viewdirs = mode == NEFES_FIELD_SIGMA ? nullptr : viewdirs;
-    a.raw_t = raw_t; a.masks = masks;
-    const int TS = gen_tile(a.g.W);
-    const size_t lds = (size_t)(GEN_X_ROWS + GEN_DV_ROWS + 2 * a.g.W) * TS * 4;
-    const long long n_tiles = (a.M + TS - 1) / TS;
-    if (TS == 64) return gen_launch(gen_fwd_ext_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
-    return gen_launch(gen_fwd_ext_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
-}
-
-extern "C" int nefes_field_bwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
-                                           const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
-                                           float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
-    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !g_xyz_enc || !g_viewdirs_s || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
-    if (mode == NEFES_FIELD_SIGMA) return NEFES_E_BADARG;
-    GenArgsExt a;
-    memset(&a, 0, sizeof(a));
-    int rc = gen_fill(a, desc, packed, mode, N, S, NEFES_XYZ_EXTERNAL32);
-    if (rc) return rc;
-    if ((uintptr_t)g_xyz_enc & 15) return NEFES_E_BADARG;
-    a.viewdirs = viewdirs;
-    a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
-    a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
-    const int TS = gen_tile(a.g.W);
-    const int RB = a.g.W > GEN_HEAD_ROWS ? a.g.W : GEN_HEAD_ROWS;
-    const size_t lds = (size_t)(GEN_X_ROWS + GEN_DV_ROWS + 2 * RB + 1) * TS * 4;
-    const long long n_tiles = (a.M + TS - 1) / TS;
-    if (TS == 64) return gen_launch(gen_bwd_ext_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
-    return gen_launch(gen_bwd_ext_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
-}
-
-// ---- train mode ------------------------------------------------------------------------------------------------------------------
-static int gen_fill_train(GenTrain& t, const NefesGenericNetDesc* desc, float* buf, int xyz_encoding = NEFES_XYZ_FREQ10) {
+static int gen_fill_train(GenTrain& t, const NefesGenericNetDesc* desc, float* buf, int xyz_encoding) {
     t.buf = buf;
     const int rc = gen_train_map(desc, xyz_encoding, &t.map);
     t.rows = t.map.off[NEFES_TB_END];
@@ -695,25 +918,104 @@ static int gen_fill_train(GenTrain& t, const NefesGenericNetDesc* desc, float* b
 // whole 128-sample train tiles: the tiles past the last sample write zeros (gen_train_zero)
 static long long gen_train_tiles(long long M, int TS) { return (M + 127) / 128 * (128 / TS); }
 
+// forward: E, DV and the two activation buffers; backward: gE, gDV, two gradient buffers that also hold the heads' rows, dsig.
+// (On a supplied encoding the E region is GEN_X_ROWS rows: the GEN_E_ROWS - GEN_X_ROWS rows it does not have are not requested.)
+static size_t gen_lds_bytes(bool ext, bool bwd, int W, int TS) {
+    const int ER = ext ? GEN_X_ROWS : GEN_E_ROWS;
+    const int RB = W > GEN_HEAD_ROWS ? W : GEN_HEAD_ROWS;
+    return (size_t)(ER + GEN_DV_ROWS + (bwd ? 2 * RB + 1 : 2 * W)) * TS * 4;
+}
+
+// Everything behind an entry point's own test of its pointers, sizes and mode, on `a` with that call's pointers in place: the layout,
+// the train buffer's row map (train_buf = `acts` / `dacts`; Args::train), the 16-byte alignment of the buffers a supplied encoding
+// is moved through as float4 (Args::ext), LDS size, tile count, the instance of the tile size.
+template <bool BWD, class Args>
+static int gen_run(Args& a, const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S, float* train_buf, void* stream) {
+    constexpr int enc = Args::ext ? NEFES_XYZ_EXTERNAL32 : NEFES_XYZ_FREQ10;
+    int rc = gen_fill(a, desc, packed, mode, N, S, enc);
+    if (rc) return rc;
+    if constexpr (Args::train) {
+        rc = gen_fill_train(a.t, desc, train_buf, enc);
+        if (rc) return rc;
+    }
+    if constexpr (Args::ext) {
+        uintptr_t p = (uintptr_t)(BWD ? (const float*)a.g_enc : a.xyz_enc);
+        if constexpr (Args::train) p |= (uintptr_t)train_buf;
+        if (p & 15) return NEFES_E_BADARG;
+    }
+    const int TS = gen_tile(a.g.W);
+    const size_t lds = gen_lds_bytes(Args::ext, BWD, a.g.W, TS);
+    const long long n_tiles = Args::train ? gen_train_tiles(a.M, TS) : (a.M + TS - 1) / TS;
+    if (TS == 64) return gen_launch(BWD ? gen_bwd_kernel<2, Args> : gen_fwd_kernel<2, Args>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_launch(BWD ? gen_bwd_kernel<1, Args> : gen_fwd_kernel<1, Args>, a, lds, n_tiles, (hipStream_t)stream);
+}
+
+// ---- inference: the frequency embedding, then a supplied encoding ---------------------------------------------------------------------
+extern "C" int nefes_field_fwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                       const float* rays_o, const float* rays_d, const float* z, const float* pts,
+                                       const float* viewdirs, float* raw_t, uint32_t* masks, void* stream) {
+    if (!desc || !packed || !raw_t || N <= 0 || S <= 0 || (!pts && !(rays_o && rays_d && z)) || (mode != NEFES_FIELD_SIGMA && !viewdirs))
+        return NEFES_E_BADARG;
+    GenArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts;
+    a.viewdirs = mode == NEFES_FIELD_SIGMA ? nullptr : viewdirs;
+    a.raw_t = raw_t; a.masks = masks;
+    return gen_run<false>(a, desc, packed, mode, N, S, nullptr, stream);
+}
+
+extern "C" int nefes_field_bwd_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                       const float* rays_o, const float* rays_d, const float* z, const float* pts,
+                                       const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
+                                       float* g_pts, float* g_viewdirs_s, void* stream) {
+    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !g_pts || !g_viewdirs_s || !viewdirs || N <= 0 || S <= 0 ||
+        (!pts && !(rays_o && rays_d && z)) || mode == NEFES_FIELD_SIGMA)
+        return NEFES_E_BADARG;
+    GenArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.pts = pts; a.viewdirs = viewdirs;
+    a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
+    a.g_pts = g_pts; a.g_vs = g_viewdirs_s;
+    return gen_run<true>(a, desc, packed, mode, N, S, nullptr, stream);
+}
+
+extern "C" int nefes_field_fwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                           const float* xyz_enc, const float* viewdirs, float* raw_t, uint32_t* masks, void* stream) {
+    if (!desc || !packed || !xyz_enc || !raw_t || N <= 0 || S <= 0 || (mode != NEFES_FIELD_SIGMA && !viewdirs)) return NEFES_E_BADARG;
+    GenArgsExt a;
+    memset(&a, 0, sizeof(a));
+    a.xyz_enc = xyz_enc;
+    a.viewdirs = mode == NEFES_FIELD_SIGMA ? nullptr : viewdirs;
+    a.raw_t = raw_t; a.masks = masks;
+    return gen_run<false>(a, desc, packed, mode, N, S, nullptr, stream);
+}
+
+extern "C" int nefes_field_bwd_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
+                                           const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
+                                           float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
+    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !g_xyz_enc || !g_viewdirs_s || !viewdirs || N <= 0 || S <= 0 ||
+        mode == NEFES_FIELD_SIGMA)
+        return NEFES_E_BADARG;
+    GenArgsExt a;
+    memset(&a, 0, sizeof(a));
+    a.viewdirs = viewdirs;
+    a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
+    a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
+    return gen_run<true>(a, desc, packed, mode, N, S, nullptr, stream);
+}
+
+// ---- train mode: the same two pairs with the train buffer (`acts` / `dacts`), rays only, mode STATIC or FULL ----------------------------
 extern "C" int nefes_field_fwd_train_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
                                              const float* rays_o, const float* rays_d, const float* z, const float* viewdirs,
                                              float* raw_t, float* acts, uint32_t* masks, void* stream) {
-    if (!desc || !packed || !raw_t || !acts || !masks || !viewdirs || !rays_o || !rays_d || !z || N <= 0 || S <= 0) return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
+    if (!desc || !packed || !raw_t || !acts || !masks || !viewdirs || !rays_o || !rays_d || !z || N <= 0 || S <= 0 ||
+        (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL))
+        return NEFES_E_BADARG;
     GenArgsTrain a;
     memset(&a, 0, sizeof(a));
-    int rc = gen_fill(a, desc, packed, mode, N, S);
-    if (rc) return rc;
-    GenTrain& t = a.t;
-    rc = gen_fill_train(t, desc, acts);
-    if (rc) return rc;
     a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.viewdirs = viewdirs;
     a.raw_t = raw_t; a.masks = masks;
-    const int TS = gen_tile(a.g.W);
-    const size_t lds = (size_t)(GEN_E_ROWS + GEN_DV_ROWS + 2 * a.g.W) * TS * 4;
-    const long long n_tiles = gen_train_tiles(a.M, TS);
-    if (TS == 64) return gen_launch(gen_fwd_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
-    return gen_launch(gen_fwd_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_run<false>(a, desc, packed, mode, N, S, acts, stream);
 }
 
 extern "C" int nefes_field_bwd_train_generic(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
@@ -721,69 +1023,39 @@ extern "C" int nefes_field_bwd_train_generic(const NefesGenericNetDesc* desc, co
                                              const float* raw_t, const float* g_raw_t, const uint32_t* masks, float* dacts, float* g_pts,
                                              float* g_viewdirs_s, void* stream) {
     if (!desc || !packed || !raw_t || !g_raw_t || !masks || !dacts || !g_pts || !g_viewdirs_s || !viewdirs || !rays_o || !rays_d || !z ||
-        N <= 0 || S <= 0)
+        N <= 0 || S <= 0 || (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL))
         return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
     GenArgsTrain a;
     memset(&a, 0, sizeof(a));
-    int rc = gen_fill(a, desc, packed, mode, N, S);
-    if (rc) return rc;
-    GenTrain& t = a.t;
-    rc = gen_fill_train(t, desc, dacts);
-    if (rc) return rc;
     a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.viewdirs = viewdirs;
     a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
     a.g_pts = g_pts; a.g_vs = g_viewdirs_s;
-    const int TS = gen_tile(a.g.W);
-    const int RB = a.g.W > GEN_HEAD_ROWS ? a.g.W : GEN_HEAD_ROWS;
-    const size_t lds = (size_t)(GEN_E_ROWS + GEN_DV_ROWS + 2 * RB + 1) * TS * 4;
-    const long long n_tiles = gen_train_tiles(a.M, TS);
-    if (TS == 64) return gen_launch(gen_bwd_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
-    return gen_launch(gen_bwd_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_run<true>(a, desc, packed, mode, N, S, dacts, stream);
 }
 
-// ---- train mode on a supplied encoding: the checks of the _ext pair, the buffers and the launch of the train pair ------------------
 extern "C" int nefes_field_fwd_train_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
                                                  const float* xyz_enc, const float* viewdirs, float* raw_t, float* acts, uint32_t* masks,
                                                  void* stream) {
-    if (!desc || !packed || !xyz_enc || !raw_t || !acts || !masks || !viewdirs || N <= 0 || S <= 0) return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
+    if (!desc || !packed || !xyz_enc || !raw_t || !acts || !masks || !viewdirs || N <= 0 || S <= 0 ||
+        (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL))
+        return NEFES_E_BADARG;
     GenArgsExtTrain a;
     memset(&a, 0, sizeof(a));
-    int rc = gen_fill(a, desc, packed, mode, N, S, NEFES_XYZ_EXTERNAL32);
-    if (rc) return rc;
-    rc = gen_fill_train(a.t, desc, acts, NEFES_XYZ_EXTERNAL32);
-    if (rc) return rc;
-    if (((uintptr_t)xyz_enc | (uintptr_t)acts) & 15) return NEFES_E_BADARG;
     a.xyz_enc = xyz_enc; a.viewdirs = viewdirs;
     a.raw_t = raw_t; a.masks = masks;
-    const int TS = gen_tile(a.g.W);
-    const size_t lds = (size_t)(GEN_X_ROWS + GEN_DV_ROWS + 2 * a.g.W) * TS * 4;
-    const long long n_tiles = gen_train_tiles(a.M, TS);
-    if (TS == 64) return gen_launch(gen_fwd_ext_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
-    return gen_launch(gen_fwd_ext_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_run<false>(a, desc, packed, mode, N, S, acts, stream);
 }
 
 extern "C" int nefes_field_bwd_train_generic_ext(const NefesGenericNetDesc* desc, const void* packed, int mode, int N, int S,
                                                  const float* viewdirs, const float* raw_t, const float* g_raw_t, const uint32_t* masks,
                                                  float* dacts, float* g_xyz_enc, float* g_viewdirs_s, void* stream) {
-    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !dacts || !g_xyz_enc || !g_viewdirs_s || !viewdirs || N <= 0 || S <= 0)
+    if (!desc || !packed || !raw_t || !g_raw_t || !masks || !dacts || !g_xyz_enc || !g_viewdirs_s || !viewdirs || N <= 0 || S <= 0 ||
+        (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL))
         return NEFES_E_BADARG;
-    if (mode != NEFES_FIELD_STATIC && mode != NEFES_FIELD_FULL) return NEFES_E_BADARG;
     GenArgsExtTrain a;
     memset(&a, 0, sizeof(a));
-    int rc = gen_fill(a, desc, packed, mode, N, S, NEFES_XYZ_EXTERNAL32);
-    if (rc) return rc;
-    rc = gen_fill_train(a.t, desc, dacts, NEFES_XYZ_EXTERNAL32);
-    if (rc) return rc;
-    if (((uintptr_t)g_xyz_enc | (uintptr_t)dacts) & 15) return NEFES_E_BADARG;
     a.viewdirs = viewdirs;
     a.raw_in = raw_t; a.g_raw_t = g_raw_t; a.masks = const_cast<uint32_t*>(masks);
     a.g_enc = g_xyz_enc; a.g_vs = g_viewdirs_s;
-    const int TS = gen_tile(a.g.W);
-    const int RB = a.g.W > GEN_HEAD_ROWS ? a.g.W : GEN_HEAD_ROWS;
-    const size_t lds = (size_t)(GEN_X_ROWS + GEN_DV_ROWS + 2 * RB + 1) * TS * 4;
-    const long long n_tiles = gen_train_tiles(a.M, TS);
-    if (TS == 64) return gen_launch(gen_bwd_ext_train_kernel<2>, a, lds, n_tiles, (hipStream_t)stream);
-    return gen_launch(gen_bwd_ext_train_kernel<1>, a, lds, n_tiles, (hipStream_t)stream);
+    return gen_run<true>(a, desc, packed, mode, N, S, dacts, stream);
 }

@@ -493,32 +493,61 @@ def _param_grads_generic(pk, mode, acts, dacts):
     return g
 
 
-def weight_grads_generic(net, pk, mode, N, S, raw_t, g_raw_t, acts, o, d, v, zz, masks):
-    """weight_grads on the generic kernels: one fused backward launch (ray gradients + every layer's pre-activation gradient to
-    `dacts`), then the weight gradients of _param_grads_generic."""
-    dev = acts.device
-    dacts = torch.empty_like(acts)
-    g_pts, g_vs = torch.empty(N * S, 3, device=dev), torch.empty(N * S, 3, device=dev)
-    L.check(L.load().nefes_field_bwd_train_generic(pk.desc, pk.blob.data_ptr(), mode, N, S, o.data_ptr(), d.data_ptr(), zz.data_ptr(),
-                                                   v.data_ptr(), raw_t.data_ptr(), g_raw_t.data_ptr(), masks.data_ptr(), dacts.data_ptr(),
-                                                   g_pts.data_ptr(), g_vs.data_ptr(), ops._stream()), "nefes_field_bwd_train_generic")
-    g = _param_grads_generic(pk, mode, acts, dacts)
-    g["__rays__"] = (g_pts, g_vs)
-    return g
+def _generic_entry(direction, ext):
+    """(C entry point, timer key) of the train-mode launch of `direction` ("fwd" / "bwd") on the frequency embedding or a supplied encoding"""
+    return f"nefes_field_{direction}_train_generic" + ("_ext" if ext else ""), f"field_{direction}_train[generic" + (",ext]" if ext else "]")
 
 
-def weight_grads_generic_encoded(net, pk, mode, N, S, raw_t, g_raw_t, acts, v, masks, want_w=True):
-    """weight_grads_generic for a pack on a supplied encoding: "__rays__" holds (d encoding [N*S, 32], d viewdirs per sample).
-    want_w=False: the backward launch alone (no parameter gradients)."""
-    dev = acts.device
-    dacts = torch.empty_like(acts)
-    g_enc, g_vs = torch.empty(N * S, 32, device=dev), torch.empty(N * S, 3, device=dev)
-    L.check(L.load().nefes_field_bwd_train_generic_ext(pk.desc, pk.blob.data_ptr(), mode, N, S, v.data_ptr(), raw_t.data_ptr(),
-                                                       g_raw_t.data_ptr(), masks.data_ptr(), dacts.data_ptr(), g_enc.data_ptr(),
-                                                       g_vs.data_ptr(), ops._stream()), "nefes_field_bwd_train_generic_ext")
-    g = _param_grads_generic(pk, mode, acts, dacts) if want_w else {}
-    g["__rays__"] = (g_enc, g_vs)
-    return g
+def _generic_train_pack(net, mode, ext):
+    """net.packed_generic() once train mode can evaluate `mode` on it (ext: on a supplied encoding)."""
+    pk = net.packed_generic()
+    L.load()
+    if mode not in (L.FIELD_STATIC, L.FIELD_FULL):
+        raise ValueError("nefes_amd: train mode evaluates the static or the full head")
+    if mode == L.FIELD_FULL and not pk.has_transient:
+        raise ValueError("nefes_amd: the full head of a network without a transient head")
+    if ext and pk.xyz_encoding != L.XYZ_EXTERNAL32:
+        raise RuntimeError(f"nefes_amd: train mode on a supplied encoding needs a network with in_channels_xyz=32; got {net._shape()}")
+    return pk
+
+
+def _generic_train_forward(ctx, net, pk, mode, N, S, ext, inputs, save):
+    """The forward of both generic train Functions: one launch on `inputs` ((name, tensor) in the entry point's order) -> raw_t
+    [N,R,S]; ctx keeps (raw_t, acts, *save, masks) for the backward."""
+    dev = inputs[0][1].device
+    entry, key = _generic_entry("fwd", ext)
+    _generic_buffers_fit(pk, N, S, dev)
+    rows, off = pk.train_rows()
+    raw_t = torch.empty(N, pk.n_raw(mode), S, device=dev)
+    acts = torch.empty((N * S + 127) // 128, rows, 128, device=dev)
+    masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=dev)
+    with ops._timed(key):
+        L.check(getattr(L.load(), entry)(pk.desc, pk.blob.data_ptr(), mode, N, S, *[ops._chk(t, n) for n, t in inputs], raw_t.data_ptr(),
+                                         acts.data_ptr(), masks.data_ptr(), ops._stream()), entry)
+    ops._tap("masks_generic", (masks, N, S, pk, mode))
+    ctx.save_for_backward(raw_t, acts, *save, masks)
+    if DEBUG is not None:
+        DEBUG.update(acts=rows_view(acts), rows=rows, off=dict(enumerate(off)))
+    ctx.net, ctx.pk, ctx.mode, ctx.NS, ctx.pk_gen = net, pk, mode, (N, S), pk.generation
+    return raw_t
+
+
+def _generic_train_backward(ctx, g_raw_t, ext, inputs, want_w=True):
+    """The backward of both: one fused launch on `inputs` (in the entry point's order; input gradients + every layer's
+    pre-activation gradient to `dacts`), then the weight gradients of _param_grads_generic unless want_w is false.  -> (those,
+    d loss / d positions [N*S, 3] or d encoding [N*S, 32], d viewdirs per sample)."""
+    raw_t, acts, masks = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[-1]
+    pk, mode, (N, S), dev = ctx.pk, ctx.mode, ctx.NS, acts.device
+    entry, key = _generic_entry("bwd", ext)
+    with ops._timed(key):
+        g_raw_t = ops._f32(g_raw_t)
+        dacts = torch.empty_like(acts)
+        g_in, g_vs = torch.empty(N * S, 32 if ext else 3, device=dev), torch.empty(N * S, 3, device=dev)
+        L.check(getattr(L.load(), entry)(pk.desc, pk.blob.data_ptr(), mode, N, S, *[t.data_ptr() for t in inputs], raw_t.data_ptr(),
+                                         g_raw_t.data_ptr(), masks.data_ptr(), dacts.data_ptr(), g_in.data_ptr(), g_vs.data_ptr(),
+                                         ops._stream()), entry)
+        g = _param_grads_generic(pk, mode, acts, dacts) if want_w else {}
+    return g, g_in, g_vs
 
 
 class FieldTrainGeneric(torch.autograd.Function):
@@ -527,40 +556,20 @@ class FieldTrainGeneric(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, viewdirs, z, net, mode, *params):
-        pk = net.packed_generic()
-        lib = L.load()
-        if mode not in (L.FIELD_STATIC, L.FIELD_FULL):
-            raise ValueError("nefes_amd: train mode evaluates the static or the full head")
-        if mode == L.FIELD_FULL and not pk.has_transient:
-            raise ValueError("nefes_amd: the full head of a network without a transient head")
+        pk = _generic_train_pack(net, mode, ext=False)
         o, d, v, zz = ops._f32(rays_o), ops._f32(rays_d), ops._f32(viewdirs), ops._f32(z)
         N, S = zz.shape
-        _generic_buffers_fit(pk, N, S, zz.device)
-        rows, off = pk.train_rows()
-        raw_t = torch.empty(N, pk.n_raw(mode), S, device=zz.device)
-        acts = torch.empty((N * S + 127) // 128, rows, 128, device=zz.device)
-        masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=zz.device)
-        with ops._timed("field_fwd_train[generic]"):
-            L.check(lib.nefes_field_fwd_train_generic(pk.desc, pk.blob.data_ptr(), mode, N, S, ops._chk(o, "rays_o"), ops._chk(d, "rays_d"),
-                                                      ops._chk(zz, "z"), ops._chk(v, "viewdirs"), raw_t.data_ptr(), acts.data_ptr(),
-                                                      masks.data_ptr(), ops._stream()), "nefes_field_fwd_train_generic")
-        ops._tap("masks_generic", (masks, N, S, pk, mode))
-        ctx.save_for_backward(raw_t, acts, o, d, v, zz, masks)
-        if DEBUG is not None:
-            DEBUG.update(acts=rows_view(acts), rows=rows, off=dict(enumerate(off)))
-        ctx.net, ctx.pk, ctx.mode, ctx.NS, ctx.pk_gen = net, pk, mode, (N, S), pk.generation
-        return raw_t
+        return _generic_train_forward(ctx, net, pk, mode, N, S, False, (("rays_o", o), ("rays_d", d), ("z", zz), ("viewdirs", v)),
+                                      save=(o, d, v, zz))
 
     @staticmethod
     def backward(ctx, g_raw_t):
         if ctx.needs_input_grad[3]:
             raise NotImplementedError("nefes_amd: the depths z carry no gradient in train mode (rendering.py:139 detaches them)")
         ctx.pk.check_generation(ctx.pk_gen)
-        raw_t, acts, o, d, v, zz, masks = ctx.saved_tensors
+        _, _, o, d, v, zz, _ = ctx.saved_tensors
+        g, g_pts, g_vs = _generic_train_backward(ctx, g_raw_t, False, (o, d, zz, v))
         N, S = ctx.NS
-        with ops._timed("field_bwd_train[generic]"):
-            g = weight_grads_generic(ctx.net, ctx.pk, ctx.mode, N, S, raw_t, ops._f32(g_raw_t), acts, o, d, v, zz, masks)
-        g_pts, g_vs = g.pop("__rays__")
         g = ctx.net.shrink_grads(g)    # a network on fewer embedding octaves: drop the columns packed_generic padded
         g_rays = (None, None, None)
         if any(ctx.needs_input_grad[:3]):
@@ -582,41 +591,17 @@ class FieldTrainGenericEncoded(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, viewdirs, net, mode, *params):
-        pk = net.packed_generic()
-        lib = L.load()
-        if mode not in (L.FIELD_STATIC, L.FIELD_FULL):
-            raise ValueError("nefes_amd: train mode evaluates the static or the full head")
-        if mode == L.FIELD_FULL and not pk.has_transient:
-            raise ValueError("nefes_amd: the full head of a network without a transient head")
-        if pk.xyz_encoding != L.XYZ_EXTERNAL32:
-            raise RuntimeError(f"nefes_amd: train mode on a supplied encoding needs a network with in_channels_xyz=32; got {net._shape()}")
+        pk = _generic_train_pack(net, mode, ext=True)
         N, S = enc.shape[0], enc.shape[1]
         e, v = ops._f32(enc).reshape(N * S, 32), ops._f32(viewdirs)
-        _generic_buffers_fit(pk, N, S, e.device)
-        rows, off = pk.train_rows()
-        raw_t = torch.empty(N, pk.n_raw(mode), S, device=e.device)
-        acts = torch.empty((N * S + 127) // 128, rows, 128, device=e.device)
-        masks = torch.empty(pk.mask_bytes(N * S) // 4, dtype=torch.int32, device=e.device)
-        with ops._timed("field_fwd_train[generic,ext]"):
-            L.check(lib.nefes_field_fwd_train_generic_ext(pk.desc, pk.blob.data_ptr(), mode, N, S, ops._chk(e, "enc"), ops._chk(v, "viewdirs"),
-                                                          raw_t.data_ptr(), acts.data_ptr(), masks.data_ptr(), ops._stream()),
-                    "nefes_field_fwd_train_generic_ext")
-        ops._tap("masks_generic", (masks, N, S, pk, mode))
-        ctx.save_for_backward(raw_t, acts, v, masks)
-        if DEBUG is not None:
-            DEBUG.update(acts=rows_view(acts), rows=rows, off=dict(enumerate(off)))
-        ctx.net, ctx.pk, ctx.mode, ctx.NS, ctx.pk_gen = net, pk, mode, (N, S), pk.generation
-        return raw_t
+        return _generic_train_forward(ctx, net, pk, mode, N, S, True, (("enc", e), ("viewdirs", v)), save=(v,))
 
     @staticmethod
     def backward(ctx, g_raw_t):
         ctx.pk.check_generation(ctx.pk_gen)
-        raw_t, acts, v, masks = ctx.saved_tensors
+        v, want_w = ctx.saved_tensors[2], any(ctx.needs_input_grad[4:])
+        g, g_enc, g_vs = _generic_train_backward(ctx, g_raw_t, True, (v,), want_w=want_w)
         N, S = ctx.NS
-        want_w = any(ctx.needs_input_grad[4:])
-        with ops._timed("field_bwd_train[generic,ext]"):
-            g = weight_grads_generic_encoded(ctx.net, ctx.pk, ctx.mode, N, S, raw_t, ops._f32(g_raw_t), acts, v, masks, want_w=want_w)
-        g_enc, g_vs = g.pop("__rays__")
         g_v = None
         if ctx.needs_input_grad[1]:
             _, _, g_v = ops.ray_grad_reduce(N, S, torch.zeros(N, S, device=v.device), g_vs, g_vs)

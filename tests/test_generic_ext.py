@@ -1,4 +1,4 @@
-"""Generic field kernels on a SUPPLIED 32-feature encoding (nefes_amd/csrc/field_generic.hip, the gen_*_ext_kernel instances;
+"""Generic field kernels on a SUPPLIED 32-feature encoding (nefes_amd/csrc/field_generic.hip, the gen_{fwd,bwd}_kernel<NCB, GenArgsExt> instances;
 NEFES_XYZ_EXTERNAL32 in NefesGenericNetDesc), host side: the packer's layout against a numpy restatement of the kernels' addressing
 and the float64 oracle, the refusals that need no device, and the routing (ops.field_route, NeRFH_NFF's predicates)."""
 import ctypes as C

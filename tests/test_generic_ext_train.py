@@ -1,5 +1,5 @@
-"""Train mode of the generic field kernels on a SUPPLIED 32-feature encoding (csrc/field_generic.hip gen_*_ext_train_kernel,
-nefes_field_{fwd,bwd}_train_generic_ext), the part a CPU can check: the row map of the acts / dacts buffers against the frequency
+"""Train mode of the generic field kernels on a SUPPLIED 32-feature encoding (csrc/field_generic.hip gen_{fwd,bwd}_kernel<NCB,
+GenArgsExtTrain>, nefes_field_{fwd,bwd}_train_generic_ext), the part a CPU can check: the row map of the acts / dacts buffers against the frequency
 map of the same shape, the argument checks of the two calls, the library surface and the opt-in switch, and the fp32 oracle on the
 fixture the reference itself produced (tools/make_golden_generic_ext_train.py), so that the fixture is checked without a GPU too."""
 import ctypes as C
@@ -86,6 +86,65 @@ def test_entry_points_refuse_before_any_launch():
     # the frequency train pair keeps refusing an ext description
     assert lib.nefes_field_fwd_train_generic(ext, p, L.FIELD_FULL, 1, 1, p, p, p, p, p, p, p, None) == U
     assert lib.nefes_field_bwd_train_generic(ext, p, L.FIELD_FULL, 1, 1, p, p, p, p, p, p, p, p, p, p, None) == U
+
+
+# Pointer arguments of the eight generic entry points behind (desc, packed, mode, N, S), in order; the stream follows.
+ENTRY_PTRS = {
+    "fwd_generic": ("rays_o", "rays_d", "z", "pts", "viewdirs", "raw_t", "masks"),
+    "bwd_generic": ("rays_o", "rays_d", "z", "pts", "viewdirs", "raw_t", "g_raw_t", "masks", "g_pts", "g_viewdirs_s"),
+    "fwd_generic_ext": ("xyz_enc", "viewdirs", "raw_t", "masks"),
+    "bwd_generic_ext": ("viewdirs", "raw_t", "g_raw_t", "masks", "g_xyz_enc", "g_viewdirs_s"),
+    "fwd_train_generic": ("rays_o", "rays_d", "z", "viewdirs", "raw_t", "acts", "masks"),
+    "bwd_train_generic": ("rays_o", "rays_d", "z", "viewdirs", "raw_t", "g_raw_t", "masks", "dacts", "g_pts", "g_viewdirs_s"),
+    "fwd_train_generic_ext": ("xyz_enc", "viewdirs", "raw_t", "acts", "masks"),
+    "bwd_train_generic_ext": ("viewdirs", "raw_t", "g_raw_t", "masks", "dacts", "g_xyz_enc", "g_viewdirs_s"),
+}
+EXT_ENTRIES = {"fwd_generic_ext": "xyz_enc", "bwd_generic_ext": "g_xyz_enc", "fwd_train_generic_ext": "xyz_enc",
+               "bwd_train_generic_ext": "g_xyz_enc"}      # entry -> the pointer it moves as float4
+TRAIN_BUF = {"fwd_train_generic_ext": "acts", "bwd_train_generic_ext": "dacts"}
+
+
+def _precedence_cases():
+    """(entry, description, mode, {pointer: "off4" | None}, expected): TWO reasons to refuse in every call, so which code comes back
+    says which test runs first.  `other` = a valid description of the encoding the entry point does not serve, `width48` = an invalid
+    one of its own encoding, `other_coarse` = `other` without the transient head."""
+    out = []
+    for e in ENTRY_PTRS:
+        train, ext = "train" in e, e in EXT_ENTRIES
+        # the entry point's own test (null, mode of a train call, SIGMA into a backward) comes first ...
+        out.append((e, "other", L.FIELD_FULL, {"packed": None}, BAD))
+        out.append((e, "width48", 7, {}, BAD if train else U))                   # ... then the description, then the mode
+        out.append((e, "other", 7, {}, BAD if train else U))
+        out.append((e, "other_coarse", L.FIELD_FULL, {}, U))                     # encoding before FULL-without-the-head
+        if e != "fwd_generic" and e != "fwd_generic_ext":
+            out.append((e, "other", L.FIELD_SIGMA, {}, BAD))
+        if ext:                                                                    # alignment last
+            out.append((e, "other", L.FIELD_FULL, {EXT_ENTRIES[e]: "off4"}, U))
+            out.append((e, "width48", L.FIELD_FULL, {EXT_ENTRIES[e]: "off4"}, U))
+            out.append((e, "own_coarse", L.FIELD_FULL, {EXT_ENTRIES[e]: "off4"}, BAD))
+            out.append((e, "own", 7, {EXT_ENTRIES[e]: "off4"}, BAD))
+        if e in TRAIN_BUF:
+            out.append((e, "other", L.FIELD_FULL, {TRAIN_BUF[e]: "off4"}, U))
+            out.append((e, "width48", L.FIELD_STATIC, {TRAIN_BUF[e]: "off4"}, U))
+    return out
+
+
+@pytest.mark.parametrize("entry,desc,mode,ptrs,expected", _precedence_cases(),
+                         ids=[f"{e}-{d}-mode{m}-" + ",".join(f"{k}={x}" for k, x in p.items()) for e, d, m, p, _ in _precedence_cases()])
+def test_refusal_precedence_of_every_entry_point(entry, desc, mode, ptrs, expected):
+    """The order of the refusals of the eight entry points, where two apply at once: the call's own null / size / mode test, then the
+    description (invalid, or of the other encoding: UNSUPPORTED), then the mode and FULL without a transient head, then the row map,
+    then the alignment of a supplied encoding's buffers.  The expected codes are what the library returned before the entry points
+    shared one launcher.  Every call is refused on the host: the pointers are dummies that are never read."""
+    lib = L.load()
+    ext = entry in EXT_ENTRIES
+    enc = {True: L.XYZ_EXTERNAL32, False: L.XYZ_FREQ10}
+    d = {"own": L.NefesGenericNetDesc(64, 6, 4, 16, 1, enc[ext]), "own_coarse": L.NefesGenericNetDesc(64, 6, 4, 16, 0, enc[ext]),
+         "other": L.NefesGenericNetDesc(64, 6, 4, 16, 1, enc[not ext]), "other_coarse": L.NefesGenericNetDesc(64, 6, 4, 16, 0, enc[not ext]),
+         "width48": L.NefesGenericNetDesc(48, 6, 4, 16, 1, enc[ext])}[desc]
+    p = {"off4": C.c_void_p(4096 + 4), None: None}
+    args = [p[ptrs[k]] if k in ptrs else C.c_void_p(4096) for k in ("packed",) + ENTRY_PTRS[entry]]
+    assert getattr(lib, "nefes_field_" + entry)(d, args[0], mode, 2, 8, *args[1:], None) == expected
 
 
 def test_library_surface_and_switch():

@@ -153,7 +153,7 @@ def test_module_prefixed_checkpoint_loads(tmp_path, monkeypatch):
 
 
 def test_generic_kernels_are_in_the_library_and_clean(tmp_path):
-    """The library's gfx950 code holds the four generic kernels; they use the fp32 MFMA, no scratch and no packed-fp32
+    """The library's gfx950 code holds the sixteen generic kernels; they use the fp32 MFMA, no scratch and no packed-fp32
     op_sel:[0,1] form and tools/hazard_lint.py has no finding in them (the library-wide checks of
     tests/test_hazard_lint.py and tests/test_pack_stream.py read them too)."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -191,5 +191,5 @@ def test_generic_kernels_are_in_the_library_and_clean(tmp_path):
                 mfma += "v_mfma_f32_32x32x2_f32" in line
                 if re.search(r"v_pk_(mul|add|fma)_f32\b.*op_sel:\[0,1", line) or "scratch_" in line:
                     bad.append((name[:60], line.strip()))
-    assert len(seen) == 4, seen
+    assert len(seen) == 16, seen
     assert mfma > 100 and not bad, (mfma, bad[:4])

@@ -1,5 +1,5 @@
 """Hash-grid fields of any --netwidth / --netdepth: the generic field kernels on a SUPPLIED 32-feature encoding
-(nefes_amd/csrc/field_generic.hip gen_fwd_ext_kernel / gen_bwd_ext_kernel, nefes_field_fwd_generic_ext / nefes_field_bwd_generic_ext).
+(nefes_amd/csrc/field_generic.hip gen_fwd_kernel / gen_bwd_kernel<NCB, GenArgsExt>, nefes_field_fwd_generic_ext / nefes_field_bwd_generic_ext).
 
 Ground truth: oracle/ref_cpu.py (+ oracle/hashgrid_ref.py through the grid) in float64, the fp32 oracle next to it.  Bounds, the
 project's (tests/branch.py, tests/parity_log.py): outputs and gradients e_hip <= max(1e-4, 1.5 e_ref), gradients on the kernels' own

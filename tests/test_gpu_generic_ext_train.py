@@ -1,5 +1,5 @@
 """Training the MLP behind a hash grid at any --netwidth / --netdepth: the generic field kernels' train-mode instances on a SUPPLIED
-32-feature encoding (nefes_amd/csrc/field_generic.hip gen_fwd_ext_train_kernel / gen_bwd_ext_train_kernel,
+32-feature encoding (nefes_amd/csrc/field_generic.hip gen_fwd_kernel / gen_bwd_kernel<NCB, GenArgsExtTrain>,
 nefes_field_{fwd,bwd}_train_generic_ext, train.field_train_generic_encoded, opt-in: ops.GENERIC_TRAIN_EXT).
 
 Ground truth: oracle/ref_cpu.py (+ oracle/hashgrid_ref.py through the grid) in float64, the fp32 oracle next to it.  Bounds, the

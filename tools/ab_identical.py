@@ -5,7 +5,11 @@ and ReLU masks (TRAIN rows: `acts` too), backward g_pts / g_xyz_enc and g_viewdi
 one full 128-sample tile and a ragged one, S a multiple of nothing; one shared-depth-row case for _zrow and _hashgrid; fixed seeds.
 Run it once per library and compare the lines that do not start with '#': a re-arrangement of the host code, or a re-scheduling of the
 same arithmetic, gives the same digests.  Only entry points that older libraries export as well are called, and an older library's
-ABI number is accepted, so the same script runs on both sides."""
+ABI number is accepted, so the same script runs on both sides.
+    NEFES_HIP_LIB=<lib> python tools/ab_identical.py --generic
+prints, instead, the digests of every output of the eight generic entry points (csrc/field_generic.hip) and of both packers, at
+GENERIC_SHAPES on the frequency embedding and on a supplied encoding.  Every output buffer is filled with a fixed non-zero pattern
+before the call and digested whole, so what a kernel must not touch is compared as well."""
 import ctypes as C
 import hashlib, os, sys
 import torch
@@ -153,7 +157,77 @@ def run(pk, what):
             out(f"{tag} bwd_train_h3 mode {mode}", g_pts=gx, g_viewdirs_s=gv, dacts=dacts)
 
 
+# (W, D, C, transient head), skip = 4 where D > 4: depth 1, a skip layer and none, row-block counts that are no multiple of the four
+# waves, W below and above the head's 160 rows, both head paddings, both tile sizes (64 samples up to W = 256, 32 above).  With
+# N x S = 3 x 50 the last tile is ragged at both sizes and the train launches have tiles wholly past the last sample.
+GENERIC_SHAPES = ((32, 1, 16, False), (64, 6, 16, True), (96, 5, 128, True), (288, 5, 128, True))
+
+
+def generic_network(W, D, c, fine, ext):
+    """(host state dict, PackedGeneric) of a random network of that shape"""
+    gw = torch.Generator(device='cpu').manual_seed(W + D + c)
+    skip, H, k_in = (4 if D > 4 else -1), W // 2, 32 if ext else 63
+    shapes = [(W, k_in if i == 0 else (W + k_in if i == skip else W)) for i in range(D)] + [(W, W), (H, W + 27), (1, W), (3 + c, H)]
+    if fine:
+        shapes += [(H, W + 27), (H, H), (H, H), (1, H), (3, H), (1, H)]
+    sd = {}
+    for i, (name, (n_out, n_in)) in enumerate(zip(ops.PackedGeneric.layer_names(D, fine), shapes)):
+        sc = (1.0 + 0.5 * ((i * 7) % 5)) / n_in ** 0.5
+        sd[name + ".weight"] = (torch.rand(n_out, n_in, generator=gw) * 2 - 1) * sc * 1.7
+        sd[name + ".bias"] = (torch.rand(n_out, generator=gw) * 2 - 1) * 0.1
+    return sd, ops.PackedGeneric(sd, W, D, skip, c, fine, dev, xyz_encoding=L.XYZ_EXTERNAL32 if ext else L.XYZ_FREQ10)
+
+
+def run_generic(W, D, c, fine, ext):
+    sd, pk = generic_network(W, D, c, fine, ext)
+    ds, blob, tag = pk.desc, P(pk.blob), f"W{W} D{D} C{c} {'ext' if ext else 'freq'}"
+    sfx, first = ("_ext", "g_xyz_enc") if ext else ("", "g_pts")
+    call = lambda name, *a: L.check(getattr(lib, f"nefes_field_{name}{sfx}")(ds, blob, *a, None), f"{tag} {name}{sfx}")
+    fill = lambda *shape: torch.full(shape, 0.123, device=dev)
+    words = lambda: torch.full((pk.mask_bytes(M) // 4,), 0x5a5a5a5a, dtype=torch.int32, device=dev)
+    upstream = lambda R: (torch.randn(N, R, S, generator=torch.Generator(device='cpu').manual_seed(R)) * 0.1).to(dev)
+    rays = (P(enc),) if ext else (P(o), P(d), P(z))
+    pts = (o[:, None, :] + d[:, None, :] * z[..., None]).reshape(M, 3).contiguous()
+    # the two packers: the host's into a patterned buffer (it clears the whole blob), the device's over a patterned blob (it leaves
+    # the padding alone)
+    names = ops.PackedGeneric.layer_names(D, fine)
+    host = [sd[n + k].contiguous() for n in names for k in (".weight", ".bias")]
+    hblob = torch.full((pk.blob.numel(),), 0x5a, dtype=torch.uint8)
+    L.check(lib.nefes_generic_pack(ds, (C.c_void_p * len(host))(*[t.data_ptr() for t in host]), len(host), P(hblob), hblob.numel()), tag)
+    devt = [t.to(dev) for t in host]
+    dblob = torch.full((pk.blob.numel(),), 0x5a, dtype=torch.uint8, device=dev)
+    L.check(lib.nefes_generic_pack_device(ds, (C.c_void_p * len(devt))(*[t.data_ptr() for t in devt]), len(devt), P(dblob), dblob.numel(), None), tag)
+    out(f"{tag} pack", host=hblob, device=dblob, used=pk.blob)
+    top = FULL if fine else STATIC
+    for mode in (SIGMA, STATIC, FULL) if fine else (SIGMA, STATIC):
+        R = pk.n_raw(mode)
+        raw, masks = fill(N, R, S), words()
+        call("fwd_generic", mode, N, S, *rays, *(() if ext else (None,)), P(d), P(raw), P(masks))
+        out(f"{tag} fwd_generic{sfx} mode {mode}", raw=raw, masks=masks)
+        if mode == top and not ext:                  # the caller's points in the place of rays
+            raw_p, masks_p = fill(N, R, S), words()
+            call("fwd_generic", mode, N, S, None, None, None, P(pts), P(d), P(raw_p), P(masks_p))
+            out(f"{tag} fwd_generic mode {mode} pts", raw=raw_p, masks=masks_p)
+        if mode == SIGMA:
+            continue
+        g_up, gx, gv = upstream(R), fill(M, 32 if ext else 3), fill(M, 3)
+        call("bwd_generic", mode, N, S, *(() if ext else rays + (None,)), P(d), P(raw), P(g_up), P(masks), P(gx), P(gv))
+        out(f"{tag} bwd_generic{sfx} mode {mode}", **{first: gx, "g_viewdirs_s": gv})
+        raw, masks = fill(N, R, S), words()
+        acts, gx, gv = fill((M + 127) // 128, pk.train_rows()[0], 128), fill(M, 32 if ext else 3), fill(M, 3)
+        dacts = torch.full_like(acts, 0.123)
+        call("fwd_train_generic", mode, N, S, *rays, P(d), P(raw), P(acts), P(masks))
+        out(f"{tag} fwd_train_generic{sfx} mode {mode}", raw=raw, masks=masks, acts=acts)
+        call("bwd_train_generic", mode, N, S, *(() if ext else rays), P(d), P(raw), P(g_up), P(masks), P(dacts), P(gx), P(gv))
+        out(f"{tag} bwd_train_generic{sfx} mode {mode}", **{first: gx, "g_viewdirs_s": gv, "dacts": dacts})
+
+
 print("# lib", os.environ.get("NEFES_HIP_LIB") or "shipped", "ABI", L.ABI_VERSION)
+if "--generic" in sys.argv[1:]:
+    for shape in GENERIC_SHAPES:
+        for ext in (False, True):
+            run_generic(*shape, ext)
+    sys.exit(0)
 for width, c, ext, fold, what in ((256, 16, 0, 0, "zrow"), (256, 128, 0, 0, "freq"), (128, 16, 0, 0, "freq"), (128, 128, 0, 0, "freq"),
                                   (128, 0, 0, 0, "fh"), (256, 16, 0, 1, "fold"), (256, 128, 0, 1, "fold"), (256, 16, 1, 0, "ext"),
                                   (256, 128, 1, 0, "ext")):

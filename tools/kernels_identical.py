@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Are the device kernels of two builds of libnefes_hip.so the same?  For a host-side refactor that must not move device code.
-    python tools/kernels_identical.py <old.so> <new.so>
+    python tools/kernels_identical.py [--allow-renames] <old.so> <new.so>
 For every kernel of either library: its bytes in its code object's .text and its metadata note entry (vgpr / agpr / sgpr counts,
 spill counts, private_segment_fixed_size, group_segment_fixed_size) must be equal, and so must the two sets of kernel names.
+--allow-renames: a kernel only in the old library and one only in the new one with equal code bytes, size and notes are printed as
+`renamed: old -> new` and are no difference (a refactor that renames kernels without touching them).
 Prints every difference and the number of kernels compared; exit status 1 on any difference."""
 import hashlib, os, re, subprocess, sys, tempfile
 
@@ -41,10 +43,26 @@ def kernels(lib):
     return out
 
 
+def renames(old, new):
+    """[(old name, new name)]: kernels that only one library has and whose code and notes are equal, paired in name order"""
+    came = sorted(set(new) - set(old))
+    pairs = []
+    for o in sorted(set(old) - set(new)):
+        same = [n for n in came if new[n] == old[o]]
+        if same:
+            pairs.append((o, same[0]))
+            came.remove(same[0])
+    return pairs
+
+
 def main():
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    args = [a for a in sys.argv[1:] if a != "--allow-renames"]
+    old, new = kernels(args[0]), kernels(args[1])
+    renamed = renames(old, new) if len(args) < len(sys.argv) - 1 else []
+    for o, n in renamed:
+        print(f"renamed: {o} -> {n}")
     bad = 0
-    for name in sorted(set(old) | set(new)):
+    for name in sorted((set(old) | set(new)) - {x for pair in renamed for x in pair}):
         if name not in old or name not in new:
             print(f"only in {'new' if name in new else 'old'}: {name}")
             bad += 1
@@ -52,9 +70,10 @@ def main():
             what = "code" if old[name][:2] != new[name][:2] else "notes"
             print(f"{what} differ: {name}\n    old {old[name]}\n    new {new[name]}")
             bad += 1
-    n = len(set(old) & set(new))
+    n = len(set(old) & set(new)) + len(renamed)
     print(f"{n} kernels compared ({sum(s for _, s, _ in new.values())} bytes of code in the new library): "
-          + (f"{bad} DIFFERENCES" if bad else "code bytes and resource notes identical, same set of names"))
+          + (f"{bad} DIFFERENCES" if bad else "code bytes and resource notes identical" + ("" if renamed else ", same set of names"))
+          + (f", {len(renamed)} renamed" if renamed else ""))
     return 1 if bad else 0
 
 

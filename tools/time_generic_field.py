@@ -3,7 +3,7 @@
 frame (80x60 rays, 64 + 64 samples) and the BASELINE frame (640x480, 64 + 128) for a few network shapes, as a fraction of the
 fp32-MFMA bound bench.py uses for its strict-fp32 anchor (157.3 TFLOP/s), and at (256, 8) next to the tuned instance.
 
---ext: the instances on a SUPPLIED 32-feature encoding (hash-grid fields: gen_fwd_ext_kernel / gen_bwd_ext_kernel) instead:
+--ext: the instances on a SUPPLIED 32-feature encoding (hash-grid fields: gen_fwd_kernel / gen_bwd_kernel<NCB, GenArgsExt>) instead:
 FieldFromEncoding forward + backward at 4096 rays x 192 samples, (256, 8, 16) generic against tuned alternating in the same run,
 (128, 8, 128) and (64, 6, 16) generic alone; per shape a warm-up, --reps repetitions of each, median and spread (min..max), the
 sustained clock of the device beside them (nefes_probe_mfma_clock).
