@@ -591,6 +591,54 @@ int nefes_fusion_input_bwd(int B, int HW, int C, const float* g_x, const float* 
 int nefes_adam_step(int n, float* p, const float* g, float* m, float* v, float* step, const double* lr, double beta1, double beta2,
                     double eps, void* stream);
 
+/* ---- the training step's losses (script/models/losses.py:4-173: ColorLoss, ColorFeatureLoss, ColorFeatureFusionLoss, NerfWLoss,
+ *      ColorFeatureFusionNerfWLoss), two launches forward and one backward whatever the class and its switches; no host read, no
+ *      allocation.  Every element is widened to fp64, every sum is fp64 in a fixed order (no atomics: the same bits from call to call),
+ *      every output is rounded to fp32 once.  A block owns NEFES_TRAIN_LOSS_ROWS consecutive rays. ---- */
+#define NEFES_TRAIN_LOSS_ROWS 16
+#define NEFES_LOSS_FEAT_MSE 0 /* mean((a - b)^2) */
+#define NEFES_LOSS_FEAT_L1 1  /* mean(|a - b|); the gradient at a == b is 0 */
+#define NEFES_LOSS_FEAT_COS 2 /* 1 - mean_n cos(a_n, b_n) over the channels, torch.nn.CosineSimilarity(dim=1, eps=1e-8): each norm clamped */
+/* NefesTrainLossDesc.present: which inputs are there, and NEFES_LOSS_NERFW for the NeRF-W form of the colour loss */
+#define NEFES_LOSS_HAS_RGB_FINE 1u
+#define NEFES_LOSS_HAS_RGB_COARSE 2u
+#define NEFES_LOSS_HAS_BETA 4u /* beta AND transient_sigmas; NeRF-W with rgb_fine only */
+#define NEFES_LOSS_HAS_FEAT_FINE 8u
+#define NEFES_LOSS_HAS_FEAT_COARSE 16u
+#define NEFES_LOSS_HAS_FEAT_FUSION 32u
+#define NEFES_LOSS_NERFW 64u
+#define NEFES_LOSS_PRESENT_ALL 127u
+typedef struct NefesTrainLossDesc {
+    int32_t N;         /* rays */
+    int32_t C;         /* feature channels (read when a feature bit is set) */
+    int32_t S;         /* samples per ray of transient_sigmas (read with NEFES_LOSS_HAS_BETA) */
+    int32_t feat_kind; /* NEFES_LOSS_FEAT_* */
+    uint32_t present;
+    float coef;        /* plain colour: coef (mse fine + mse coarse); NeRF-W: every term times coef */
+    float lambda_u;
+    int64_t sigma_row_stride; /* elements between rows of transient_sigmas (>= S; unit inner stride) */
+} NefesTrainLossDesc;
+/* Plain colour needs rgb_fine, NeRF-W needs rgb_coarse; rgb_target always.  NeRF-W: c_l = 1/2 mean((rgb_coarse - t)^2); f_l =
+ * 1/2 mean((rgb_fine - t)^2), or with beta mean((rgb_fine - t)^2 / (2 beta^2)), b_l = 3 + mean(log beta), s_l = lambda_u
+ * mean(transient_sigmas); each times coef.  Inputs (dev; NULL where the bit is off): rgb_* [N,3], beta [N], transient_sigmas [N,S] through its
+ * row stride, feat_* [N,C].  scratch: nefes_train_loss_scratch_doubles(N) dev doubles (not needed by the backward).
+ * terms dev [8]: c_l, f_l, b_l, s_l (plain colour: coef mse coarse, coef mse fine, 0, 0), feature term of feat_fine, feat_coarse, feat_fusion,
+ * 0.  losses dev [3]: the colour loss, loss_f = fine + coarse, loss_fusion; 0 where nothing is present.
+ * NEFES_E_BADARG: N <= 0, a missing required pointer, a bit outside the mask, an unknown feat_kind; NEFES_E_UNSUPPORTED: C or S above 2^20. */
+size_t nefes_train_loss_scratch_doubles(int N);
+int nefes_train_loss_fwd(const NefesTrainLossDesc* desc, const float* rgb_fine, const float* rgb_coarse, const float* rgb_target,
+                         const float* beta, const float* transient_sigmas, const float* feat_fine, const float* feat_coarse,
+                         const float* feat_fusion, const float* feat_target, double* scratch, float* terms, float* losses, void* stream);
+/* One launch.  g_color / g_loss_f / g_loss_fusion: dev scalars, the upstream gradients of losses[0..2]; NULL = that output was unused (its
+ * gradient counts as 0).  g_* outputs: NULL = not wanted; at least one must be given, and only for an input that is present.  g_sigma is ONE
+ * float, g coef lambda_u / (N S): every element of transient_sigmas has that gradient, the caller expands it.  Targets get none.
+ * COS rows with a norm below 1e-8: the clamped norm is a constant, so the gradient is b / (1e-8 |b|) -- large but finite. */
+int nefes_train_loss_bwd(const NefesTrainLossDesc* desc, const float* g_color, const float* g_loss_f, const float* g_loss_fusion,
+                         const float* rgb_fine, const float* rgb_coarse, const float* rgb_target, const float* beta,
+                         const float* transient_sigmas, const float* feat_fine, const float* feat_coarse, const float* feat_fusion,
+                         const float* feat_target, float* g_rgb_fine, float* g_rgb_coarse, float* g_beta, float* g_sigma, float* g_feat_fine,
+                         float* g_feat_coarse, float* g_feat_fusion, void* stream);
+
 /* ---- measurement aid (bench.py's roofline): the matrix-core rate this GPU SUSTAINS under its power management.  Runs
  *      v_mfma_f32_32x32x16_f16 back to back on every SIMD for ~ms_target milliseconds (operands all zero, or random bits) and
  *      returns the settled shader clock and the dense fp16 rate.  Synchronises the stream.  Not part of the render path. ---- */

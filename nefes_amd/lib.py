@@ -34,6 +34,11 @@ class NefesBlobInfo(C.Structure):
     _fields_ = [("total_bytes", C.c_uint64), ("stream", NefesStreamInfo * 13)]
 
 
+class NefesTrainLossDesc(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("S", C.c_int32), ("feat_kind", C.c_int32), ("present", C.c_uint32),
+                ("coef", C.c_float), ("lambda_u", C.c_float), ("sigma_row_stride", C.c_int64)]
+
+
 class NefesHashGridDesc(C.Structure):
     _fields_ = [("n_levels", C.c_int32), ("n_features", C.c_int32), ("log2_hashmap_size", C.c_int32),
                 ("base_resolution", C.c_int32), ("per_level_scale", C.c_float), ("bound", C.c_float)]
@@ -48,6 +53,11 @@ H3_REQ_TRAIN, H3_REQ_EXT, H3_REQ_HASHGRID, H3_REQ_FH, H3_REQ_ZROW, H3_REQ_STATIC
 (TB_E, TB_DV, TB_L1, TB_FINAL, TB_DIR, TB_T0, TB_T1, TB_T2, TB_RGB, TB_SIG, TB_TH, TB_END) = (0, 1, 2, 10, 11, 12, 13, 14, 15, 16,
                                                                                               17, 18)
 COMP_TRANSIENT, COMP_STATIC_ONLY, COMP_SIGMA_ONLY, COMP_WHITE_BKGD, COMP_FEAT_WEIGHTS_ONLY = 1, 2, 4, 8, 16
+
+TRAIN_LOSS_ROWS = 16        # NEFES_TRAIN_LOSS_ROWS: rays per block of the train-loss kernels
+LOSS_FEAT_MSE, LOSS_FEAT_L1, LOSS_FEAT_COS = 0, 1, 2
+(LOSS_HAS_RGB_FINE, LOSS_HAS_RGB_COARSE, LOSS_HAS_BETA, LOSS_HAS_FEAT_FINE, LOSS_HAS_FEAT_COARSE, LOSS_HAS_FEAT_FUSION,
+ LOSS_NERFW) = 1, 2, 4, 8, 16, 32, 64
 
 _p, _i, _f, _u32, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.c_size_t
 _desc = C.POINTER(NefesNetDesc)
@@ -158,6 +168,9 @@ SIGNATURES = {
     "nefes_cosine_loss_scratch_doubles": (_sz, [_i]),
     "nefes_cosine_loss_fwd": (_i, [_i, C.c_int64, _p, _p, _p, _p, _p]),
     "nefes_cosine_loss_bwd": (_i, [_i, C.c_int64, _p, _p, _p, _p, _p, _p]),
+    "nefes_train_loss_scratch_doubles": (_sz, [_i]),
+    "nefes_train_loss_fwd": (_i, [C.POINTER(NefesTrainLossDesc)] + [_p] * 13),
+    "nefes_train_loss_bwd": (_i, [C.POINTER(NefesTrainLossDesc)] + [_p] * 20),
     "nefes_sample_pdf_merge": (_i, [_i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
 }
 

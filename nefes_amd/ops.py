@@ -1869,3 +1869,103 @@ class FusedAdam:
         L.check(L.load().nefes_adam_step(self.flat.numel(), self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
                                          self.step_t.data_ptr(), self.lr.data_ptr(), float(self.betas[0]), float(self.betas[1]),
                                          float(self.eps), _stream()), "nefes_adam_step")
+
+
+# ---------------------------------------------------------------------------------------------
+# the training step's losses (script/models/losses.py; csrc/losses.hip)
+# ---------------------------------------------------------------------------------------------
+def _loss_in(t, name, shape):
+    """A loss input as the kernels read it: float32 on the GPU (anything else raises -- no CPU path, no silent cast), made contiguous."""
+    if t is None:
+        return None
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+        raise RuntimeError(f"nefes_amd: train loss: `{name}` must be a float32 GPU tensor (got {getattr(t, 'dtype', type(t))}, "
+                           f"{getattr(t, 'device', None)}); there is no CPU path")
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"nefes_amd: train loss: `{name}` must be {tuple(shape)} (got {tuple(t.shape)})")
+    return _f32(t)
+
+
+class TrainLoss(torch.autograd.Function):
+    """The five loss classes of script/models/losses.py as two launches forward and one backward (csrc/losses.hip).
+
+    apply(rgb_fine, rgb_coarse, rgb_target, beta, transient_sigmas, feat_fine, feat_coarse, feat_fusion, feat_target, nerfw, feat_kind,
+          coef, lambda_u) -> (colour loss, loss_f, loss_fusion, terms[8])
+    A tensor that is None is absent.  `transient_sigmas` [N,S] is read in place through its row stride (render()'s raw[:, ch, :] view);
+    its gradient is one number on the device, returned as a stride-0 [N,S] view.  `terms` carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, rgb_fine, rgb_coarse, rgb_target, beta, sigmas, feat_fine, feat_coarse, feat_fusion, feat_target, nerfw, feat_kind,
+                coef, lambda_u):
+        if rgb_target is None:
+            raise RuntimeError("nefes_amd: train loss: `rgb_target` is required")
+        N = int(rgb_target.shape[0])
+        rgb_target = _loss_in(rgb_target, "rgb_target", (N, 3))
+        rgb_fine, rgb_coarse = _loss_in(rgb_fine, "rgb_fine", (N, 3)), _loss_in(rgb_coarse, "rgb_coarse", (N, 3))
+        Cc = int(feat_target.shape[-1]) if feat_target is not None else 0
+        feat_target = _loss_in(feat_target, "feat_target", (N, Cc))
+        feat_fine, feat_coarse = _loss_in(feat_fine, "feat_fine", (N, Cc)), _loss_in(feat_coarse, "feat_coarse", (N, Cc))
+        feat_fusion = _loss_in(feat_fusion, "feat_fusion", (N, Cc))
+        beta = _loss_in(beta, "beta", (N,))
+        S, stride = 0, 0
+        if beta is not None:
+            if sigmas is None or sigmas.dim() != 2 or sigmas.shape[0] != N:
+                raise RuntimeError("nefes_amd: train loss: `beta` needs `transient_sigmas` [N,S]")
+            S = int(sigmas.shape[1])
+            if not (sigmas.is_cuda and sigmas.dtype == torch.float32):
+                raise RuntimeError(f"nefes_amd: train loss: `transient_sigmas` must be a float32 GPU tensor (got {sigmas.dtype}, {sigmas.device})")
+            sigmas = sigmas.detach()
+            if not ((sigmas.stride(1) == 1 or S == 1) and sigmas.stride(0) >= S):
+                sigmas = sigmas.contiguous()                                # (any other layout; render()'s view is read in place)
+            stride = int(sigmas.stride(0))
+        else:
+            sigmas = None
+        present = ((L.LOSS_HAS_RGB_FINE if rgb_fine is not None else 0) | (L.LOSS_HAS_RGB_COARSE if rgb_coarse is not None else 0)
+                   | (L.LOSS_HAS_BETA if beta is not None else 0) | (L.LOSS_HAS_FEAT_FINE if feat_fine is not None else 0)
+                   | (L.LOSS_HAS_FEAT_COARSE if feat_coarse is not None else 0) | (L.LOSS_HAS_FEAT_FUSION if feat_fusion is not None else 0)
+                   | (L.LOSS_NERFW if nerfw else 0))
+        desc = L.NefesTrainLossDesc(N, Cc, S, int(feat_kind), present, float(coef), float(lambda_u), stride)
+        lib = L.load()
+        dev = rgb_target.device
+        scratch = torch.empty(lib.nefes_train_loss_scratch_doubles(N), dtype=torch.float64, device=dev)
+        out = torch.empty(11, device=dev)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with _timed("train_loss_fwd"):
+            L.check(lib.nefes_train_loss_fwd(C.byref(desc), _chk(rgb_fine, "rgb_fine"), _chk(rgb_coarse, "rgb_coarse"),
+                                             _chk(rgb_target, "rgb_target"), _chk(beta, "beta"), ptr(sigmas), _chk(feat_fine, "feat_fine"),
+                                             _chk(feat_coarse, "feat_coarse"), _chk(feat_fusion, "feat_fusion"),
+                                             _chk(feat_target, "feat_target"), _chk(scratch, "scratch", torch.float64), _chk(out, "out"),
+                                             C.c_void_p(out.data_ptr() + 32), _stream()), "nefes_train_loss_fwd")
+        ctx.desc = desc
+        ctx.tensors = (rgb_fine, rgb_coarse, rgb_target, beta, sigmas, feat_fine, feat_coarse, feat_fusion, feat_target)
+        ctx.set_materialize_grads(False)               # an output nobody used arrives as None: a null pointer, no zero-filled scalar
+        # four tensors on the one buffer, not views of it: an output that is a view of a multi-output function cannot be modified in
+        # place (`loss += ...`, as the reference's own classes write)
+        store = out.untyped_storage()
+        part = lambda off, shape: torch.empty(0, device=dev).set_(store, off, shape)
+        terms = part(0, (8,))
+        ctx.mark_non_differentiable(terms)
+        return part(8, ()), part(9, ()), part(10, ()), terms
+
+    @staticmethod
+    def backward(ctx, g_color, g_f, g_fusion, _g_terms):
+        rgb_fine, rgb_coarse, rgb_target, beta, sigmas, feat_fine, feat_coarse, feat_fusion, feat_target = ctx.tensors
+        need = ctx.needs_input_grad
+        fix = lambda g: None if g is None else _f32(g).reshape(1)
+        g_color, g_f, g_fusion = fix(g_color), fix(g_f), fix(g_fusion)
+        want = lambda i, t, g: torch.empty_like(t) if (need[i] and t is not None and g is not None) else None
+        o_rf, o_rc, o_b = want(0, rgb_fine, g_color), want(1, rgb_coarse, g_color), want(3, beta, g_color)
+        o_s = torch.empty(1, device=rgb_target.device) if (need[4] and sigmas is not None and g_color is not None) else None
+        o_ff, o_fc, o_fu = want(5, feat_fine, g_f), want(6, feat_coarse, g_f), want(7, feat_fusion, g_fusion)
+        outs = (o_rf, o_rc, o_b, o_s, o_ff, o_fc, o_fu)
+        if all(o is None for o in outs):
+            return (None,) * 13
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with _timed("train_loss_bwd"):
+            L.check(L.load().nefes_train_loss_bwd(C.byref(ctx.desc), _chk(g_color, "g_color"), _chk(g_f, "g_loss_f"),
+                                                  _chk(g_fusion, "g_loss_fusion"), ptr(rgb_fine), ptr(rgb_coarse), ptr(rgb_target), ptr(beta),
+                                                  ptr(sigmas), ptr(feat_fine), ptr(feat_coarse), ptr(feat_fusion), ptr(feat_target),
+                                                  *[_chk(o, "gradient") for o in outs], _stream()), "nefes_train_loss_bwd")
+        if o_s is not None:
+            o_s = o_s.reshape(1, 1).expand(ctx.desc.N, ctx.desc.S)           # one number for every element: no [N,S] tensor
+        return o_rf, o_rc, None, o_b, o_s, o_ff, o_fc, o_fu, None, None, None, None, None
