@@ -327,6 +327,11 @@ class PackedField:
     def mask_bytes(self, M):
         return L.load().nefes_field_mask_bytes(self.desc, M)
 
+    def train_rows(self):
+        """(rows per tile, first row of block L.TB_*) of the train-mode acts / dacts buffers (nefes_train_row_offset)."""
+        lib = L.load()
+        return int(lib.nefes_train_rows(self.desc)), [int(lib.nefes_train_row_offset(self.desc, b)) for b in range(L.TB_END + 1)]
+
     def n_raw(self, mode):
         return 1 if mode == L.FIELD_SIGMA else (3 + self.feat_dim + (1 if mode == L.FIELD_STATIC else 6))
 

@@ -141,15 +141,7 @@ def _render_core(rays_o, rays_d, viewdirs, near, far, network_fn, network_fine, 
         grid_static = mode == L.FIELD_STATIC and _grid_trainable(cfg.xyz_encoder) and not ops.is_generic(pk)
         if (trainable(net) or grid_static) and mode != L.FIELD_SIGMA:
             from . import train as T
-            if ops.is_generic(pk):
-                if cfg.xyz_encoder is not None and ops.GENERIC_TRAIN_EXT:
-                    return T.field_train_generic_encoded(net, mode, cfg.xyz_encoder, rays_o, rays_d, viewdirs, z_)
-                if not ops.GENERIC_TRAIN or cfg.xyz_encoder is not None:
-                    net.require_frozen_for_generic("train mode (weight gradients)")
-                return T.field_train_generic(net, mode, rays_o, rays_d, viewdirs, z_)
-            if cfg.xyz_encoder is not None:
-                return T.field_train_encoded(net, mode, cfg.xyz_encoder, rays_o, rays_d, viewdirs, z_)
-            return T.field_train(net, mode, rays_o, rays_d, viewdirs, z_)
+            return T.field_train_any(net, pk, mode, cfg.xyz_encoder, rays_o, rays_d, viewdirs, z_)
         return _field(pk, mode, rays_o, rays_d, viewdirs, z_, cfg.xyz_encoder)
 
     pk_c = network_fn.packed_any()

@@ -9,7 +9,11 @@ ABI number is accepted, so the same script runs on both sides.
     NEFES_HIP_LIB=<lib> python tools/ab_identical.py --generic
 prints, instead, the digests of every output of the eight generic entry points (csrc/field_generic.hip) and of both packers, at
 GENERIC_SHAPES on the frequency embedding and on a supplied encoding.  Every output buffer is filled with a fixed non-zero pattern
-before the call and digested whole, so what a kernel must not touch is compared as well."""
+before the call and digested whole, so what a kernel must not touch is compared as well.
+    NEFES_HIP_LIB=<lib> python tools/ab_identical.py --train
+prints, instead, the digests of one train-mode forward + backward through the four autograd Functions of nefes_amd/train.py (raw_t,
+every parameter gradient, the gradients of the rays or of the encoding and viewdirs) at TRAIN_CASES: for A/B revisions of the HOST code
+on one library.  37 rays x 24 samples = seven tiles, the last ragged."""
 import ctypes as C
 import hashlib, os, sys
 import torch
@@ -222,7 +226,48 @@ def run_generic(W, D, c, fine, ext):
         out(f"{tag} bwd_train_generic{sfx} mode {mode}", **{first: gx, "g_viewdirs_s": gv, "dacts": dacts})
 
 
+# (tag, NeRFH_NFF arguments, mode, NEFES_SPLIT, generic kernels): both tuned pipes, a supplied encoding, a reduced embedding (33 / 15
+# inputs), and the generic kernels on either input
+TRAIN_CASES = (("tuned W128 C128 fine h3", dict(typ="fine", W=128, f_dim=128, encode_transient=True), FULL, "h3", False),
+               ("tuned W256 C16 coarse f32", dict(typ="coarse", W=256, f_dim=16), STATIC, "f32", False),
+               ("tuned W256 C16 fine ext", dict(typ="fine", W=256, f_dim=16, encode_transient=True, in_channels_xyz=32), FULL, "h3", False),
+               ("tuned W128 C128 fine reduced", dict(typ="fine", W=128, f_dim=128, encode_transient=True, in_channels_xyz=33, in_channels_dir=15),
+                FULL, "h3", False),
+               ("generic W64 D6 C16 fine", dict(typ="fine", D=6, W=64, f_dim=16, encode_transient=True), FULL, "h3", True),
+               ("generic W96 D5 C128 fine ext", dict(typ="fine", D=5, W=96, f_dim=128, encode_transient=True, in_channels_xyz=32), FULL, "h3", True))
+
+
+def run_train():
+    from nefes_amd import field as F, train as T
+    Nt, St = 37, 24
+    gt = torch.Generator(device='cpu').manual_seed(7)
+    leaf = lambda t: t.to(dev).requires_grad_()
+    for tag, kw, mode, split, generic in TRAIN_CASES:
+        ops.SPLIT, ops.GENERIC_TRAIN, ops.GENERIC_TRAIN_EXT = split, True, True
+        net = F.NeRFH_NFF(**kw).to(dev)
+        ext = kw.get("in_channels_xyz") == 32
+        names = (T.param_names_generic if generic else T.param_names)(net, mode)
+        sd = dict(net.named_parameters())
+        ro, rd = leaf(torch.randn(Nt, 3, generator=gt) * 0.3), leaf(torch.nn.functional.normalize(torch.randn(Nt, 3, generator=gt), dim=-1))
+        rv = leaf(torch.nn.functional.normalize(torch.randn(Nt, 3, generator=gt), dim=-1))
+        rz = torch.sort(torch.rand(Nt, St, generator=gt) * 3.5 + 0.2, -1)[0].to(dev)
+        if ext:
+            e = leaf(torch.randn(Nt, St, 32, generator=gt) * 0.5)
+            raw = (T.FieldTrainGenericEncoded if generic else T.FieldTrainEncoded).apply(e, rv, net, mode, *[sd[n] for n in names])
+            inputs = {"enc": e, "viewdirs": rv}
+        else:
+            raw = (T.field_train_generic if generic else T.field_train)(net, mode, ro, rd, rv, rz)
+            inputs = {"rays_o": ro, "rays_d": rd, "viewdirs": rv}
+        raw.backward((torch.randn(raw.shape, generator=gt) * 0.1).to(dev))
+        torch.cuda.synchronize()
+        for k, t in [("raw_t", raw)] + [(n, sd[n].grad) for n in names] + [("d " + k, t.grad) for k, t in inputs.items()]:
+            print(f"{tag:30s} {k:34s} {tuple(t.shape)!s:18s} {dig(t)}", flush=True)
+
+
 print("# lib", os.environ.get("NEFES_HIP_LIB") or "shipped", "ABI", L.ABI_VERSION)
+if "--train" in sys.argv[1:]:
+    run_train()
+    sys.exit(0)
 if "--generic" in sys.argv[1:]:
     for shape in GENERIC_SHAPES:
         for ext in (False, True):
