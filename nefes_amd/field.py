@@ -45,12 +45,12 @@ class FusionNet(nn.Module):
             self._norm[key] = (x.new_tensor(self.mean), x.new_tensor(self.std))
         return self._norm[key]
 
-    def forward(self, x):
+    def forward(self, x, track_stats=None):
         mean, std = self._mean_std(x)
         x[:, :3] = (x[:, :3] - mean[:, None, None]) / std[:, None, None]     # in place, as the reference does
         if self._use_hip_train(x):
             out = self._convs_hip_train(x)
-            out = out if self.no_BN else self._bn(out, False)
+            out = out if self.no_BN else self._bn(out, False, track_stats)
         else:
             out = self.net(x)
         return x[:, 3:] + out if self.fusion_residule else out
@@ -88,24 +88,28 @@ class FusionNet(nn.Module):
     HIP_BATCHNORM = os.environ.get("NEFES_HIP_BATCHNORM", "1") != "0"   # the refinement loop's case (train mode, frozen affine parameters, GPU): csrc/refine.hip bn_train_* instead of MIOpen
 
     # False: train-mode BatchNorm calls leave the module's running statistics and batch counter alone (its outputs never depend on
-    # them; the reference's loop never reads them either: the net is never .eval()ed).  PoseRefiner(bn_running_stats=False) sets it
-    # around its own calls: refiners on different streams share this module, and the update is a read-modify-write of its buffers.
+    # them; the reference's loop never reads them either: the net is never .eval()ed).  The module-wide default of the forward methods'
+    # `track_stats=None`; nothing in the package assigns it.  A caller that wants its OWN calls quiet passes track_stats=False instead
+    # (PoseRefiner(bn_running_stats=False) does: refiners on different streams share this module, and the update is a read-modify-write
+    # of its buffers) -- the module and every other caller's forwards are left as they were.
     track_bn_stats = True
 
-    def _bn(self, y, per_image_norm):
-        """The last layer on the convolutions' output y [B,C,H,W]."""
+    def _bn(self, y, per_image_norm, track_stats=None):
+        """The last layer on the convolutions' output y [B,C,H,W].  track_stats: whether THIS call updates the running statistics and
+        the batch counter (None: self.track_bn_stats)."""
         from . import ops
         bn = self.net[-1]
+        track = self.track_bn_stats if track_stats is None else bool(track_stats)
         per_image = bool(per_image_norm and y.shape[0] > 1 and bn.training)
         if (self.HIP_BATCHNORM and not per_image and bn.training and bn.momentum is not None and bn.weight is not None and bn.bias is not None
                 and (bn.weight.requires_grad or bn.bias.requires_grad) and self._use_hip_train(y)):
-            return ops.batch_norm_train(y, bn, track_stats=self.track_bn_stats)      # (per image with trainable affine parameters: torch, below)
+            return ops.batch_norm_train(y, bn, track_stats=track)      # (per image with trainable affine parameters: torch, below)
         if (self.HIP_BATCHNORM and self.HIP_CONVS and y.is_cuda and y.dtype == torch.float32 and bn.training and bn.momentum is not None
                 and not any(p is not None and p.requires_grad for p in (bn.weight, bn.bias))):
-            return ops.batch_norm_train_frozen(y, bn, per_image, track_stats=self.track_bn_stats)
+            return ops.batch_norm_train_frozen(y, bn, per_image, track_stats=track)
         if per_image:
             return nn.functional.instance_norm(y, weight=bn.weight, bias=bn.bias, eps=bn.eps)
-        if bn.training and not self.track_bn_stats:
+        if bn.training and not track:
             return nn.functional.batch_norm(y, None, None, bn.weight, bn.bias, True, 0.0, bn.eps)
         return bn(y)
 
@@ -124,7 +128,7 @@ class FusionNet(nn.Module):
                 self._gmap_conv0 = (key, torch.cat([w1[:, :3], wg, wb], 1).float().contiguous())
         return self._gmap_conv0[1]
 
-    def forward_prepared_gmap(self, x, w_f, b_f, per_image_norm=False):
+    def forward_prepared_gmap(self, x, w_f, b_f, per_image_norm=False, track_stats=None):
         """forward_prepared for x = [B, 3 + Cg + 1, H, W] holding the factored head's per-pixel INPUT in the features' place
         (render(..., feat_as_gmap=True)): the head is folded into the first convolution (_conv0_on_gmap), so neither the per-ray head
         kernels nor 128 feature channels exist.  Frozen weights on the GPU, no residual connection (it needs the features)."""
@@ -136,9 +140,9 @@ class FusionNet(nn.Module):
         y = ops.frozen_conv2d(y, c1.weight, c1.bias, relu=True)
         y = ops.frozen_conv2d(y, c2.weight, c2.bias, relu=True)
         y = ops.frozen_conv2d(y, c3.weight, c3.bias, relu=False)
-        return y if self.no_BN else self._bn(y, per_image_norm)
+        return y if self.no_BN else self._bn(y, per_image_norm, track_stats)
 
-    def forward_parts(self, rgb_nchw, feat_nchw, per_image_norm=False):
+    def forward_parts(self, rgb_nchw, feat_nchw, per_image_norm=False, track_stats=None):
         """forward(cat([rgb, feat], 1)) without the in-place slice assignment (whose autograd costs a fill and two copies):
         the colour channels are normalised before the concatenation -- same values, same order of operations.
         per_image_norm: B independent images in one batch (PoseRefiner(images=B)).  The reference runs this net on one image at
@@ -148,13 +152,15 @@ class FusionNet(nn.Module):
         per image already -- so the batch then goes through the module itself, like a single image does."""
         mean, std = self._mean_std(rgb_nchw)
         x = torch.cat([(rgb_nchw - mean[:, None, None]) / std[:, None, None], feat_nchw], dim=1)
-        return self.forward_prepared(x, per_image_norm)
+        if track_stats is None or bool(track_stats) == self.track_bn_stats:
+            return self.forward_prepared(x, per_image_norm)      # (the two-argument form: what a stand-in for that method implements)
+        return self.forward_prepared(x, per_image_norm, track_stats)
 
-    def forward_prepared(self, x, per_image_norm=False):
+    def forward_prepared(self, x, per_image_norm=False, track_stats=None):
         """forward_parts from the concatenated, colour-normalised input [B,3+C,H,W] on (ops.fusion_input builds it in one launch)."""
         feat_nchw = x[:, 3:]
         convs = self._convs_hip if self._use_hip(x) else self._convs_hip_train if self._use_hip_train(x) else self.net[:7]
-        out = convs(x) if self.no_BN else self._bn(convs(x), per_image_norm)
+        out = convs(x) if self.no_BN else self._bn(convs(x), per_image_norm, track_stats)
         return feat_nchw + out if self.fusion_residule else out
 
 
@@ -445,10 +451,10 @@ class NeRFH_NFF(nn.Module):
         return torch.cat([static, self.transient_rgb(t), self.transient_sigma(t), self.transient_beta(t)], 1)
 
     # -- post-render helpers used by the refinement loop (nerfh_nff.py:578-626) ----------------------
-    def run_fusion_net(self, rgb, feature, H, W, B, per_image_norm=False):
+    def run_fusion_net(self, rgb, feature, H, W, B, per_image_norm=False, track_stats=None):
         render_rgb = rgb.reshape(B, H, W, 3).permute(0, 3, 1, 2)
         render_feature = feature.reshape(B, H, W, self.W_features).permute(0, 3, 1, 2)
-        fused = self.fusion_net.forward_parts(render_rgb, render_feature, per_image_norm)
+        fused = self.fusion_net.forward_parts(render_rgb, render_feature, per_image_norm, track_stats)
         return render_rgb, render_feature, fused
 
     def exposure_coefficients(self, hist):

@@ -1560,16 +1560,18 @@ def regressed_pose(pose, do_svd, world_setup=None):
     return RegressedPose.apply(pose, bool(do_svd), sc, mv)
 
 
-# Where the next feature-loss Function writes its value: PoseRefiner points this at its static loss buffer around its loss call, so that an
-# iteration needs no separate 4-byte copy kernel to leave the value there (None: a fresh tensor, as any other caller gets).
-LOSS_OUT = None
-
-
-def _loss_out(device):
-    t = LOSS_OUT
-    if t is not None and t.dim() == 0 and t.dtype == torch.float32 and t.device == torch.device(device) and not t.requires_grad:
-        return t.detach()          # (a new tensor object on the same storage: autograd attaches this call's history to it, not to the buffer)
-    return torch.empty((), device=device)
+def _loss_buffer(out, device):
+    """Where a feature-loss Function's forward kernel writes its value: the caller's `out=` (PoseRefiner passes its static loss buffer, so
+    that an iteration needs no separate 4-byte copy kernel to leave the value there) or, with None, a fresh tensor."""
+    if out is None:
+        return torch.empty((), device=device)
+    wrong = ("is not a tensor" if not torch.is_tensor(out) else f"is {out.dim()}-d" if out.dim() != 0
+             else f"is {out.dtype}" if out.dtype != torch.float32
+             else f"is on {out.device}, the inputs on {device}" if out.device != torch.device(device)
+             else "requires grad" if out.requires_grad else None)
+    if wrong:
+        raise ValueError(f"nefes_amd: the loss's `out` must be a 0-d float32 tensor on the inputs' device that does not require grad: this one {wrong}")
+    return out.detach()            # (a new tensor object on the same storage: autograd attaches this call's history to it, not to the buffer)
 
 
 class CosineFeatureLoss(torch.autograd.Function):
@@ -1577,14 +1579,14 @@ class CosineFeatureLoss(torch.autograd.Function):
     similarity over pixels; two launches forward, one backward (to `a` only: the target carries no gradient)."""
 
     @staticmethod
-    def forward(ctx, a, b):
+    def forward(ctx, a, b, out=None):
         Cc = a.shape[0]
         af, bf = _f32(a).reshape(Cc, -1), _f32(b).reshape(Cc, -1)
         if af.shape != bf.shape:
             raise ValueError(f"nefes_amd: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
         lib = L.load()
         scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(Cc), dtype=torch.float64, device=af.device)
-        loss = _loss_out(af.device)
+        loss = _loss_buffer(out, af.device)
         L.check(lib.nefes_cosine_loss_fwd(Cc, af.shape[1], _chk(af, "a"), _chk(bf, "b"), _chk(scratch, "scratch", torch.float64),
                                           _chk(loss, "loss"), _stream()), "nefes_cosine_loss_fwd")
         ctx.save_for_backward(af, bf, scratch)
@@ -1597,20 +1599,22 @@ class CosineFeatureLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_cos):
         if g is None:
-            return (None,) * 2
+            return (None,) * 3
         af, bf, scratch = ctx.saved_tensors
         gf = _f32(g).reshape(1)
         g_a = torch.empty_like(af)
         L.check(L.load().nefes_cosine_loss_bwd(af.shape[0], af.shape[1], _chk(af, "a"), _chk(bf, "b"),
                                                _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), _chk(g_a, "g_a"), _stream()),
                 "nefes_cosine_loss_bwd")
-        return g_a.reshape(ctx.shape), None
+        return g_a.reshape(ctx.shape), None, None
 
 
-def cosine_feature_loss(a, b, return_cos=False):
+def cosine_feature_loss(a, b, return_cos=False, out=None):
     """1 - mean over the leading (channel) dimension of the cosine similarity over everything else; `return_cos` adds the
-    per-channel similarities (float64, no gradient) -- per-image losses of a batch folded into the channel dimension."""
-    loss, cos = CosineFeatureLoss.apply(a, b)
+    per-channel similarities (float64, no gradient) -- per-image losses of a batch folded into the channel dimension.
+    `out`: a 0-d float32 tensor on the inputs' device that does not require grad; the forward kernel writes the value there and the
+    returned loss shares its storage (None: a fresh tensor)."""
+    loss, cos = CosineFeatureLoss.apply(a, b, out)
     return (loss, cos) if return_cos else loss
 
 
@@ -1669,14 +1673,14 @@ class UpsampledCosineLoss(torch.autograd.Function):
     csrc/refine.hip upcos kernels.  Returns (loss, per-channel cosine similarities) like CosineFeatureLoss."""
 
     @staticmethod
-    def forward(ctx, x, target, OH, OW, crop):
+    def forward(ctx, x, target, OH, OW, crop, out=None):
         xf = _f32(x)
         Cc, h, w = xf.shape[-3:]
         xf = xf.reshape(Cc, h, w)
         tf = _f32(target).reshape(Cc, OH - 2 * crop, OW - 2 * crop)
         lib = L.load()
         scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(Cc), dtype=torch.float64, device=xf.device)
-        loss = _loss_out(xf.device)
+        loss = _loss_buffer(out, xf.device)
         with _timed("upcos_loss_fwd"):
             L.check(lib.nefes_upcos_loss_fwd(Cc, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"), _chk(scratch, "scratch", torch.float64),
                                              _chk(loss, "loss"), _stream()), "nefes_upcos_loss_fwd")
@@ -1690,7 +1694,7 @@ class UpsampledCosineLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_cos):
         if g is None:
-            return (None,) * 5
+            return (None,) * 6
         xf, tf, scratch = ctx.saved_tensors
         shape, OH, OW, crop = ctx.cfg
         Cc, h, w = xf.shape
@@ -1702,12 +1706,13 @@ class UpsampledCosineLoss(torch.autograd.Function):
             L.check(L.load().nefes_upcos_loss_bwd(Cc, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"), _chk(scratch, "scratch", torch.float64),
                                                   _chk(gf, "g_loss"), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), fy.data_ptr(), cy.data_ptr(),
                                                   wy.data_ptr(), T, _chk(tmp, "tmp"), _chk(g_x, "g_x"), _stream()), "nefes_upcos_loss_bwd")
-        return g_x.reshape(shape), None, None, None, None
+        return g_x.reshape(shape), None, None, None, None, None
 
 
-def upsampled_cosine_loss(x, target, size, crop=0, return_cos=False):
-    """1 - mean over channels of the cosine similarity (over pixels) between the bicubically up-sampled, cropped x and target."""
-    loss, cos = UpsampledCosineLoss.apply(x, target, int(size[0]), int(size[1]), int(crop))
+def upsampled_cosine_loss(x, target, size, crop=0, return_cos=False, out=None):
+    """1 - mean over channels of the cosine similarity (over pixels) between the bicubically up-sampled, cropped x and target.
+    `out` as in cosine_feature_loss."""
+    loss, cos = UpsampledCosineLoss.apply(x, target, int(size[0]), int(size[1]), int(crop), out)
     return (loss, cos) if return_cos else loss
 
 
@@ -1765,7 +1770,7 @@ class UpsampledCosineLossPrepared(torch.autograd.Function):
     """UpsampledCosineLoss against a prepared target (UpcosTarget): two small launches forward, one backward, on [C,h,w] data only."""
 
     @staticmethod
-    def forward(ctx, x, prep):
+    def forward(ctx, x, prep, out=None):
         xf = _f32(x)
         if tuple(xf.shape[-3:]) != (prep.C, prep.h, prep.w) or xf.numel() != prep.C * prep.h * prep.w:
             raise ValueError(f"nefes_amd: features {tuple(x.shape)} do not match the prepared target ({prep.C}, {prep.h}, {prep.w})")
@@ -1773,7 +1778,7 @@ class UpsampledCosineLossPrepared(torch.autograd.Function):
         lib = L.load()
         scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(prep.C), dtype=torch.float64, device=xf.device)
         pmat = torch.empty(prep.C, prep.h, prep.w, dtype=torch.float64, device=xf.device)
-        loss = _loss_out(xf.device)
+        loss = _loss_buffer(out, xf.device)
         with _timed("upcos_gram_fwd"):
             L.check(lib.nefes_upcos_gram_fwd(prep.C, prep.h, prep.w, _chk(xf, "x"), _chk(prep.tt, "tt", torch.float64),
                                              _chk(prep.dbb, "dbb", torch.float64), _chk(prep.gx, "gram_x", torch.float64),
@@ -1789,7 +1794,7 @@ class UpsampledCosineLossPrepared(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_cos):
         if g is None:
-            return (None,) * 2
+            return (None,) * 3
         scratch, pmat = ctx.saved_tensors
         prep = ctx.prep
         gf = _f32(g).reshape(1)
@@ -1798,12 +1803,13 @@ class UpsampledCosineLossPrepared(torch.autograd.Function):
             L.check(L.load().nefes_upcos_gram_bwd(prep.C, prep.h, prep.w, _chk(prep.tt, "tt", torch.float64), _chk(pmat, "pmat", torch.float64),
                                                   _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), _chk(g_x, "g_x"), _stream()),
                     "nefes_upcos_gram_bwd")
-        return g_x.reshape(ctx.shape), None
+        return g_x.reshape(ctx.shape), None, None
 
 
-def upsampled_cosine_loss_prepared(x, prep, return_cos=False):
-    """upsampled_cosine_loss(x, target, (OH, OW), crop) for the target `prep` (an UpcosTarget) was last updated with."""
-    loss, cos = UpsampledCosineLossPrepared.apply(x, prep)
+def upsampled_cosine_loss_prepared(x, prep, return_cos=False, out=None):
+    """upsampled_cosine_loss(x, target, (OH, OW), crop) for the target `prep` (an UpcosTarget) was last updated with.  `out` as in
+    cosine_feature_loss."""
+    loss, cos = UpsampledCosineLossPrepared.apply(x, prep, out)
     return (loss, cos) if return_cos else loss
 
 

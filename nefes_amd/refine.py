@@ -13,6 +13,7 @@ lives in static device buffers that are reset in place.  The bicubic up-sampling
 backward; the library's atomic scatter backward was 40 % of an iteration).  No CPU fallback anywhere on the path.
 """
 import os
+import typing
 
 import torch
 import torch.nn as nn
@@ -157,7 +158,6 @@ class PoseRefiner:
         # fused_glue: the pose chain, the crop and the feature loss as library kernels (ops.pose_compose, the windowed
         # ops.bicubic_upsample, ops.cosine_feature_loss) and one fused Adam launch -- ~80 launches per iteration instead of ~215.
         # False keeps the torch expressions (the tests compare the two).
-        self.fused_glue = bool(fused_glue)
         # fused glue: Adam over (r, t) with (lr_r, lr_t) as ONE launch (ops.FusedAdam: the two parameters and their gradients are
         # views of flat buffers, the pose kernel's backward writes the gradients there); otherwise torch.optim.Adam, two groups
         if self.fused_glue and not lietorch:
@@ -171,13 +171,17 @@ class PoseRefiner:
         self.hist = torch.zeros(self.B, 10, device=self.dev)
         self.loss = torch.zeros((), device=self.dev) if self.B == 1 else torch.zeros(self.B, device=self.dev)
         self._affine = None            # static [1,12] buffer with the image's colour transform when the exposure network is frozen
-        self.use_graph, self.graph, self.apr_graph = bool(graph), None, None
+        self.graph, self.apr_graph = None, None
 
     # one iteration on the static buffers -------------------------------------------------------------------------
     def _loss(self):
         """DFM_optimization_NFF (:310-337): pose -> render -> affine colour transform -> fusion CNN -> feature loss.
-        Returns (scalar to differentiate, per-image losses [B] or the same scalar)."""
+        Returns (scalar to differentiate, per-image losses [B] or the same scalar).  One image on the fused glue: the library's loss
+        kernel writes its value straight into the static buffer self.loss (`out=`: no 4-byte copy launch per iteration); everything
+        else (images=B, the torch expressions) returns its own tensor and the callers copy it."""
         B = self.B
+        out = self.loss if (B == 1 and self.fused_glue) else None
+        track = self.bn_running_stats                      # this refiner's calls only: the shared FusionNet's own setting is not touched
         if self.apr is not None:                           # train_on_batch :91-97
             c2w = self.apr(self.photo).reshape(1, 3, 4)
             if self.fused_glue and self.FUSED_REGRESSED_POSE and HIP_SVD_REG and c2w.is_cuda and c2w.dtype == torch.float32:
@@ -198,7 +202,6 @@ class PoseRefiner:
                 c2w = fix_coord_supp(c2w, self.world_setup)
         enc = bool(getattr(self.args, "encode_hist", False))
         fnet = self.coarse.fusion_net
-        fnet.track_bn_stats = self.bn_running_stats        # (read at call time by FusionNet._bn: eager calls and graph capture alike)
         fused_input = self.fused_glue and (not enc or self._affine is not None) and fnet._use_hip(self.hist)
         kw = self.kw
         if fused_input and self.GMAP_CONV0 and not fnet.fusion_residule and kw.get("network_fine", None) is not None:
@@ -218,9 +221,9 @@ class PoseRefiner:
                 self._x_rgb = x.detach()[:, :3]            # the verification step's image, still normalised (:117-118)
             if gmap:
                 _, w_f, _, b_f = kw["network_fine"].packed_fh()
-                fused = fnet.forward_prepared_gmap(x, w_f, b_f, per_image_norm=B > 1)
+                fused = fnet.forward_prepared_gmap(x, w_f, b_f, per_image_norm=B > 1, track_stats=track)
             else:
-                fused = fnet.forward_prepared(x, per_image_norm=B > 1)
+                fused = fnet.forward_prepared(x, per_image_norm=B > 1, track_stats=track)
         else:
             if enc:
                 if self._affine is not None:               # frozen exposure network: its 12 numbers were computed once per image
@@ -229,15 +232,15 @@ class PoseRefiner:
                     rgb = self.coarse.affine_color_transform(self.args, rgb, self.hist, B)
             if self.apr is not None:
                 self._rgb, self._x_rgb = rgb.detach(), None
-            _, _, fused = self.coarse.run_fusion_net(rgb, feat, self.h, self.w, B, per_image_norm=B > 1)
+            _, _, fused = self.coarse.run_fusion_net(rgb, feat, self.h, self.w, B, per_image_norm=B > 1, track_stats=track)
         if self.upsample and self.fused_glue and not self.per_pixel and self.FUSED_UPSAMPLED_LOSS:
             # up-sampling, crop and feature loss in one pass each way: the 34 MB up-sampled image is never written (ops.upsampled_cosine_loss)
             if self._uses_prepared_target():
-                mean_loss, cos = ops.upsampled_cosine_loss_prepared(fused.reshape(B * self.C, self.h, self.w), self._sync_upcos(), return_cos=True)
+                mean_loss, cos = ops.upsampled_cosine_loss_prepared(fused.reshape(B * self.C, self.h, self.w), self._sync_upcos(), return_cos=True, out=out)
             else:
                 mean_loss, cos = ops.upsampled_cosine_loss(fused.reshape(B * self.C, self.h, self.w),
                                                            self.target.reshape(B * self.C, self.H - 20, self.W - 20), (self.H, self.W), crop=10,
-                                                           return_cos=True)
+                                                           return_cos=True, out=out)
             if B > 1:
                 return mean_loss * float(B), (1.0 - cos.view(B, self.C).mean(1)).float()
             return mean_loss, mean_loss.detach()
@@ -253,26 +256,34 @@ class PoseRefiner:
         # (a view where possible: fused[0] costs a 34 MB zero fill and a copy in the backward)
         fused = fused.view(fused.shape[1:]) if fused.is_contiguous() else fused[0]
         if self.fused_glue and not self.per_pixel:
-            loss = ops.cosine_feature_loss(fused, self.target)
+            loss = ops.cosine_feature_loss(fused, self.target, out=out)
         else:
             loss = feature_loss(fused, self.target, per_pixel=self.per_pixel)
         return loss, loss.detach()
 
-    def _sync_upcos(self):
-        """The prepared form of self.target (ops.UpcosTarget), recomputed whenever the target buffer was written since (tensor version
-        counter).  _reset / refine_apr call this after copying an image's target in, i.e. before a captured graph is replayed; under
-        capture the buffers must already be current (a re-computation would be replayed with every iteration)."""
-        key = (self.target.data_ptr(), self.target._version)
+    def _ensure_upcos(self):
+        """self._upcos (ops.UpcosTarget) with the target buffer's shape, built when there is none or the shape moved -- never under
+        capture: its set-up launches would be replayed with every iteration."""
         if getattr(self, "_upcos", None) is None or self._upcos_shape != tuple(self.target.shape):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("nefes_amd: the refinement target changed without PoseRefiner._sync_upcos() before graph capture")
             self._upcos = ops.UpcosTarget(self.B * self.C, self.h, self.w, self.H, self.W, 10, self.dev)
             self._upcos_shape, self._upcos_key = tuple(self.target.shape), None
+        return self._upcos
+
+    def _sync_upcos(self):
+        """The prepared form of self.target (ops.UpcosTarget), recomputed whenever the target buffer was written since (tensor version
+        counter).  _reset / _apr_image_state call this after copying an image's target in, i.e. before a captured graph is replayed; under
+        capture the buffers must already be current (a re-computation would be replayed with every iteration)."""
+        key = (self.target.data_ptr(), self.target._version)
+        upcos = self._ensure_upcos()
         if self._upcos_key != key:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("nefes_amd: the refinement target changed without PoseRefiner._sync_upcos() before graph capture")
             with torch.no_grad():
-                self._upcos.update(self.target.reshape(self.B * self.C, self.H - 20, self.W - 20))
+                upcos.update(self.target.reshape(self.B * self.C, self.H - 20, self.W - 20))
             self._upcos_key = key
-        return self._upcos
+        return upcos
 
     def _uses_prepared_target(self):
         """The Gram-form loss against the prepared target -- where the loop takes the fused up-sampled loss at all AND the geometry fits
@@ -280,41 +291,43 @@ class PoseRefiner:
         self.target itself on every iteration."""
         if not (self.upsample and self.fused_glue and not self.per_pixel and self.FUSED_UPSAMPLED_LOSS and self.PREPARED_TARGET):
             return False
-        if getattr(self, "_upcos", None) is None or self._upcos_shape != tuple(self.target.shape):
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("nefes_amd: the refinement target changed without PoseRefiner._sync_upcos() before graph capture")
-            self._upcos = ops.UpcosTarget(self.B * self.C, self.h, self.w, self.H, self.W, 10, self.dev)
-            self._upcos_shape, self._upcos_key = tuple(self.target.shape), None
-        return bool(self._upcos.fits)
+        return bool(self._ensure_upcos().fits)
+
+    def _one_like(self, loss):
+        """The root gradient, once: autograd otherwise fills a new one per iteration."""
+        if getattr(self, "_one", None) is None or self._one.shape != loss.shape:
+            self._one = torch.ones_like(loss)
+        return self._one
 
     def loss_and_grad(self):
         """Loss at the current (r, t) and its gradient, written into the parameters' static .grad buffers (no optimizer step).
         The gradients are copied over the previous ones: nothing has to be zeroed between iterations."""
-        loss, per_image = self._loss_into_buffer()
-        if getattr(self, "_one", None) is None or self._one.shape != loss.shape:
-            self._one = torch.ones_like(loss)              # the root gradient, once: autograd otherwise fills a new one per iteration
-        gr, gt = torch.autograd.grad(loss, [self.model.r, self.model.t], grad_outputs=self._one)
+        loss, per_image = self._loss()
+        gr, gt = torch.autograd.grad(loss, [self.model.r, self.model.t], grad_outputs=self._one_like(loss))
         for p, g in ((self.model.r, gr), (self.model.t, gt)):
             if p.grad is None:
                 p.grad = torch.empty_like(p)
             if g.data_ptr() != p.grad.data_ptr():          # (the fused pose kernel writes the parameters' .grad itself)
                 p.grad.copy_(g)
-        if per_image.data_ptr() != self.loss.data_ptr():   # (the fused loss kernels wrote it there themselves: _loss_into_buffer)
+        if per_image.data_ptr() != self.loss.data_ptr():   # (the fused loss kernels wrote it there themselves: `out=` in _loss)
             self.loss.copy_(per_image)
         return self.loss
-
-    def _loss_into_buffer(self):
-        """self._loss() with the library's loss kernel writing its value straight into the static buffer self.loss (one image, fused glue):
-        no 4-byte copy launch per iteration.  Everything else (images=B, the torch expressions) returns its own tensor and is copied."""
-        ops.LOSS_OUT = self.loss if (self.B == 1 and self.fused_glue) else None
-        try:
-            return self._loss()
-        finally:
-            ops.LOSS_OUT = None
 
     def _iteration(self):
         self.loss_and_grad()
         self.opt.step()
+
+    def _exposure_into_affine(self):
+        """Frozen exposure network: the image's twelve colour-transform numbers, computed once per image from self.hist and written IN
+        PLACE into the static buffer self._affine (a captured graph keeps reading the same buffer)."""
+        expo = getattr(self.coarse, "exposure_embedding", None)
+        if (self.fused_glue and getattr(self.args, "encode_hist", False) and expo is not None
+                and not any(p.requires_grad for p in expo.parameters())):
+            a = self.coarse.exposure_coefficients(self.hist)
+            if self._affine is None:
+                self._affine = a.clone()
+            else:
+                self._affine.copy_(a)
 
     def _reset(self, init_c2w, feature_target, hist):
         with torch.no_grad():
@@ -325,38 +338,59 @@ class PoseRefiner:
             if self._uses_prepared_target():
                 self._sync_upcos()
             self.hist.copy_(hist.reshape(self.B, 10))
-            expo = getattr(self.coarse, "exposure_embedding", None)
-            if (self.fused_glue and getattr(self.args, "encode_hist", False) and expo is not None
-                    and not any(p.requires_grad for p in expo.parameters())):
-                a = self.coarse.exposure_coefficients(self.hist)
-                if self._affine is None:
-                    self._affine = a.clone()
-                else:
-                    self._affine.copy_(a)                  # in place: a captured graph keeps reading the same buffer
+            self._exposure_into_affine()
             if isinstance(self.opt, ops.FusedAdam):
                 self.opt.zero_state()
             else:
-                for st in self.opt.state.values():
-                    for v in st.values():
-                        if torch.is_tensor(v):
-                            v.zero_()
+                _zero_optimizer_state(self.opt)
                 for p in (self.model.r, self.model.t):
                     if p.grad is not None:
                         p.grad.zero_()
 
-    def _capture(self):
-        """Warm up on a side stream (allocator, MIOpen plans, Adam state), then capture one iteration."""
+    def _refined_pose(self):
+        with torch.no_grad():
+            idx = 0 if self.B == 1 else torch.arange(self.B, device=self.dev)
+            return self.model(idx).detach().clone()
+
+    # ---- the loop, written once for both modes ---------------------------------------------------------------------------
+    def _mode(self, apr=False, verification=True):
+        """The _Mode record of `refine` (mode 3) or, apr=True, of `refine_apr` (mode 2) on this refiner."""
+        first_use = lambda m: self.use_graph and getattr(self, m.slot) is None
+        if not apr:
+            return _Mode(False, on_device=lambda job: tuple(t.to(self.dev) for t in job), set_state=self._reset, iteration=self._iteration,
+                         prepare=lambda m, job: first_use(m) and self._run(m, job, iters=0), read=self._refined_pose,
+                         read_own=self._refined_pose, finish=lambda pose, _, __, losses: (pose, losses))
+        if self.apr is None:
+            raise RuntimeError("nefes_amd: PoseRefiner was built without pose_model=")
+
+        def before_capture():
+            for p in self.apr.parameters():
+                p.grad = None                              # the captured backward allocates them in the graph's pool and keeps them there
+            self._captured_apr_opt = self.apr_opt          # (the graph updates THIS optimizer's state tensors)
+
+        def check(i, iters):                               # (tensors, read after the loop: no host sync behind iteration 0)
+            return self._verification(as_tensors=True) if verification and i in (0, iters - 1) else None
+        return _Mode(True, on_device=tuple, set_state=self._apr_set_state, iteration=self._apr_iteration,
+                     prepare=lambda m, job: (m.set_state(*job), first_use(m) and self._capture(m)), read=self.predicted_pose,
+                     read_own=lambda: self.predicted_pose().detach().clone(), finish=self._apr_result, before_capture=before_capture,
+                     before=self.predicted_pose, check=check)
+
+    def _capture(self, m):
+        """One iteration of mode `m` (forward, backward, optimizer step; mode 2: regression network, svd_reg, ..., torch's Adam over its
+        weights) as ONE HIP graph in the mode's slot, after a warm-up on a side stream (allocator, MIOpen plans, Adam state).  The caller
+        re-writes the image's state afterwards: the warm-up steps moved it."""
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(side):
             for _ in range(3):
-                self._iteration()
+                m.iteration()
         torch.cuda.current_stream(self.dev).wait_stream(side)
         torch.cuda.synchronize(self.dev)
+        m.before_capture()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._iteration()
-        self.graph = g
+            m.iteration()
+        setattr(self, m.slot, g)
 
     def replay(self, apr=False):
         """One iteration as the captured graph -- after a HOST check that what the graph reads in place is current: the prepared form of
@@ -367,38 +401,46 @@ class PoseRefiner:
             self._sync_upcos()
         (self.apr_graph if apr else self.graph).replay()
 
+    def _step(self, m, i, iters, losses, checks):
+        """Iteration i of `iters` on the current stream: replayed or eager, its loss into losses[i], what the mode records behind it."""
+        if self.use_graph and getattr(self, m.slot) is not None:
+            self.replay(apr=m.apr)
+        else:
+            m.iteration()
+        losses[i] = self.loss
+        seen = m.check(i, iters)
+        if seen is not None:
+            checks.append(seen)
+
+    def _run(self, m, job, iters):
+        """One image (or one batch) through mode `m` on the current stream: state, capture on first use and the state again, `iters`
+        iterations, the mode's result."""
+        job = m.on_device(job)
+        m.set_state(*job)
+        if self.use_graph and getattr(self, m.slot) is None:
+            self._capture(m)
+            m.set_state(*job)
+        before = m.before()
+        losses, checks = torch.empty((iters,) + tuple(self.loss.shape), device=self.dev), []
+        for i in range(iters):
+            self._step(m, i, iters, losses, checks)
+        return m.finish(m.read(), before, checks, losses)
+
     def refine(self, init_c2w, feature_target, hist, iters=50):
         """One image (images=1): (refined 4x4 c2w, losses [iters]).  A batch (images=B): init_c2w [B,4,4], feature_target
         [B,C,h,w], hist [B,10] -> (refined poses [B,4,4], losses [iters,B]), each image as if refined alone."""
-        init_c2w, feature_target, hist = init_c2w.to(self.dev), feature_target.to(self.dev), hist.to(self.dev)
-        self._reset(init_c2w, feature_target, hist)
-        if self.use_graph and self.graph is None:
-            self._capture()
-            self._reset(init_c2w, feature_target, hist)
-        losses = torch.empty((iters,) + tuple(self.loss.shape), device=self.dev)
-        for i in range(iters):
-            if self.use_graph:
-                self.replay()
-            else:
-                self._iteration()
-            losses[i] = self.loss
-        with torch.no_grad():
-            if self.B == 1:
-                return self.model(0).detach().clone(), losses
-            return self.model(torch.arange(self.B, device=self.dev)).detach().clone(), losses
+        return self._run(self._mode(), (init_c2w, feature_target, hist), iters)
 
     refine_batch = refine
 
     # ---- train_on_batch / DFM_post_processing (pose_only=2) ------------------------------------------------------------
     def apr_loss_and_grad(self):
         """Loss at the working network's current parameters; gradients into their .grad (no optimizer step)."""
-        loss, _ = self._loss_into_buffer()
+        loss, _ = self._loss()
         params = [p for p in self.apr.parameters() if p.requires_grad]
         # loss.backward() in the reference (train_on_batch, DFM_pose_refine.py:318) tolerates parameters the loss never touches --
         # DFNet's adaptation_layers with return_feature=False (feature/dfnet.py:142): their .grad stays None and Adam skips them
-        if getattr(self, "_one", None) is None or self._one.shape != loss.shape:
-            self._one = torch.ones_like(loss)              # the root gradient, once (as loss_and_grad does)
-        for p, g in zip(params, torch.autograd.grad(loss, params, grad_outputs=self._one, allow_unused=True)):
+        for p, g in zip(params, torch.autograd.grad(loss, params, grad_outputs=self._one_like(loss), allow_unused=True)):
             p.grad = g
         if loss.data_ptr() != self.loss.data_ptr():
             self.loss.copy_(loss.detach())
@@ -442,14 +484,11 @@ class PoseRefiner:
             for bw, bb in zip(self.apr.buffers(), self.apr_base.buffers()):
                 bw.copy_(bb.to(dev))                                       # deepcopy resets BatchNorm statistics too
             self.hist.copy_(hist.to(dev).reshape(1, 10))
-            expo = getattr(self.coarse, "exposure_embedding", None)
-            if (self.fused_glue and getattr(self.args, "encode_hist", False) and expo is not None
-                    and not any(p.requires_grad for p in expo.parameters())):
-                a = self.coarse.exposure_coefficients(self.hist)
-                if self._affine is None:
-                    self._affine = a.clone()
-                else:
-                    self._affine.copy_(a)
+            self._exposure_into_affine()
+
+    def _apr_set_state(self, photo, feature_target, hist):
+        self._apr_image_state(photo, feature_target, hist)
+        self._apr_fresh_adam()
 
     def _apr_iteration(self):
         self.apr_loss_and_grad()
@@ -469,66 +508,56 @@ class PoseRefiner:
         state is zeroed in place instead -- the same thing to Adam (step 0, zero moments)."""
         if self.apr_graph is None:
             self.apr_opt = self._apr_adam(self.apr_opt.param_groups[0]["lr"])
-            return
-        with torch.no_grad():
-            for st in self.apr_opt.state.values():
-                for v in st.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
+        else:
+            _zero_optimizer_state(self.apr_opt)
 
-    def _capture_apr(self):
-        """One iteration of train_on_batch -- regression network, svd_reg, render, FusionNet, loss, backward to the network's weights,
-        Adam -- as ONE HIP graph.  Possible since round 5: svd_reg is a kernel (torch.svd calls a solver and checks its status on the
-        host), the target's share of the loss is prepared outside.  Warm-up on a side stream as _capture does; the caller re-writes the
-        image's state afterwards (the warm-up steps moved the network)."""
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                self._apr_iteration()
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        for p in self.apr.parameters():
-            p.grad = None                                   # the captured backward allocates them in the graph's pool and keeps them there
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._apr_iteration()
-        self.apr_graph = g
-        self._captured_apr_opt = self.apr_opt               # (the graph updates THIS optimizer's state tensors)
+    def _apr_result(self, pose, first, checks, losses):
+        """What DFM_post_processing records for the image (:233-250): the refined network's pose, or the one from before the loop when the
+        verification step (iterations 0 and iters - 1) finds PSNR or SSIM lower after the loop than before it."""
+        info = {"retreat": False}
+        if len(checks) == 2:
+            (p0, s0), (p1, s1) = [(float(a), float(b)) for a, b in checks]
+            info = {"psnr": (p0, p1), "ssim": (s0, s1), "retreat": p1 < p0 or s1 < s0}       # :242-250
+            if info["retreat"]:
+                pose = first
+        return pose.detach().clone(), losses, info
 
     def refine_apr(self, photo, feature_target, hist, iters=50, verification=True):
         """One query image, `pose_only=2`: `photo` [1,3,H,W], `feature_target` [C,H,W] (the query image's features at full
         resolution; cropped here as :125 does).  Returns (pose [3,4] in the regression network's coordinates, losses [iters],
         info = dict(psnr=(first, last), ssim=(first, last), retreat=bool)).  PoseRefiner(graph=True): the iteration is captured on
         first use and replayed (the regression network must be capturable: no host reads, static shapes)."""
-        if self.apr is None:
-            raise RuntimeError("nefes_amd: PoseRefiner was built without pose_model=")
-        dev = self.dev
-        self._apr_image_state(photo, feature_target, hist)
-        self._apr_fresh_adam()
-        if self.use_graph and self.apr_graph is None:
-            self._capture_apr()
-            self._apr_image_state(photo, feature_target, hist)
-            self._apr_fresh_adam()
-        first = self.predicted_pose()
-        losses = torch.empty(iters, device=dev)
-        checks = []
-        for i in range(iters):
-            if self.apr_graph is not None:
-                self.replay(apr=True)
-            else:
-                self._apr_iteration()
-            losses[i] = self.loss
-            if verification and (i == 0 or i == iters - 1):
-                checks.append(self._verification(as_tensors=True))        # (read after the loop: no host sync behind iteration 0)
-        pose = self.predicted_pose()
-        info = {"retreat": False}
-        if verification and len(checks) == 2:
-            (p0, s0), (p1, s1) = [(float(a), float(b)) for a, b in checks]
-            info = {"psnr": (p0, p1), "ssim": (s0, s1), "retreat": bool(p1 < p0) or bool(s1 < s0)}       # :242-250
-            if info["retreat"]:
-                pose = first
-        return pose.detach().clone(), losses, info
+        return self._run(self._mode(apr=True, verification=verification), (photo, feature_target, hist), iters)
+
+
+_nothing = lambda *args: None
+
+
+class _Mode(typing.NamedTuple):
+    """What PoseRefiner's two loops differ in -- mode 3 (`refine`: optimise (r, t)) and mode 2 (`refine_apr`: train a copy of a regression
+    network) -- as bound methods of one refiner (PoseRefiner._mode).  Capture (_capture), loop (_run, _step) and stream driver (_drive)
+    are written once on top of it; where the modes order their device work differently, the difference is a field here."""
+    apr: bool                   # mode 2; its captured iteration lives in `apr_graph` (mode 3: `graph`)
+    on_device: typing.Callable  # job -> job with its tensors on the device (mode 2 copies inside set_state instead)
+    set_state: typing.Callable  # (*job): the image's state and a fresh optimizer state, written in place
+    iteration: typing.Callable  # (): one eager iteration -- what is warmed up, captured, and run where nothing is replayed
+    prepare: typing.Callable    # (mode, job): what _drive has the refiner do on the CALLER'S stream first (capture on first use)
+    read: typing.Callable       # () -> the result on the device
+    read_own: typing.Callable   # the same on a refiner's own stream (mode 2 copies it there)
+    finish: typing.Callable     # (read(), before(), [check() ...], losses) -> what the caller gets
+    before_capture: typing.Callable = _nothing      # (): between warm-up and capture
+    before: typing.Callable = _nothing              # () -> recorded in front of the loop (mode 2: the regression network's first pose)
+    check: typing.Callable = _nothing               # (i, iters) -> recorded behind iteration i, or None (mode 2: the verification pair)
+    slot = property(lambda self: "apr_graph" if self.apr else "graph")
+
+
+def _zero_optimizer_state(opt):
+    """A torch optimizer back to step 0 with zero moments, IN PLACE: a captured graph keeps updating the same state tensors."""
+    with torch.no_grad():
+        for st in opt.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
 
 
 def _apr_kernels_bit_stable(r, photo, feature_target, hist, trials=6):
@@ -554,8 +583,7 @@ def _apr_kernels_bit_stable(r, photo, feature_target, hist, trials=6):
     side = torch.cuda.Stream(device=dev)
 
     def run(storm):
-        r._apr_image_state(photo, feature_target, hist)
-        r._apr_fresh_adam()
+        r._apr_set_state(photo, feature_target, hist)
         torch.cuda.synchronize(dev)
         keep = []
         if storm:
@@ -584,78 +612,6 @@ def _apr_kernels_bit_stable(r, photo, feature_target, hist, trials=6):
     return bool(ok)
 
 
-def refine_apr_concurrently(refiners, jobs, iters=50, verification=True, verify_kernels=True):
-    """refine_apr for K query images at the same time (the shipped default mode, `pose_only = 2`): one PoseRefiner(pose_model=...) and
-    one HIP stream per image, iterations replayed round-robin like refine_concurrently.  jobs = [(photo, feature_target, hist), ...] ->
-    [(pose [3,4], losses [iters], info), ...] in job order, each identical to what refine_apr returns for that image alone.
-    The regression network's kernels are the caller's: `verify_kernels` first TRIES them next to this library's field kernels
-    (_apr_kernels_bit_stable) and raises if a result moves -- run such a network's images one after the other (refine_apr)."""
-    if not refiners or not jobs:
-        raise ValueError("nefes_amd: refine_apr_concurrently needs at least one PoseRefiner and one job")
-    if len({id(r) for r in refiners}) != len(refiners):
-        raise ValueError("nefes_amd: refine_apr_concurrently needs DISTINCT PoseRefiner objects")
-    if any(r.apr is None for r in refiners):
-        raise RuntimeError("nefes_amd: refine_apr_concurrently needs refiners built with pose_model=")
-    if len(jobs) > len(refiners):
-        out = []
-        for k in range(0, len(jobs), len(refiners)):
-            part = jobs[k:k + len(refiners)]
-            out += refine_apr_concurrently(refiners[:len(part)], part, iters, verification, verify_kernels)
-        return out
-    refiners = refiners[:len(jobs)]
-    dev = refiners[0].dev
-    _check_concurrent(refiners, apr=True)
-    if verify_kernels:
-        for r, job in zip(refiners, jobs):
-            if not _apr_kernels_bit_stable(r, *job):
-                raise RuntimeError("nefes_amd: this regression network's kernels (or torch's Adam / the verification step) do not give "
-                                   "bit-identical results next to another stream's field kernels (DESIGN.md 4.7): refine its images "
-                                   "one after the other with PoseRefiner.refine_apr")
-    for r, job in zip(refiners, jobs):                      # per-image state, capture (one refiner at a time, on the caller's stream)
-        r._apr_image_state(*job)
-        r._apr_fresh_adam()
-        if r.use_graph and r.apr_graph is None:
-            r._capture_apr()
-    cur = torch.cuda.current_stream(dev)
-    for r in refiners:
-        if getattr(r, "_own_stream", None) is None:
-            r._own_stream = torch.cuda.Stream(device=dev)
-        r._own_stream.wait_stream(cur)
-    firsts, losses, checks = [], [torch.empty(iters, device=dev) for _ in refiners], [[] for _ in refiners]
-    for r, job in zip(refiners, jobs):
-        with torch.cuda.stream(r._own_stream):
-            r._apr_image_state(*job)
-            r._apr_fresh_adam()
-            firsts.append(r.predicted_pose())
-    for i in range(iters):
-        for k, r in enumerate(refiners):
-            with torch.cuda.stream(r._own_stream):
-                if r.apr_graph is not None:
-                    r.replay(apr=True)
-                else:
-                    r._apr_iteration()
-                losses[k][i] = r.loss
-                if verification and (i == 0 or i == iters - 1):
-                    checks[k].append(r._verification(as_tensors=True))
-    poses = []
-    for r in refiners:
-        with torch.cuda.stream(r._own_stream):
-            poses.append(r.predicted_pose().detach().clone())
-    for r in refiners:
-        cur.wait_stream(r._own_stream)
-    torch.cuda.synchronize(dev)
-    outs = []
-    for k in range(len(refiners)):
-        info, pose = {"retreat": False}, poses[k]
-        if verification and len(checks[k]) == 2:
-            (p0, s0), (p1, s1) = [(float(a), float(b)) for a, b in checks[k]]
-            info = {"psnr": (p0, p1), "ssim": (s0, s1), "retreat": bool(p1 < p0) or bool(s1 < s0)}
-            if info["retreat"]:
-                pose = firsts[k]
-        outs.append((pose.detach().clone(), losses[k], info))
-    return outs
-
-
 def _check_concurrent(refiners, apr=False):
     """What refine_concurrently's guarantees rest on, checked instead of assumed.
     (1) No shared mutable state between streams: refiners that share a FusionNet must not update its BatchNorm's running statistics
@@ -681,6 +637,53 @@ def _check_concurrent(refiners, apr=False):
                              "refiners one after the other (PoseRefiner.refine)")
 
 
+
+
+def _drive(name, refiners, jobs, iters, mode_of, guard=None, sync=False):
+    """The stream driver of refine_concurrently / refine_apr_concurrently: rounds of len(refiners) jobs; per round the checks, capture on
+    first use (one refiner at a time, on the caller's stream), every refiner's own stream behind the caller's, the image's state written
+    on it, the iterations issued round-robin, the results read on the own streams, and the caller's stream behind them all."""
+    if not refiners or not jobs:
+        raise ValueError(f"nefes_amd: {name} needs at least one PoseRefiner and one job")
+    if len({id(r) for r in refiners}) != len(refiners):
+        raise ValueError(f"nefes_amd: {name} needs DISTINCT PoseRefiner objects (each owns the static buffers of its image)")
+    modes = [mode_of(r) for r in refiners]                 # (mode 2 refuses a refiner built without pose_model= here)
+    if len(jobs) > len(refiners):
+        return [out for k in range(0, len(jobs), len(refiners))
+                for out in _drive(name, refiners[:len(jobs[k:k + len(refiners)])], jobs[k:k + len(refiners)], iters, mode_of, guard, sync)]
+    refiners, modes = refiners[:len(jobs)], modes[:len(jobs)]
+    dev = refiners[0].dev
+    _check_concurrent(refiners, apr=modes[0].apr)
+    if guard is not None:
+        guard(refiners, jobs)
+    jobs = [m.on_device(job) for m, job in zip(modes, jobs)]
+    for m, job in zip(modes, jobs):
+        m.prepare(m, job)
+    cur = torch.cuda.current_stream(dev)
+    for r in refiners:
+        if getattr(r, "_own_stream", None) is None:
+            r._own_stream = torch.cuda.Stream(device=dev)
+        r._own_stream.wait_stream(cur)
+    losses = [torch.empty((iters,) + tuple(r.loss.shape), device=dev) for r in refiners]
+    before, checks, raw = [], [[] for _ in refiners], []
+    for r, m, job in zip(refiners, modes, jobs):
+        with torch.cuda.stream(r._own_stream):
+            m.set_state(*job)
+            before.append(m.before())
+    for i in range(iters):
+        for r, m, l, c in zip(refiners, modes, losses, checks):
+            with torch.cuda.stream(r._own_stream):
+                r._step(m, i, iters, l, c)
+    for r, m in zip(refiners, modes):
+        with torch.cuda.stream(r._own_stream):
+            raw.append(m.read_own())
+    for r in refiners:
+        cur.wait_stream(r._own_stream)
+    if sync:
+        torch.cuda.synchronize(dev)
+    return [m.finish(*done) for m, done in zip(modes, zip(raw, before, checks, losses))]
+
+
 def refine_concurrently(refiners, jobs, iters=50):
     """K query images refined AT THE SAME TIME: one PoseRefiner (its own static buffers and captured graph; the frozen networks can be
     shared) and one HIP stream per image, replays issued round-robin.  An iteration is ~1.45 ms of field kernels, which hold the whole
@@ -692,45 +695,20 @@ def refine_concurrently(refiners, jobs, iters=50):
     More jobs than refiners: rounds of len(refiners) images (the last one smaller).
     Refiners that share a FusionNet are constructed with bn_running_stats=False, and every refiner runs on the library's own kernels
     (_check_concurrent refuses anything else: see there)."""
-    if not refiners or not jobs:
-        raise ValueError("nefes_amd: refine_concurrently needs at least one PoseRefiner and one job")
-    if len({id(r) for r in refiners}) != len(refiners):
-        raise ValueError("nefes_amd: refine_concurrently needs DISTINCT PoseRefiner objects (each owns the static buffers of its image)")
-    if len(jobs) > len(refiners):
-        out = []
-        for k in range(0, len(jobs), len(refiners)):
-            part = jobs[k:k + len(refiners)]
-            out += refine_concurrently(refiners[:len(part)], part, iters)
-        return out
-    refiners = refiners[:len(jobs)]
-    dev = refiners[0].dev
-    _check_concurrent(refiners)
-    jobs = [tuple(t.to(dev) for t in job) for job in jobs]
-    for r, job in zip(refiners, jobs):
-        if r.use_graph and r.graph is None:
-            r.refine(*job, iters=0)                        # reset, warm-up, capture (on the caller's stream, one refiner at a time)
-    cur = torch.cuda.current_stream(dev)
-    for r in refiners:
-        if getattr(r, "_own_stream", None) is None:
-            r._own_stream = torch.cuda.Stream(device=dev)
-        r._own_stream.wait_stream(cur)
-    losses = [torch.empty((iters,) + tuple(r.loss.shape), device=dev) for r in refiners]
-    for r, job in zip(refiners, jobs):
-        with torch.cuda.stream(r._own_stream):
-            r._reset(*job)
-    for i in range(iters):
-        for r, l in zip(refiners, losses):
-            with torch.cuda.stream(r._own_stream):
-                if r.use_graph:
-                    r.replay()
-                else:
-                    r._iteration()
-                l[i] = r.loss
-    outs = []
-    for r, l in zip(refiners, losses):
-        with torch.cuda.stream(r._own_stream), torch.no_grad():
-            pose = r.model(0) if r.B == 1 else r.model(torch.arange(r.B, device=dev))
-            outs.append((pose.detach().clone(), l))
-    for r in refiners:
-        cur.wait_stream(r._own_stream)
-    return outs
+    return _drive("refine_concurrently", refiners, jobs, iters, lambda r: r._mode())
+
+
+def refine_apr_concurrently(refiners, jobs, iters=50, verification=True, verify_kernels=True):
+    """refine_apr for K query images at the same time (the shipped default mode, `pose_only = 2`): one PoseRefiner(pose_model=...) and
+    one HIP stream per image, iterations replayed round-robin like refine_concurrently.  jobs = [(photo, feature_target, hist), ...] ->
+    [(pose [3,4], losses [iters], info), ...] in job order, each identical to what refine_apr returns for that image alone.
+    The regression network's kernels are the caller's: `verify_kernels` first TRIES them next to this library's field kernels
+    (_apr_kernels_bit_stable) and raises if a result moves -- run such a network's images one after the other (refine_apr)."""
+    def guard(refiners, jobs):
+        for r, job in zip(refiners, jobs):
+            if not _apr_kernels_bit_stable(r, *job):
+                raise RuntimeError("nefes_amd: this regression network's kernels (or torch's Adam / the verification step) do not give "
+                                   "bit-identical results next to another stream's field kernels (DESIGN.md 4.7): refine its images "
+                                   "one after the other with PoseRefiner.refine_apr")
+    return _drive("refine_apr_concurrently", refiners, jobs, iters, lambda r: r._mode(apr=True, verification=verification),
+                  guard=guard if verify_kernels else None, sync=True)

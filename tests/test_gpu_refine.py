@@ -531,3 +531,69 @@ def test_verification_step_through_the_kernels_equals_the_torch_expressions(gold
         PoseRefiner.FUSED_VERIFICATION = True
     assert abs(on[0] - off[0]) <= 5e-6 * abs(off[0]) and abs(on[1] - off[1]) <= 5e-6, (on, off)
     assert abs(on[0] - g["m2_psnr"][0, 1]) < 2e-2 and abs(on[1] - g["m2_ssim"][0, 1]) < 2e-4, (on, g["m2_psnr"][0, 1], g["m2_ssim"][0, 1])
+
+
+def _loss_call(which):
+    """(f, x): f(x, out=None) -> one of the three feature losses on fixed inputs, x the [.., C, ..] features it differentiates."""
+    from nefes_amd import ops
+    g = torch.Generator().manual_seed(21)
+    if which == "cosine":
+        C, P = 3, 1000
+        x, b = torch.randn(C, P, generator=g).to(DEV), torch.randn(C, P, generator=g).to(DEV)
+        return (lambda t, out=None: ops.cosine_feature_loss(t, b, out=out)), x
+    C, h, w, ts = 5, 15, 20, 4
+    H, W = h * ts, w * ts
+    x, tgt = torch.randn(1, C, h, w, generator=g).to(DEV), torch.randn(C, H - 20, W - 20, generator=g).to(DEV)
+    if which == "upsampled":
+        return (lambda t, out=None: ops.upsampled_cosine_loss(t, tgt, (H, W), crop=10, out=out)), x
+    prep = ops.UpcosTarget(C, h, w, H, W, 10, DEV).update(tgt)
+    return (lambda t, out=None: ops.upsampled_cosine_loss_prepared(t, prep, out=out)), x
+
+
+@pytest.mark.parametrize("which", ["cosine", "upsampled", "prepared"])
+def test_feature_losses_write_their_value_into_the_callers_buffer(which):
+    """`out=` of ops.cosine_feature_loss (C, P = 3, 1000), ops.upsampled_cosine_loss (C, h, w, ts = 5, 15, 20, 4) and
+    ops.upsampled_cosine_loss_prepared (5, 15, 20 -> 60, 80, crop 10): the forward kernel writes the value into the caller's 0-d fp32
+    buffer and the returned loss shares its storage; value and input gradient are bit-equal to the call without `out`; a later call
+    without `out` leaves the buffer alone (no module-level state names it); a buffer of the wrong kind is refused, not ignored."""
+    f, x = _loss_call(which)
+    xa, xb = x.clone().requires_grad_(), x.clone().requires_grad_()
+    plain = f(xa)
+    (2.0 * plain).backward()
+    buf = torch.full((), -7.0, device=DEV)
+    into = f(xb, out=buf)
+    (2.0 * into).backward()
+    assert torch.equal(buf, plain.detach()) and torch.equal(into.detach(), plain.detach())
+    assert into.untyped_storage().data_ptr() == buf.untyped_storage().data_ptr() and into.data_ptr() == buf.data_ptr()
+    assert not buf.requires_grad and torch.equal(xa.grad, xb.grad) and float(xa.grad.abs().max()) > 0
+    kept = buf.clone()
+    other = f(-x.roll(1, -1))                          # another value, no `out`: a fresh tensor
+    assert not torch.equal(other, kept) and other.data_ptr() != buf.data_ptr() and torch.equal(buf, kept)
+    for bad in (torch.zeros(1, device=DEV), torch.zeros((), device=DEV, dtype=torch.float64), torch.zeros((), device=DEV).requires_grad_()):
+        with pytest.raises(ValueError, match="`out`"):
+            f(x, out=bad)
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_quiet_refiner_leaves_the_shared_fusion_nets_batchnorm_bookkeeping_to_others(golden, graph):
+    """PoseRefiner(bn_running_stats=False) passes `track_stats=False` with its OWN FusionNet calls (the refine50 scene, a shared
+    FusionNet, 2 iterations): the module's `track_bn_stats` stays True, the refiner's iterations leave num_batches_tracked, running_mean
+    and running_var bit-equal, and a plain train-mode forward_prepared of the same module afterwards advances the counter by exactly
+    one.  (Until the flag became an argument the refiner wrote it onto the module and never restored it: every later train-mode forward
+    by anyone else silently stopped updating the statistics.)"""
+    from tests.test_gpu_refine50 import nets, refiner as refiner50
+    g = golden("refine50")
+    shared = nets(g)
+    fnet = shared[0].fusion_net
+    bn = fnet.net[-1]
+    quiet = refiner50(g, graph=graph, networks=shared, bn_running_stats=False)
+    before = (int(bn.num_batches_tracked), bn.running_mean.clone(), bn.running_var.clone())
+    quiet.refine(T(g["init_c2w"][0]), T(g["target_low"]), T(g["hist"]), iters=2)
+    torch.cuda.synchronize()
+    assert fnet.track_bn_stats is True and "track_bn_stats" not in vars(fnet)
+    assert int(bn.num_batches_tracked) == before[0] and torch.equal(bn.running_mean, before[1]) and torch.equal(bn.running_var, before[2])
+    assert bn.training
+    x = torch.randn(1, 3 + int(g["C"]), quiet.h, quiet.w, generator=torch.Generator().manual_seed(3)).to(DEV)
+    fnet.forward_prepared(x)
+    torch.cuda.synchronize()
+    assert int(bn.num_batches_tracked) == before[0] + 1 and not torch.equal(bn.running_mean, before[1])

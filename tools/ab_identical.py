@@ -13,7 +13,12 @@ before the call and digested whole, so what a kernel must not touch is compared 
     NEFES_HIP_LIB=<lib> python tools/ab_identical.py --train
 prints, instead, the digests of one train-mode forward + backward through the four autograd Functions of nefes_amd/train.py (raw_t,
 every parameter gradient, the gradients of the rays or of the encoding and viewdirs) at TRAIN_CASES: for A/B revisions of the HOST code
-on one library.  37 rays x 24 samples = seven tiles, the last ragged."""
+on one library.  37 rays x 24 samples = seven tiles, the last ragged.
+    NEFES_HIP_LIB=<lib> python tools/ab_identical.py --refine
+prints, instead, the digests of what the refinement loop of nefes_amd/refine.py returns (pose, loss curve, the numbers of `info`) at
+REFINE_CASES, 6 iterations each, on the scene of tests/golden/refine50.npz (30 x 40 rays, 64 + 64 samples, 8 x 128 networks, C = 128):
+for A/B revisions of the HOST code on one library.  Only PoseRefiner's constructor, refine, refine_apr, refine_concurrently and
+refine_apr_concurrently are called."""
 import ctypes as C
 import hashlib, os, sys
 import torch
@@ -264,7 +269,111 @@ def run_train():
             print(f"{tag:30s} {k:34s} {tuple(t.shape)!s:18s} {dig(t)}", flush=True)
 
 
+# (tag, PoseRefiner arguments, what is run): both modes replayed and eager, every route of the up-sampled loss, the torch glue, a batch,
+# a second image through an existing graph (state reset in place), and both stream drivers (rounds of two included)
+REFINE_CASES = (("mode3 graph", dict(graph=True), "twice"),
+                ("mode3 eager", dict(graph=False), "once"),
+                ("mode3 upsample prepared", dict(graph=True, upsample=True, plain=True, prepared=True), "once"),
+                ("mode3 upsample one-pass", dict(graph=True, upsample=True, plain=True, prepared=False), "once"),
+                ("mode3 upsample hist world", dict(graph=True, upsample=True), "once"),
+                ("mode3 torch glue", dict(graph=False, fused_glue=False), "once"),
+                ("mode3 images=2", dict(graph=True, images=2), "batch"),
+                ("mode2 graph", dict(graph=True, apr=0), "apr twice"),
+                ("mode2 eager", dict(graph=False, apr=0), "apr twice"),
+                ("mode3 two streams", dict(graph=True, bn_running_stats=False), "streams"),
+                ("mode2 two streams", dict(graph=True, apr=0, bn_running_stats=False), "apr streams"))
+
+
+def run_refine():
+    import types
+    import numpy as np
+    from nefes_amd.field import NeRFH_NFF
+    from nefes_amd.refine import PoseRefiner, refine_apr_concurrently, refine_concurrently
+    from oracle import refine_cpu as RC
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gd = dict(np.load(os.path.join(root, "tests", "golden", "refine50.npz")))
+    T = lambda a: torch.from_numpy(np.asarray(a))
+    iters, (H, W, focal) = 6, gd["hwf"].tolist()
+    H, W = int(H), int(W)
+
+    class TinyAPR(torch.nn.Module):            # the fixture's stand-in regression network (tests/test_gpu_refine50.py)
+        def __init__(self, k):
+            super().__init__()
+            self.fc = torch.nn.Linear(12, 12)
+            with torch.no_grad():
+                self.fc.weight.copy_(T(gd["m2_weight"][k]))
+                self.fc.bias.copy_(T(gd["m2_bias"][k]))
+
+        def forward(self, x):
+            return self.fc(torch.nn.functional.adaptive_avg_pool2d(x, 2).reshape(x.shape[0], -1))
+
+    def nets():
+        coarse = NeRFH_NFF('coarse', W=int(gd["Wd"]), f_dim=int(gd["C"]))
+        fine = NeRFH_NFF('fine', W=int(gd["Wd"]), f_dim=int(gd["C"]), encode_appearance=True, encode_transient=True)
+        gain, decay, sg = (float(v) for v in gd["scene"])
+        with torch.no_grad():
+            coarse.exposure_embedding.params.copy_(T(gd["exposure_params"]))
+            for n in (coarse, fine):
+                RC.structure_scene(dict(n.named_parameters()), gain, decay, sg)
+        return coarse.requires_grad_(False).to(dev), fine.requires_grad_(False).to(dev)
+
+    def refiner(networks, apr=None, plain=False, prepared=None, **more):
+        coarse, fine = networks
+        args = types.SimpleNamespace(nerfh_nff=True, use_fine_only=False, NeRFW=True, transient_at_test=True, encode_hist=not plain)
+        kw = dict(network_query_fn=None, perturb=0., N_importance=int(gd["Ni"]), N_samples=int(gd["Nc"]), network_fn=coarse, network_fine=fine,
+                  use_viewdirs=True, white_bkgd=False, raw_noise_std=0., test_time=True, args=args, ndc=False, lindisp=False)
+        world = None if plain else dict(pose_scale=float(gd["pose_scale"]), pose_scale2=float(gd["pose_scale2"]),
+                                        move_all_cam_vec=gd["move_all_cam_vec"].tolist())
+        if apr is not None:
+            more.update(pose_model=TinyAPR(apr), svd_reg=True, learning_rate=float(gd["m2_lr"]))
+        if prepared is not None:
+            PoseRefiner.PREPARED_TARGET = prepared
+        return PoseRefiner(kw, args, (H, W, focal), float(gd["near"]), float(gd["far"]), tinyscale=int(gd["tinyscale"]), lr_r=float(gd["lr"][0]),
+                           lr_t=float(gd["lr"][1]), world_setup=world, device=dev, **more)
+
+    def show(tag, result):
+        torch.cuda.synchronize()
+        pose, losses, info = (tuple(result) + ({},))[:3]
+        nums = torch.tensor([float(v) for k in sorted(info) for v in (info[k] if isinstance(info[k], tuple) else (info[k],))], dtype=torch.float64)
+        print(f"{tag:44s} pose {dig(pose)}  losses {dig(losses)}  info {dig(nums)}", flush=True)
+
+    full = torch.nn.functional.interpolate(T(gd["target_low"])[None], size=(H, W), mode="bicubic")[0]       # on the CPU, as the fixture's generator
+    photo, hist = T(gd["photo_u8"]).float()[None] / 255., T(gd["hist"])
+    default_prepared = PoseRefiner.PREPARED_TARGET
+    shared = nets()
+    for tag, kw, what in REFINE_CASES:
+        PoseRefiner.PREPARED_TARGET = default_prepared
+        target = full[:, 10:-10, 10:-10] if kw.get("upsample") else T(gd["target_low"])
+        job = lambda k: (T(gd["init_c2w"][k]), target, hist)
+        if what in ("once", "twice"):
+            r = refiner(shared, **kw)
+            show(tag, r.refine(*job(0), iters=iters))
+            if what == "twice":
+                show(tag + ", next image", r.refine(*job(3), iters=iters))
+        elif what == "batch":
+            r = refiner(shared, **kw)
+            show(tag, r.refine(T(gd["init_c2w"][[0, 3]]), torch.stack([target, target.flip(-1)]), torch.stack([hist.reshape(-1)] * 2), iters=iters))
+        elif what == "apr twice":
+            r = refiner(shared, **kw)
+            show(tag, r.refine_apr(photo, full, hist, iters=iters, verification=True))
+            r.apr_base = TinyAPR(3)
+            show(tag + ", next image", r.refine_apr(photo, full, hist, iters=iters, verification=True))
+        elif what == "streams":
+            rs = [refiner(shared, **kw) for _ in range(2)]
+            for n_jobs, starts in ((2, (0, 3)), (3, (3, 0, 5))):
+                for j, out in enumerate(refine_concurrently(rs, [job(k) for k in starts], iters=iters)):
+                    show(f"{tag}, {n_jobs} jobs [{j}]", out)
+        elif what == "apr streams":
+            rs = [refiner(shared, **dict(kw, apr=k)) for k in (0, 3)]
+            for j, out in enumerate(refine_apr_concurrently(rs, [(photo, full, hist)] * 2, iters=iters)):
+                show(f"{tag} [{j}]", out)
+    PoseRefiner.PREPARED_TARGET = default_prepared
+
+
 print("# lib", os.environ.get("NEFES_HIP_LIB") or "shipped", "ABI", L.ABI_VERSION)
+if "--refine" in sys.argv[1:]:
+    run_refine()
+    sys.exit(0)
 if "--train" in sys.argv[1:]:
     run_train()
     sys.exit(0)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Which Python lines of one EAGER refinement iteration launch torch's own small kernels (fills, copies, element-wise glue): the
 iteration is a replayed graph in production, so each of them costs its ~4 us of execution, not a launch -- this lists them with the
-source line that asked for them.  python tools/loop_ops.py [mode]"""
+source line that asked for them.  python tools/loop_ops.py [mode]
+With --launches, instead: the count of every device kernel, autograd Function and HIP runtime call of that iteration (the launch census
+two revisions of the host code are compared by: profiles/refine_one_loop/README.md).  python tools/loop_ops.py [mode] --launches"""
 import os, sys, collections
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -9,7 +11,8 @@ from torch.profiler import profile, ProfilerActivity
 import bench
 from nefes_amd import refine as R
 
-mode = sys.argv[1] if len(sys.argv) > 1 else "upsampled"
+argv = [a for a in sys.argv[1:] if a != "--launches"]
+mode = argv[0] if argv else "upsampled"
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
 keep = {}
@@ -27,6 +30,14 @@ ref = keep["ref"]
 with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], with_stack=True) as prof:
     ref._iteration()
     torch.cuda.synchronize()
+if "--launches" in sys.argv[1:]:
+    census = collections.Counter()
+    for e in prof.key_averages():
+        if getattr(e, "self_device_time_total", getattr(e, "self_cuda_time_total", 0)) > 0 or e.key.startswith("hip"):
+            census[e.key] += e.count
+    for name, n in sorted(census.items()):
+        print(f"{n:4d} x {name}")
+    sys.exit(0)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rows = collections.Counter()
 for ev in prof.events():
