@@ -549,6 +549,25 @@ int nefes_upcos_loss_fwd(int C, int h, int w, int OH, int OW, int crop, const fl
 int nefes_upcos_loss_bwd(int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const double* scratch,
                          const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt, const int* ty_first,
                          const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream);
+/* feature_loss with per_pixel=True (`--per_pixel`, dm/options.py:73; DFM_pose_refine.py:227-233): torch.nn.CosineSimilarity(dim=0,
+ * eps=1e-6) over the CHANNELS of every pixel, a, b dev [G,C,P] contiguous: G groups (images), each with its own mean,
+ *     loss = sum_g (1 - mean_p cos(a[g,:,p], b[g,:,p])),      float64 accumulation in ascending c, no atomics, fixed summation order.
+ * scratch: dev doubles, nefes_pixcos_scratch_doubles(G, P) of them, kept by the caller for the backward; its first G doubles are the
+ * groups' mean cosines.  g_a [G,C,P] = g_loss[0] * d loss / d a.  The normalisation is per pixel: there is no Gram / prepared-target
+ * form of this loss. */
+size_t nefes_pixcos_scratch_doubles(int G, int64_t P);
+int nefes_pixcos_loss_fwd(int G, int C, int64_t P, const float* a, const float* b, double* scratch, float* loss, void* stream);
+int nefes_pixcos_loss_bwd(int G, int C, int64_t P, const float* a, const float* b, const double* scratch, const float* g_loss, float* g_a,
+                          void* stream);
+/* The same loss ON the up-sampled, cropped image without materialising it (the per-pixel twin of nefes_upcos_loss_fwd / _bwd; any
+ * geometry those take): x dev [G,C,h,w], target dev [G,C,OH-2crop,OW-2crop]; scratch: nefes_uppixcos_scratch_doubles(G, OH, OW, crop)
+ * doubles (first G: the mean cosines); tmp dev [G*C, OH-2crop, w] floats; tx_* / ty_* and T as nefes_upcos_loss_bwd. */
+size_t nefes_uppixcos_scratch_doubles(int G, int OH, int OW, int crop);
+int nefes_uppixcos_loss_fwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, double* scratch,
+                            float* loss, void* stream);
+int nefes_uppixcos_loss_bwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const double* scratch,
+                            const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt, const int* ty_first,
+                            const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream);
 /* The same loss for a FIXED target (the refinement loop holds the query image's features for all opt_iter iterations of an image:
  * DFM_APR_refine.py:100-131), through the Gram matrices of the up-sampling.  Per channel up = Uy X Ux^T, so
  *     <up, target> = <X, Tt>, Tt = Uy^T target Ux;   |up|^2 = <X, Gy X Gx>, Gy = Uy^T Uy, Gx = Ux^T Ux;   |target|^2 a constant,

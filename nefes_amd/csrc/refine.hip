@@ -609,6 +609,208 @@ __global__ __launch_bounds__(256) void upcos_gather_rows_kernel(long outer, int 
     dst[idx] = gather_axis_table(gy, y, src + p * n_win * inner + q, inner);
 }
 
+// ---- per-pixel feature loss (`--per_pixel`, dm/options.py:73; DFM_pose_refine.py:227-233 with dim = channels) ----------------------
+// For maps a, b [G, C, P] (G groups = images, each with its own mean):
+//     cos_p = a_p.b_p / (max(|a_p|, eps) max(|b_p|, eps)),   loss = sum over groups of (1 - mean_p cos_p)
+//     d loss / d a[c,p] = -(g / P) (b[c,p] / (na' nb') - [|a_p| > eps] (a_p.b_p) a[c,p] / (|a_p|^3 nb'))     (a clamped norm is a constant)
+// The normalisation is per pixel, so all C values of a pixel are needed at once: there is no Gram form and NO PREPARED-TARGET FORM of
+// this loss (<up, t> = <X, Uy^T t Ux> needs ONE factor per channel in front of the sum over pixels; here every pixel has its own).
+// Forward: a workgroup owns kPixCols consecutive pixels (loads coalesced along P) and splits the channels into kPixSlices
+// contiguous slices, one wave each -- 66 000 pixels are only ~1 000 waves, and a wave that walks all 128 channels alone waits
+// out 128 memory latencies one after the other (measured at the loop's shape: 257 us; this form 106 us, profiles/per_pixel_loss).  A
+// thread walks its slice's c in ascending order with (a.b, |a|^2, |b|^2) in float64; slice 0 adds the four slices in order, leaves
+// stats [G][3][P] = (a.b, |a|, |b|) planes for the backward, and the workgroup's float64 sum of cos_p goes to part [G][nb]; a
+// finalising launch adds the partials in a fixed order: mean [G] (float64) and the float32 loss.  Backward: one launch from the
+// pixel's three numbers.  No atomics, fixed summation order: a step repeats bit for bit and can be captured.
+// scratch (doubles) = mean [G] | stats [G][3][P] | part [G][nb]
+constexpr int kPixCols = 64, kPixSlices = 4, kPixBlock = kPixCols * kPixSlices;      // (8 slices: the same time; 16: slower)
+
+// sh[0] = sum of sh[0 .. n) in a fixed tree order; n <= 512, every thread of the block calls
+__device__ __forceinline__ void pix_block_sum(double* sh, int n) {
+    __syncthreads();
+    for (int s = 256; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s && (int)threadIdx.x + s < n) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ double pix_cos(double dab, double na, double nb, double eps) {
+    return dab / ((na > eps ? na : eps) * (nb > eps ? nb : eps));
+}
+
+// the slices' sums of one pixel added in slice order by slice 0's thread -> stats planes, cos_p; then the workgroup's sum of cos_p
+// (fixed tree) in sh[0][0][0].  Every thread of the workgroup calls.
+__device__ __forceinline__ void pix_finish(double (*sh)[kPixSlices][kPixCols], double dab, double daa, double dbb, bool live, double eps,
+                                           double* st, long P) {
+    const int col = threadIdx.x % kPixCols, sl = threadIdx.x / kPixCols;
+    sh[0][sl][col] = dab; sh[1][sl][col] = daa; sh[2][sl][col] = dbb;
+    __syncthreads();
+    double cs = 0;
+    if (sl == 0 && live) {
+        double t[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            t[k] = sh[k][0][col];
+#pragma unroll
+            for (int q = 1; q < kPixSlices; ++q) t[k] += sh[k][q][col];
+        }
+        const double na = sqrt(t[1]), nb = sqrt(t[2]);
+        st[0] = t[0]; st[P] = na; st[2 * P] = nb;
+        cs = pix_cos(t[0], na, nb, eps);
+    }
+    __syncthreads();
+    double* red = &sh[0][0][0];
+    if (sl == 0) red[col] = cs;
+    pix_block_sum(red, kPixCols);
+}
+
+__global__ __launch_bounds__(kPixBlock) void pixcos_fwd_kernel(int C, long P, double eps, const float* __restrict__ a, const float* __restrict__ b,
+                                                               double* __restrict__ stats, double* __restrict__ part) {
+    __shared__ double sh[3][kPixSlices][kPixCols];
+    const int g = blockIdx.y, sl = threadIdx.x / kPixCols;
+    const long p = (long)blockIdx.x * kPixCols + threadIdx.x % kPixCols;
+    const int per = (C + kPixSlices - 1) / kPixSlices, c0 = sl * per, c1 = c0 + per < C ? c0 + per : C;
+    double dab = 0, daa = 0, dbb = 0;
+    if (p < P) {
+        const float* pa = a + (long)g * C * P + p;
+        const float* pb = b + (long)g * C * P + p;
+#pragma unroll 4
+        for (int c = c0; c < c1; ++c) {
+            const double x = pa[(long)c * P], y = pb[(long)c * P];
+            dab += x * y;
+            daa += x * x;
+            dbb += y * y;
+        }
+    }
+    pix_finish(sh, dab, daa, dbb, p < P, eps, stats + (long)g * 3 * P + p, P);
+    if (threadIdx.x == 0) part[(long)g * gridDim.x + blockIdx.x] = sh[0][0][0];
+}
+
+// mean[g] = (sum of the group's nb partials) / P;  loss = sum_g (1 - mean[g])
+__global__ __launch_bounds__(256) void pixcos_final_kernel(int G, int nb, double P, const double* __restrict__ part, double* __restrict__ mean,
+                                                           float* __restrict__ loss) {
+    __shared__ double sh[256];
+    double total = 0;
+    for (int g = 0; g < G; ++g) {
+        double acc = 0;
+        for (int i = threadIdx.x; i < nb; i += 256) acc += part[(long)g * nb + i];
+        sh[threadIdx.x] = acc;
+        pix_block_sum(sh, 256);
+        const double m = sh[0] / P;
+        __syncthreads();
+        if (threadIdx.x == 0) mean[g] = m;
+        total += 1.0 - m;
+    }
+    if (threadIdx.x == 0) *loss = (float)total;
+}
+
+// the two factors of the gradient at one pixel: g_a = k1 b - k2 a
+struct PixK {
+    double k1, k2;
+};
+__device__ __forceinline__ PixK pix_factors(double k, double dab, double na, double nb, double eps) {
+    const double nbc = nb > eps ? nb : eps;
+    PixK r;
+    r.k1 = na > eps ? k / (na * nbc) : k / (eps * nbc);
+    r.k2 = na > eps ? k * dab / (na * na * na * nbc) : 0.0;
+    return r;
+}
+
+__global__ __launch_bounds__(256) void pixcos_bwd_kernel(long n, int C, long P, double eps, const float* __restrict__ a, const float* __restrict__ b,
+                                                         const double* __restrict__ stats, const float* __restrict__ g_loss,
+                                                         float* __restrict__ g_a) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const long p = idx % P, g = idx / (P * C);
+    const double* st = stats + g * 3 * P + p;
+    const PixK f = pix_factors(-(double)g_loss[0] / (double)P, st[0], st[P], st[2 * P], eps);
+    g_a[idx] = (float)(f.k1 * (double)b[idx] - f.k2 * (double)a[idx]);
+}
+
+// The same loss ON the up-sampled, cropped map without the up-sampled map: the per-pixel twin of upcos_partial_kernel /
+// upcos_bwd_rows_kernel.  x [G*C, h, w], target [G*C, CH, CW] (UpCosArgs with C = G*C planes), Cg channels per group.
+// Forward: one workgroup per (group, window row r, segment of kPixCols columns), the channels in kPixSlices slices as above.  A thread
+// computes its x taps and clamped source columns once and interpolates every channel's value with up_value's expression and order
+// (x first, then y: the value bicubic_up_fwd_kernel would have written, bit for bit) from the channel's four source rows in x (2.4 MB
+// at the loop's shape: L2) -- the target row is the only HBM read.  part [G][CH][segments].
+__global__ __launch_bounds__(kPixBlock) void uppixcos_fwd_kernel(UpCosArgs a, int Cg, double eps, double* __restrict__ stats,
+                                                                 double* __restrict__ part) {
+    using namespace nefes_bicubic;
+    __shared__ double sh[3][kPixSlices][kPixCols];
+    const int r = blockIdx.x, seg = blockIdx.y, g = blockIdx.z, sl = threadIdx.x / kPixCols;
+    const int j = seg * kPixCols + threadIdx.x % kPixCols;
+    const long P = (long)a.CH * a.CW, plane = (long)a.h * a.w;
+    const int per = (Cg + kPixSlices - 1) / kPixSlices, c0 = sl * per, c1 = c0 + per < Cg ? c0 + per : Cg;
+    double dab = 0, daa = 0, dbb = 0;
+    if (j < a.CW) {
+        const Taps ty = taps_of(a.sy, r + a.o0), tx = taps_of(a.sx, j + a.o0);
+        long ro[4];
+        int xs[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            ro[i] = (long)clampi(ty.base - 1 + i, a.h) * a.w;
+            xs[i] = clampi(tx.base - 1 + i, a.w);
+        }
+        const float* src = a.x + (long)g * Cg * plane;
+        const float* tg = a.target + (long)g * Cg * P + (long)r * a.CW + j;
+#pragma unroll 4
+        for (int c = c0; c < c1; ++c) {
+            const float* pl = src + c * plane;
+            float rows[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float* rr = pl + ro[i];
+                rows[i] = rr[xs[0]] * tx.w[0] + rr[xs[1]] * tx.w[1] + rr[xs[2]] * tx.w[2] + rr[xs[3]] * tx.w[3];
+            }
+            const double xv = rows[0] * ty.w[0] + rows[1] * ty.w[1] + rows[2] * ty.w[2] + rows[3] * ty.w[3];
+            const double yv = tg[c * P];
+            dab += xv * yv;
+            daa += xv * xv;
+            dbb += yv * yv;
+        }
+    }
+    pix_finish(sh, dab, daa, dbb, j < a.CW, eps, stats + (long)g * 3 * P + (long)r * a.CW + j, P);
+    if (threadIdx.x == 0) part[((long)g * a.CH + r) * gridDim.y + seg] = sh[0][0][0];
+}
+
+// Backward: upcos_bwd_rows_kernel with the two factors read per pixel from the stats instead of per channel; one workgroup per
+// (plane = group * Cg + channel, window row), gathered along x into tmp [G*C, CH, w]; upcos_gather_rows_kernel finishes along y.
+__global__ __launch_bounds__(128) void uppixcos_bwd_rows_kernel(UpCosArgs a, int Cg, double eps, const double* __restrict__ stats,
+                                                                const float* __restrict__ g_loss, nefes_bicubic::GatherTable gx,
+                                                                float* __restrict__ tmp) {
+    using namespace nefes_bicubic;
+    extern __shared__ float lds[];
+    float* rows = lds;                 // [4][w] the four source rows of this up-sampled row
+    float* gs = lds + 4 * a.w;         // [CW]
+    const int c = blockIdx.x / a.CH, r = blockIdx.x % a.CH, oy = r + a.o0;
+    const Taps ty = taps_of(a.sy, oy);
+    const float* src = a.x + (long)c * a.h * a.w;
+    for (int i = threadIdx.x; i < 4 * a.w; i += 128) rows[i] = src[(long)clampi(ty.base - 1 + i / a.w, a.h) * a.w + i % a.w];
+    __syncthreads();
+    const long P = (long)a.CH * a.CW;
+    const double k = -(double)g_loss[0] / (double)P;
+    const double* st = stats + (long)(c / Cg) * 3 * P + (long)r * a.CW;
+    const float* pb = a.target + ((long)c * a.CH + r) * a.CW;
+    for (int j = threadIdx.x; j < a.CW; j += 128) {
+        const Taps tx = taps_of(a.sx, j + a.o0);
+        int xs[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) xs[m] = clampi(tx.base - 1 + m, a.w);
+        float rv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float* rr = rows + i * a.w;
+            rv[i] = rr[xs[0]] * tx.w[0] + rr[xs[1]] * tx.w[1] + rr[xs[2]] * tx.w[2] + rr[xs[3]] * tx.w[3];
+        }
+        const double av = rv[0] * ty.w[0] + rv[1] * ty.w[1] + rv[2] * ty.w[2] + rv[3] * ty.w[3];
+        const PixK f = pix_factors(k, st[j], st[P + j], st[2 * P + j], eps);
+        gs[j] = (float)(f.k1 * (double)pb[j] - f.k2 * av);
+    }
+    __syncthreads();
+    float* out = tmp + ((long)c * a.CH + r) * a.w;
+    for (int xi = threadIdx.x; xi < a.w; xi += 128) out[xi] = gather_axis_table(gx, xi, gs, 1);
+}
+
 
 // ---- the same loss for a FIXED target, through the Gram matrices of the up-sampling (round 5) ---------------------------------
 // Per channel the up-sampled, cropped image is  up = Uy X Ux^T  (Uy [CH, h], Ux [CW, w]: the bicubic taps of the window's rows and
@@ -875,6 +1077,75 @@ extern "C" int nefes_upcos_loss_bwd(int C, int h, int w, int OH, int OW, int cro
     hipLaunchKernelGGL(upcos_bwd_rows_kernel, dim3((unsigned)((long)C * CH)), dim3(128), lds, (hipStream_t)stream, a, 1e-6, scratch, g_loss, gx, tmp);
     const long n = (long)C * h * w;                    // g_x[c][y][x] = sum over the window's rows oy of Wy(oy -> y) tmp[c][oy - o0][x]
     hipLaunchKernelGGL(upcos_gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long)C, h, CH, (long)w, gy,
+                       (const float*)tmp, g_x);
+    return (int)hipGetLastError();
+}
+
+// scratch of the per-pixel loss (doubles): mean [G] | stats [G][3][P] | one partial per forward workgroup
+extern "C" size_t nefes_pixcos_scratch_doubles(int G, int64_t P) {
+    return G > 0 && P > 0 ? (size_t)G * (1 + 3 * (size_t)P + (size_t)((P + kPixCols - 1) / kPixCols)) : 0;
+}
+extern "C" size_t nefes_uppixcos_scratch_doubles(int G, int OH, int OW, int crop) {
+    const int CH = OH - 2 * crop, CW = OW - 2 * crop;
+    return G > 0 && crop >= 0 && CH > 0 && CW > 0 ? (size_t)G * (1 + 3 * (size_t)CH * CW + (size_t)CH * ((CW + kPixCols - 1) / kPixCols)) : 0;
+}
+
+extern "C" int nefes_pixcos_loss_fwd(int G, int C, int64_t P, const float* a, const float* b, double* scratch, float* loss, void* stream) {
+    if (G <= 0 || G > 65535 || C <= 0 || P <= 0 || !a || !b || !scratch || !loss) return NEFES_E_BADARG;
+    const int64_t nb = (P + kPixCols - 1) / kPixCols;
+    if (nb > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    double* stats = scratch + G;
+    double* part = stats + (size_t)G * 3 * P;
+    hipLaunchKernelGGL(pixcos_fwd_kernel, dim3((unsigned)nb, (unsigned)G), dim3(kPixBlock), 0, (hipStream_t)stream, C, (long)P, 1e-6, a, b, stats, part);
+    hipLaunchKernelGGL(pixcos_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, G, (int)nb, (double)P, (const double*)part, scratch, loss);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nefes_pixcos_loss_bwd(int G, int C, int64_t P, const float* a, const float* b, const double* scratch, const float* g_loss,
+                                     float* g_a, void* stream) {
+    if (G <= 0 || G > 65535 || C <= 0 || P <= 0 || !a || !b || !scratch || !g_loss || !g_a) return NEFES_E_BADARG;
+    const long n = (long)G * C * P;
+    if ((n + 255) / 256 > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    hipLaunchKernelGGL(pixcos_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, C, (long)P, 1e-6, a, b,
+                       scratch + G, g_loss, g_a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nefes_uppixcos_loss_fwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                       double* scratch, float* loss, void* stream) {
+    const int CH = OH - 2 * crop, CW = OW - 2 * crop;
+    if (G <= 0 || G > 65535 || C <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !loss) return NEFES_E_BADARG;
+    if ((long)G * C > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    UpCosArgs a{G * C, h, w, OH, OW, crop, CH, CW, (float)h / OH, (float)w / OW, x, target};
+    double* stats = scratch + G;
+    double* part = stats + (size_t)G * 3 * CH * CW;
+    const int nseg = (CW + kPixCols - 1) / kPixCols;
+    if (nseg > 65535 || (long)CH * nseg > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    hipLaunchKernelGGL(uppixcos_fwd_kernel, dim3((unsigned)CH, (unsigned)nseg, (unsigned)G), dim3(kPixBlock), 0, (hipStream_t)stream, a, C, 1e-6, stats,
+                       part);
+    hipLaunchKernelGGL(pixcos_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, G, CH * nseg, (double)CH * CW, (const double*)part, scratch,
+                       loss);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nefes_uppixcos_loss_bwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                       const double* scratch, const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt,
+                                       const int* ty_first, const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream) {
+    const int CH = OH - 2 * crop, CW = OW - 2 * crop;
+    if (G <= 0 || G > 65535 || C <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !g_loss || !tmp || !g_x)
+        return NEFES_E_BADARG;
+    if (!tx_first || !tx_count || !tx_wt || !ty_first || !ty_count || !ty_wt || T <= 0) return NEFES_E_BADARG;
+    const long planes = (long)G * C, n = planes * h * w;
+    if (planes * CH > 0x7fffffffl || (n + 255) / 256 > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    const nefes_bicubic::GatherTable gx{tx_first, tx_count, tx_wt, T}, gy{ty_first, ty_count, ty_wt, T};
+    UpCosArgs a{(int)planes, h, w, OH, OW, crop, CH, CW, (float)h / OH, (float)w / OW, x, target};
+    const size_t lds = (size_t)(4 * w + CW) * 4;
+    if (lds > 96 * 1024) return NEFES_E_UNSUPPORTED;
+    hipError_t e = hipFuncSetAttribute((const void*)uppixcos_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(uppixcos_bwd_rows_kernel, dim3((unsigned)(planes * CH)), dim3(128), lds, (hipStream_t)stream, a, C, 1e-6, scratch + G, g_loss,
+                       gx, tmp);
+    hipLaunchKernelGGL(upcos_gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, planes, h, CH, (long)w, gy,
                        (const float*)tmp, g_x);
     return (int)hipGetLastError();
 }

@@ -1716,6 +1716,107 @@ def upsampled_cosine_loss(x, target, size, crop=0, return_cos=False, out=None):
     return (loss, cos) if return_cos else loss
 
 
+class PixelCosineLoss(torch.autograd.Function):
+    """feature_loss (dm/DFM_pose_refine.py:211-233) with per_pixel=True on [G*C, ...] maps: per group 1 - mean over pixels of the cosine
+    similarity over the C channels, summed over the G groups; two launches forward, one backward (to `a` only)."""
+
+    @staticmethod
+    def forward(ctx, a, b, groups, out=None):
+        G = int(groups)
+        if G < 1 or a.shape[0] % G:
+            raise ValueError(f"nefes_amd: {a.shape[0]} leading channels do not split into {groups} groups")
+        Cc = a.shape[0] // G
+        af, bf = _f32(a).reshape(G, Cc, -1), _f32(b).reshape(G, Cc, -1)
+        if af.shape != bf.shape:
+            raise ValueError(f"nefes_amd: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
+        lib = L.load()
+        P = af.shape[2]
+        scratch = torch.empty(lib.nefes_pixcos_scratch_doubles(G, P), dtype=torch.float64, device=af.device)
+        loss = _loss_buffer(out, af.device)
+        with _timed("pixcos_loss_fwd"):
+            L.check(lib.nefes_pixcos_loss_fwd(G, Cc, P, _chk(af, "a"), _chk(bf, "b"), _chk(scratch, "scratch", torch.float64),
+                                              _chk(loss, "loss"), _stream()), "nefes_pixcos_loss_fwd")
+        ctx.save_for_backward(af, bf, scratch)
+        ctx.shape = a.shape
+        cos = scratch[:G]                                 # float64 mean cosine similarity per group (a view of the scratch)
+        ctx.set_materialize_grads(False)                  # no zero-filled gradient for `cos` in the backward
+        ctx.mark_non_differentiable(cos)
+        return loss, cos
+
+    @staticmethod
+    def backward(ctx, g, _g_cos):
+        if g is None:
+            return (None,) * 4
+        af, bf, scratch = ctx.saved_tensors
+        gf = _f32(g).reshape(1)
+        g_a = torch.empty_like(af)
+        with _timed("pixcos_loss_bwd"):
+            L.check(L.load().nefes_pixcos_loss_bwd(af.shape[0], af.shape[1], af.shape[2], _chk(af, "a"), _chk(bf, "b"),
+                                                   _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), _chk(g_a, "g_a"), _stream()),
+                    "nefes_pixcos_loss_bwd")
+        return g_a.reshape(ctx.shape), None, None, None
+
+
+def pixel_cosine_loss(a, b, groups=1, return_cos=False, out=None):
+    """The per-pixel feature loss (`--per_pixel`): a, b [groups * C, ...]; per group 1 - mean over pixels of the cosine similarity over
+    its C channels (torch.nn.CosineSimilarity(dim=0, eps=1e-6)), summed over the groups -- every group's value and gradient are what a
+    call on that group alone gives.  `return_cos` adds the per-group mean cosines (float64, no gradient); `out` as in
+    cosine_feature_loss."""
+    loss, cos = PixelCosineLoss.apply(a, b, groups, out)
+    return (loss, cos) if return_cos else loss
+
+
+class UpsampledPixelCosineLoss(torch.autograd.Function):
+    """pixel_cosine_loss(bicubic_upsample(x, size, crop), target, groups) for x [groups * C, h, w] (or [1, ., h, w]) without the
+    up-sampled image: csrc/refine.hip uppixcos kernels.  There is no prepared-target form of this loss (the normalisation is per pixel)."""
+
+    @staticmethod
+    def forward(ctx, x, target, OH, OW, crop, groups, out=None):
+        xf = _f32(x)
+        GC, h, w = xf.shape[-3:]
+        G = int(groups)
+        if G < 1 or GC % G or xf.numel() != GC * h * w:
+            raise ValueError(f"nefes_amd: features {tuple(x.shape)} do not split into {groups} groups of [C,h,w] maps")
+        xf = xf.reshape(GC, h, w)
+        tf = _f32(target).reshape(GC, OH - 2 * crop, OW - 2 * crop)
+        lib = L.load()
+        scratch = torch.empty(lib.nefes_uppixcos_scratch_doubles(G, OH, OW, crop), dtype=torch.float64, device=xf.device)
+        loss = _loss_buffer(out, xf.device)
+        with _timed("uppixcos_loss_fwd"):
+            L.check(lib.nefes_uppixcos_loss_fwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
+                                                _chk(scratch, "scratch", torch.float64), _chk(loss, "loss"), _stream()), "nefes_uppixcos_loss_fwd")
+        ctx.save_for_backward(xf, tf, scratch)
+        ctx.cfg = (x.shape, OH, OW, crop, G)
+        cos = scratch[:G]
+        ctx.set_materialize_grads(False)                  # no zero-filled gradient for `cos` in the backward
+        ctx.mark_non_differentiable(cos)
+        return loss, cos
+
+    @staticmethod
+    def backward(ctx, g, _g_cos):
+        if g is None:
+            return (None,) * 7
+        xf, tf, scratch = ctx.saved_tensors
+        shape, OH, OW, crop, G = ctx.cfg
+        GC, h, w = xf.shape
+        gf = _f32(g).reshape(1)
+        tmp = torch.empty(GC, OH - 2 * crop, w, device=xf.device)
+        g_x = torch.empty_like(xf)
+        (fx, cx, wx, T), (fy, cy, wy, _) = bicubic_gather_tables(h, w, OH, OW, crop, xf.device)
+        with _timed("uppixcos_loss_bwd"):
+            L.check(L.load().nefes_uppixcos_loss_bwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
+                                                     _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), fx.data_ptr(), cx.data_ptr(),
+                                                     wx.data_ptr(), fy.data_ptr(), cy.data_ptr(), wy.data_ptr(), T, _chk(tmp, "tmp"),
+                                                     _chk(g_x, "g_x"), _stream()), "nefes_uppixcos_loss_bwd")
+        return g_x.reshape(shape), None, None, None, None, None, None
+
+
+def upsampled_pixel_cosine_loss(x, target, size, crop=0, groups=1, return_cos=False, out=None):
+    """pixel_cosine_loss of the bicubically up-sampled, cropped x against target, one pass each way.  `out` as in cosine_feature_loss."""
+    loss, cos = UpsampledPixelCosineLoss.apply(x, target, int(size[0]), int(size[1]), int(crop), int(groups), out)
+    return (loss, cos) if return_cos else loss
+
+
 _GRAMS = {}
 
 

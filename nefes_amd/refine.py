@@ -140,12 +140,12 @@ class PoseRefiner:
         # only and Adam is element-wise, so each image walks the trajectory it would walk alone; what is shared is the launch
         # overhead and the GPU (an 80x60 frame is 19 sample tiles per CU).  The reference refines one image at a time.
         self.B = int(images)
-        if self.B > 1 and (not fused_glue or lietorch or per_pixel):
+        if self.B > 1 and (not fused_glue or lietorch):
             raise NotImplementedError("nefes_amd: batched refinement runs on the fused glue kernels (fused_glue=True, "
-                                      "lietorch=False, per_pixel=False)")
+                                      "lietorch=False)")
         self.apr = None
         if pose_model is not None:
-            if self.B > 1 or per_pixel:
+            if self.B > 1:
                 raise NotImplementedError("nefes_amd: the regression-network variant refines one image at a time")
             import copy
             self.upsample = upsample = True
@@ -244,6 +244,19 @@ class PoseRefiner:
             if B > 1:
                 return mean_loss * float(B), (1.0 - cos.view(B, self.C).mean(1)).float()
             return mean_loss, mean_loss.detach()
+        if self.fused_glue and self.per_pixel:
+            # the per-pixel loss (`--per_pixel`) on its own kernels; up-sampled, again without the up-sampled image.  No prepared-target
+            # form: the normalisation is per pixel (csrc/refine.hip), so self.target is read on every iteration
+            if self.upsample and self.FUSED_UPSAMPLED_LOSS:
+                loss, cos = ops.upsampled_pixel_cosine_loss(fused.reshape(B * self.C, self.h, self.w),
+                                                            self.target.reshape(B * self.C, self.H - 20, self.W - 20), (self.H, self.W), crop=10,
+                                                            groups=B, return_cos=True, out=out)
+            else:
+                if self.upsample:
+                    fused = ops.bicubic_upsample(fused, (self.H, self.W), crop=10)
+                loss, cos = ops.pixel_cosine_loss(fused.reshape(B * self.C, -1), self.target.reshape(B * self.C, -1), groups=B, return_cos=True,
+                                                  out=out)
+            return loss, ((1.0 - cos).float() if B > 1 else loss.detach())
         if self.upsample:
             if self.fused_glue:
                 fused = ops.bicubic_upsample(fused, (self.H, self.W), crop=10)
@@ -255,7 +268,7 @@ class PoseRefiner:
             return mean_loss * float(B), (1.0 - cos.view(B, self.C).mean(1)).float()
         # (a view where possible: fused[0] costs a 34 MB zero fill and a copy in the backward)
         fused = fused.view(fused.shape[1:]) if fused.is_contiguous() else fused[0]
-        if self.fused_glue and not self.per_pixel:
+        if self.fused_glue:
             loss = ops.cosine_feature_loss(fused, self.target, out=out)
         else:
             loss = feature_loss(fused, self.target, per_pixel=self.per_pixel)

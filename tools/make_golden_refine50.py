@@ -91,6 +91,11 @@ def main():
     ap.add_argument("--hw", type=float, nargs=3, default=[120, 160, 150.0], metavar=("H", "W", "FOCAL"),
                     help="full-resolution image; the loop renders (H/4) x (W/4) rays.  240 320 300 = the 60 x 80 rays of the reference's own "
                          "loop (DFM_APR_refine.py:107, seven_scenes_colmap.py:264-276): `--hw 240 320 300 --k 1 --out tests/golden/refine50_60x80.npz`")
+    ap.add_argument("--per-pixel", action="store_true",
+                    help="args.per_pixel = True (dm/options.py:73): FeatureLoss(per_pixel=True) in mode 2, and the float64 oracle's "
+                         "feature_loss wrapped to per_pixel=True.  `--per-pixel --modes 2 --k 2 --out tests/golden/refine50_pp.npz`")
+    ap.add_argument("--modes", type=int, nargs="+", default=[3, 2], choices=[2, 3],
+                    help="`--modes 2` skips mode 3, whose loop hard-codes per_pixel=False (DFM_pose_refine.py:338)")
     a = ap.parse_args()
     globals().update(K=a.k, ITERS=a.iters)
     torch.set_num_threads(a.threads)
@@ -122,7 +127,7 @@ def main():
     embeddirs_fn, _, _ = M.get_embedder(4, 0, -1)
     args = types.SimpleNamespace(nerfh_nff=True, use_fine_only=False, NeRFW=True, transient_at_test=True, netchunk=1 << 21,
                                  encode_hist=True, tinyscale=ts, chunk=1 << 15, lr_r=0.0087, lr_t=0.01,   # dm/options.py:137-138 (7-Scenes)
-                                 PoseEstimatorType='PoseNet', svd_reg=True, batch_size=1, learning_rate=1e-3, per_pixel=False)
+                                 PoseEstimatorType='PoseNet', svd_reg=True, batch_size=1, learning_rate=1e-3, per_pixel=a.per_pixel)
     q = lambda inputs, viewdirs, ts_, network_fn, typ, output_transient, test_time, store_rgb: \
         M.run_network_NeRFH_NFF(inputs, viewdirs, ts_, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, typ=typ,
                                 output_transient=output_transient, netchunk=args.netchunk, test_time=test_time,
@@ -183,7 +188,7 @@ def main():
     data = photo.clone()
     m3 = {k_: [] for k_ in ("loss", "grad", "r", "t", "pose", "err")}
     t0 = time.time()
-    for k in range(K):
+    for k in range(K if 3 in a.modes else 0):
         net = DR.LearnPose(1, True, True, inits[k][None].clone(), lietorch=False)
         opt = torch.optim.Adam([{'params': net.r, 'lr': args.lr_r}, {'params': net.t, 'lr': args.lr_t}])   # DFM_post_processing2 :392-398
         rec.update(loss=[], grad=[])
@@ -202,7 +207,8 @@ def main():
         print(f"mode 3 start {k}: init err {out['init_err'][k]}  ->  {m3['err'][-1]}   loss {rec['loss'][0]:.5f} -> {rec['loss'][-1]:.6f}  ({time.time() - t0:.0f} s)", flush=True)
     DR.feature_loss = ref_loss
     for k_, v in m3.items():
-        out["m3_" + k_] = np.stack(v)
+        if 3 in a.modes:
+            out["m3_" + k_] = np.stack(v)
 
     # ---- mode 2: train_on_batch, K starts x 50 iterations ------------------------------------------------------------------
     desc = RC.image_descriptor(photo)
@@ -210,7 +216,7 @@ def main():
     m2 = {k_: [] for k_ in ("weight", "bias", "loss", "grad", "psnr", "ssim", "pose", "final", "retreat", "err", "w_traj", "b_traj")}
     gt_pose = true_c2w[:3, :4].reshape(1, 12)
     loss_mod = DR.FeatureLoss(per_pixel=args.per_pixel)
-    for k in range(K):
+    for k in range(K if 2 in a.modes else 0):
         weight = 0.05 * torch.randn(12, 12, generator=wgen)
         # the network's first prediction: the k-th perturbed pose with a rotation block that is NOT orthonormal, as a regression
         # network's raw output is (R S with S symmetric positive definite: svd_reg recovers R; with an exact rotation the three
@@ -248,12 +254,14 @@ def main():
         print(f"mode 2 start {k}: init err {out['init_err'][k]}  ->  {m2['err'][-1]}  retreat {retreat}  psnr {ps[0]:.2f} -> {ps[-1]:.2f}  "
               f"loss {rec['loss'][0]:.5f} -> {rec['loss'][-1]:.6f}  ({time.time() - t0:.0f} s)", flush=True)
     for k_, v in m2.items():
+        if 2 not in a.modes:
+            break
         if k_ in ("w_traj", "b_traj"):
             v = v[:2]                                                  # the parameter trajectories of two starts (teacher forcing)
         out["m2_" + k_] = np.stack(v)
     out["m2_lr"] = args.learning_rate
     out["lr"] = np.array([args.lr_r, args.lr_t])
-    for tag in ("m3", "m2"):
+    for tag in ["m%d" % m for m in (3, 2) if m in a.modes]:
         e = out[tag + "_err"]
         print(f"{tag}: median error {np.median(e[:, 0]):.5f} m, {np.median(e[:, 1]):.4f} deg   (initial {np.median(out['init_err'][:, 0]):.4f} m, "
               f"{np.median(out['init_err'][:, 1]):.3f} deg)")
@@ -262,7 +270,10 @@ def main():
 
     if a.skip_f64:
         return
-    add_f64(a.out, a.iters)
+    if a.per_pixel:                                                    # Problem.loss_at_pose looks the name up at call time
+        plain = RC.feature_loss
+        RC.feature_loss = lambda x, y, per_pixel=False: plain(x, y, per_pixel=True)
+    add_f64(a.out, a.iters, a.modes)
 
 
 def problem(g, dtype, k, mode):
@@ -289,7 +300,7 @@ def problem(g, dtype, k, mode):
                       upsample=(int(H), int(W)) if mode == 2 else None)
 
 
-def add_f64(path, iters=ITERS):
+def add_f64(path, iters=ITERS, modes=(3, 2)):
     """The float64 oracle's run from the same starts: `m3_*_f64`, `m2_*_f64` (ORACLE output, the tests' truth)."""
     ITERS = iters
     g = dict(np.load(path))
@@ -297,21 +308,23 @@ def add_f64(path, iters=ITERS):
     photo = torch.from_numpy(g["photo_u8"]).float()[None] / 255.
     t0 = time.time()
     p3, r3, t3, p2 = [], [], [], []
-    for k in range(K_):
+    for k in range(K_ if 3 in modes else 0):
         b = RC.refine(problem(g, torch.float64, k, 3), float(g["lr"][0]), float(g["lr"][1]), ITERS)
         p3.append(b["poses"][-1].numpy())
         r3.append(b["r"].numpy())
         t3.append(b["t"].numpy())
         print(f"f64 mode 3 start {k}: |ref - f64| final pose {np.abs(p3[-1] - g['m3_pose'][k]).max():.2e}  ({time.time() - t0:.0f} s)", flush=True)
-    g.update(m3_pose_f64=np.stack(p3), m3_r_f64=np.stack(r3), m3_t_f64=np.stack(t3))
-    np.savez_compressed(path, **g)
-    for k in range(K_):
+    if 3 in modes:
+        g.update(m3_pose_f64=np.stack(p3), m3_r_f64=np.stack(r3), m3_t_f64=np.stack(t3))
+        np.savez_compressed(path, **g)
+    for k in range(K_ if 2 in modes else 0):
         b = RC.refine_apr(problem(g, torch.float64, k, 2), torch.from_numpy(g["m2_weight"][k]), torch.from_numpy(g["m2_bias"][k]), photo,
                           float(g["m2_lr"]), ITERS)
         p2.append(b["final"].numpy())
         print(f"f64 mode 2 start {k}: |ref - f64| final pose {np.abs(p2[-1] - g['m2_final'][k]).max():.2e}  retreat {bool(b['retreat'])}  ({time.time() - t0:.0f} s)", flush=True)
-    g.update(m2_final_f64=np.stack(p2))
-    np.savez_compressed(path, **g)
+    if 2 in modes:
+        g.update(m2_final_f64=np.stack(p2))
+        np.savez_compressed(path, **g)
     print("wrote the float64 oracle runs into", path)
 
 
