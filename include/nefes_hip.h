@@ -122,6 +122,18 @@ int nefes_raygen_fwd(int H, int W, float focal, const float* c2w, int row0, int 
 size_t nefes_raygen_bwd_workspace(int n_rays);
 int nefes_raygen_bwd(int H, int W, float focal, const float* c2w, int row0, int nrows, const float* g_rays_o,
                      const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w, void* stream);
+/* The same for a pinhole camera with intrinsics: dirs = [(col - cx)/fx, -(row - cy)/fy, -1].
+ * intr: dev, 4 floats (fx, fy, cx, cy), READ FROM DEVICE MEMORY when the kernel runs -- not a launch argument, so that a captured graph
+ * follows a camera updated in place between replays and the backward can return its gradient.  The values cannot be checked here
+ * (fx = 0 behaves as focal = 0 does above).  With intr = (focal, focal, (float)(W*.5), (float)(H*.5)) the outputs -- rays and the twelve
+ * pose-gradient numbers -- equal nefes_raygen_fwd / _bwd's bit for bit.
+ * backward: g_c2w[12] and, unless NULL, g_intr[4] = d L / d (fx, fy, cx, cy) (dev) = sums over rays.  g_rays_o / g_rays_d / g_viewdirs may
+ * be NULL (treated as zero).  workspace: dev, >= nefes_raygen_k_bwd_workspace(nrows*W) bytes. */
+int nefes_raygen_k_fwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, float* rays_o, float* rays_d,
+                       float* viewdirs, void* stream);
+size_t nefes_raygen_k_bwd_workspace(int n_rays);
+int nefes_raygen_k_bwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, const float* g_rays_o,
+                       const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr, void* stream);
 /* ndc_rays (:27-44) and its backward to (rays_o, rays_d). */
 int nefes_ndc_fwd(int H, int W, float focal, float near, int n, const float* rays_o, const float* rays_d, float* out_o,
                   float* out_d, void* stream);

@@ -115,6 +115,131 @@ extern "C" int nefes_raygen_bwd(int H, int W, float focal, const float* c2w, int
     return (int)hipGetLastError();
 }
 
+// ---- pinhole intrinsics (fx, fy, cx, cy) ---------------------------------------------------------
+// The camera is READ FROM DEVICE MEMORY when the kernel runs (intr[4] = fx, fy, cx, cy), never passed by value: a captured
+// iteration follows a camera that is updated in place between replays, and the backward can hand a gradient to it.  With
+// intr = (focal, focal, (float)(W*.5), (float)(H*.5)) every operation below is the one the focal kernels above perform, in the
+// same order, so rays and the twelve pose sums are theirs bit for bit.
+__device__ __forceinline__ void pixel_dir_k(const float* __restrict__ intr, int row, int col, float (&dc)[3]) {
+    // dirs = [(i - cx)/fx, -(j - cy)/fy, -1]
+    dc[0] = __fdiv_rn(__fsub_rn((float)col, intr[2]), intr[0]);
+    dc[1] = -__fdiv_rn(__fsub_rn((float)row, intr[3]), intr[1]);
+    dc[2] = -1.f;
+}
+
+__global__ __launch_bounds__(256) void raygen_k_fwd_kernel(int W, const float* __restrict__ intr, const float* __restrict__ c2w,
+                                                           int row0, int n, float* rays_o, float* rays_d, float* viewdirs) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n) return;
+    const int row = row0 + idx / W, col = idx % W;
+    float dc[3];
+    pixel_dir_k(intr, row, col, dc);
+    float d[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float p0 = __fmul_rn(dc[0], c2w[a * 4 + 0]), p1 = __fmul_rn(dc[1], c2w[a * 4 + 1]),
+                    p2 = __fmul_rn(dc[2], c2w[a * 4 + 2]);
+        d[a] = __fadd_rn(__fadd_rn(p0, p1), p2);
+    }
+    const float nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        rays_o[(size_t)idx * 3 + a] = c2w[a * 4 + 3];
+        rays_d[(size_t)idx * 3 + a] = d[a];
+        if (viewdirs) viewdirs[(size_t)idx * 3 + a] = __fdiv_rn(d[a], nrm);
+    }
+}
+
+// stage 1: per-block partial of 16 sums (f64) -- the 12 pose-gradient sums of raygen_bwd_kernel, formed exactly as there, then
+// d L/d (fx, fy, cx, cy); stage 2: fixed-order final sum.  With gd the gradient reaching rays_d and R_a column a of the rotation:
+//     d dirs_0 / d fx = -(col - cx)/fx^2 = -dirs_0/fx     d dirs_0 / d cx = -1/fx
+//     d dirs_1 / d fy = +(row - cy)/fy^2 = -dirs_1/fy     d dirs_1 / d cy = +1/fy
+__global__ __launch_bounds__(256) void raygen_k_bwd_kernel(int W, const float* __restrict__ intr, const float* __restrict__ c2w,
+                                                           int row0, int n, const float* g_o, const float* g_d, const float* g_v,
+                                                           double* partial) {
+    __shared__ double red[4][16];
+    double s[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s[k] = 0.0;
+    const float fx = intr[0], fy = intr[1];
+    const float ifx = __fdiv_rn(1.f, fx), ify = __fdiv_rn(1.f, fy);
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
+        const int row = row0 + idx / W, col = idx % W;
+        float dc[3];
+        pixel_dir_k(intr, row, col, dc);
+        float gd[3] = {0.f, 0.f, 0.f};
+        if (g_d)
+#pragma unroll
+            for (int a = 0; a < 3; ++a) gd[a] = g_d[(size_t)idx * 3 + a];
+        if (g_v) {   // v = d/|d|  =>  d L/d d += (g - v (v.g)) / |d|
+            float d[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+                d[a] = __fadd_rn(__fadd_rn(__fmul_rn(dc[0], c2w[a * 4]), __fmul_rn(dc[1], c2w[a * 4 + 1])), __fmul_rn(dc[2], c2w[a * 4 + 2]));
+            const float nrm = __fsqrt_rn(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+            const float gv0 = g_v[(size_t)idx * 3], gv1 = g_v[(size_t)idx * 3 + 1], gv2 = g_v[(size_t)idx * 3 + 2];
+            const float v0 = d[0] / nrm, v1 = d[1] / nrm, v2 = d[2] / nrm;
+            const float dot = v0 * gv0 + v1 * gv1 + v2 * gv2;
+            gd[0] += (gv0 - v0 * dot) / nrm;
+            gd[1] += (gv1 - v1 * dot) / nrm;
+            gd[2] += (gv2 - v2 * dot) / nrm;
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int b = 0; b < 3; ++b) s[a * 4 + b] += (double)gd[a] * (double)dc[b];
+            if (g_o) s[a * 4 + 3] += (double)g_o[(size_t)idx * 3 + a];
+        }
+        // gd . R_0 and gd . R_1 in fp32, the camera's factor in fp32, the product and the sum in f64
+        const float r0 = __fadd_rn(__fadd_rn(__fmul_rn(gd[0], c2w[0]), __fmul_rn(gd[1], c2w[4])), __fmul_rn(gd[2], c2w[8]));
+        const float r1 = __fadd_rn(__fadd_rn(__fmul_rn(gd[0], c2w[1]), __fmul_rn(gd[1], c2w[5])), __fmul_rn(gd[2], c2w[9]));
+        s[12] += (double)(-__fmul_rn(dc[0], ifx)) * (double)r0;   // fx
+        s[13] += (double)(-__fmul_rn(dc[1], ify)) * (double)r1;   // fy
+        s[14] += (double)(-ifx) * (double)r0;                     // cx
+        s[15] += (double)ify * (double)r1;                        // cy
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const double v = wave_sum(s[k]);
+        if (lane == 0) red[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) partial[(size_t)blockIdx.x * 16 + threadIdx.x] =
+        ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+__global__ void raygen_k_bwd_final(const double* partial, int nblocks, float* g_c2w, float* g_intr) {
+    const int k = threadIdx.x;
+    if (k >= 16) return;
+    double s = 0.0;
+    for (int b = 0; b < nblocks; ++b) s += partial[(size_t)b * 16 + k];
+    if (k < 12) g_c2w[k] = (float)s;
+    else if (g_intr) g_intr[k - 12] = (float)s;
+}
+
+extern "C" int nefes_raygen_k_fwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, float* rays_o,
+                                  float* rays_d, float* viewdirs, void* stream) {
+    if (!intr || !c2w || !rays_o || !rays_d || H <= 0 || W <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > H)
+        return NEFES_E_BADARG;
+    const int n = nrows * W;
+    hipLaunchKernelGGL(raygen_k_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, W, intr, c2w, row0, n,
+                       rays_o, rays_d, viewdirs);
+    return (int)hipGetLastError();
+}
+extern "C" size_t nefes_raygen_k_bwd_workspace(int n_rays) { return (size_t)raygen_blocks(n_rays) * 16 * sizeof(double); }
+extern "C" int nefes_raygen_k_bwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, const float* g_rays_o,
+                                  const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr,
+                                  void* stream) {
+    if (!intr || !c2w || !workspace || !g_c2w || H <= 0 || W <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > H)
+        return NEFES_E_BADARG;
+    const int n = nrows * W, nb = raygen_blocks(n);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(raygen_k_bwd_kernel, dim3(nb), dim3(256), 0, st, W, intr, c2w, row0, n, g_rays_o, g_rays_d, g_viewdirs,
+                       (double*)workspace);
+    hipLaunchKernelGGL(raygen_k_bwd_final, dim3(1), dim3(64), 0, st, (const double*)workspace, nb, g_c2w, g_intr);
+    return (int)hipGetLastError();
+}
+
 // ---- ndc_rays (ray_utils.py:27-44) ------------------------------------------------------------
 struct Ndc {
     float t, ox, oy, oz, kx, ky;

@@ -1,6 +1,7 @@
 """Ray-batch data parallelism for the render-and-refine path: one process per GPU, rays sharded by
-image rows, weights replicated (2.7 MB), and exactly one collective per backward: an all-reduce (SUM)
-of the 3x4 pose gradient (48 bytes) over RCCL/xGMI.  The reference has no distributed code at all
+image rows, weights replicated (2.7 MB), and one collective per differentiable camera input per backward: an
+all-reduce (SUM) of the 3x4 pose gradient (48 bytes) over RCCL/xGMI and, only when `render_sharded(intrinsics=K)` is given a
+K that requires a gradient, a second one of d loss / d (fx, fy, cx, cy) (16 bytes).  The reference has no distributed code at all
 (`--multi_gpu` is nn.DataParallel, nerfh_nff.py:647-648); this is new functionality.
 
 No data-path collective exists in the forward pass: every rank generates its own rays from the
@@ -61,18 +62,26 @@ def replicate_pose(c2w: torch.Tensor, group=None) -> torch.Tensor:
     return _PoseGradAllReduce.apply(c2w, group)
 
 
-def render_sharded(render_fn, H, W, focal, c2w, rank=None, world=None, group=None, **kw):
-    """render() restricted to this rank's rows, with the pose-gradient all-reduce attached."""
+def render_sharded(render_fn, H, W, focal, c2w, rank=None, world=None, group=None, intrinsics=None, **kw):
+    """render() restricted to this rank's rows, with the pose-gradient all-reduce attached.  `intrinsics` (render()'s keyword: the
+    camera (fx, fy, cx, cy), read from device memory by the ray kernels) is passed through; a tensor that requires a gradient is wrapped
+    in the same all-reduce, so every rank ends up with the full d loss / d K."""
     if rank is None:
         rank = dist.get_rank(group) if dist.is_initialized() else 0
     if world is None:
         world = dist.get_world_size(group) if dist.is_initialized() else 1
     row0, nrows = row_shard(H, rank, world)
     pose = replicate_pose(c2w, group)
+    if intrinsics is not None:
+        if torch.is_tensor(intrinsics) and intrinsics.requires_grad:
+            intrinsics = replicate_pose(intrinsics, group)          # the second collective: 4 floats
+        kw["intrinsics"] = intrinsics
     if nrows == 0:
         # more ranks than image rows: this rank renders nothing, but its (zero) loss must still reach the pose so that its
         # backward takes part in the all-reduce
         z = (pose.sum() * 0.).reshape(1, 1)
+        if torch.is_tensor(intrinsics) and intrinsics.requires_grad:
+            z = z + (intrinsics.sum() * 0.).reshape(1, 1)
         C = getattr(kw.get("network_fn", None), "W_features", 0)
         return [z.expand(0, 3), z.expand(0, 1)[:, 0], z.expand(0, 1)[:, 0], {"feat_map": z.expand(0, C)}]
     return render_fn(H, W, focal, c2w=pose, row_range=(row0, nrows), **kw)

@@ -119,6 +119,98 @@ class RayGen(torch.autograd.Function):
         return out, None, None, None, None, None
 
 
+def as_intrinsics(x, device):
+    """A pinhole camera (fx, fy, cx, cy) as the float32 [4] tensor on `device` that the raygen_k kernels READ FROM DEVICE MEMORY when they
+    run (so that a captured graph follows in-place updates of it and a gradient can reach it).  Three forms:
+      - a float32 [4] tensor already on `device`: used as is -- no copy, no sync, no check of its values (they are on the device);
+      - a 4-sequence of numbers (fx, fy, cx, cy);
+      - a 3 x 3 matrix K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]].
+    Host-side values are validated: finite, fx and fy positive, no skew, last row 0 0 1 (ValueError names the offending value)."""
+    dev = torch.device(device)
+    if torch.is_tensor(x):
+        here = x.device.type == dev.type and (dev.index is None or x.device.index == dev.index)
+        if here and x.dtype == torch.float32 and tuple(x.shape) == (4,) and x.is_contiguous():
+            return x
+        if x.device.type != "cpu":          # (reading it back to validate or convert it would be a host sync)
+            raise ValueError(f"nefes_amd: intrinsics on a device must be a contiguous float32 [4] tensor (fx, fy, cx, cy) on {dev}; got "
+                             f"{x.dtype} {tuple(x.shape)} on {x.device}")
+    import numpy as np
+    a = np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x, dtype=np.float64)
+    if a.shape == (3, 3):
+        for (i, j), want in (((0, 1), 0.), ((1, 0), 0.), ((2, 0), 0.), ((2, 1), 0.), ((2, 2), 1.)):
+            if not a[i, j] == want:
+                what = "skew is not supported" if (i, j) == (0, 1) else f"expected {want:g}"
+                raise ValueError(f"nefes_amd: intrinsics K[{i}][{j}] = {float(a[i, j])!r}: {what} (K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]])")
+        a = np.array([a[0, 0], a[1, 1], a[0, 2], a[1, 2]])
+    if a.shape != (4,):
+        raise ValueError(f"nefes_amd: intrinsics must be (fx, fy, cx, cy) or a 3 x 3 K; got shape {a.shape}")
+    for name, v in zip(("fx", "fy", "cx", "cy"), a):
+        if not np.isfinite(v):
+            raise ValueError(f"nefes_amd: intrinsics {name} = {float(v)!r} is not finite")
+    for name, v in zip(("fx", "fy"), a[:2]):
+        if not v > 0:
+            raise ValueError(f"nefes_amd: intrinsics {name} = {float(v)!r} must be positive")
+    return torch.tensor(a, dtype=torch.float32, device=dev)
+
+
+def _intr(intr):
+    if tuple(intr.shape) != (4,):
+        raise RuntimeError(f"nefes_amd: `intr` must be [4] (fx, fy, cx, cy); got {tuple(intr.shape)}")
+    return _chk(intr.detach(), "intr")
+
+
+def raygen_k_fwd(H, W, intr, c2w, row0=0, nrows=None):
+    """raygen_fwd for the camera intr = (fx, fy, cx, cy), a float32 [4] DEVICE tensor the kernel reads when it runs."""
+    nrows = H - row0 if nrows is None else nrows
+    c2w = _f32(c2w[:3, :4])
+    n = nrows * W
+    o = torch.empty(n, 3, device=c2w.device)
+    d = torch.empty_like(o)
+    v = torch.empty_like(o)
+    L.check(L.load().nefes_raygen_k_fwd(H, W, _intr(intr), _chk(c2w, "c2w"), row0, nrows, _chk(o, "o"), _chk(d, "d"),
+                                        _chk(v, "v"), _stream()), "nefes_raygen_k_fwd")
+    return o, d, v
+
+
+def raygen_k_bwd(H, W, intr, c2w, row0, nrows, g_o, g_d, g_v, want_intr=True):
+    """-> (g_c2w [3,4], g_intr [4] or None)."""
+    lib = L.load()
+    c2w = _f32(c2w[:3, :4])
+    n = nrows * W
+    ws = torch.empty(lib.nefes_raygen_k_bwd_workspace(n), dtype=torch.uint8, device=c2w.device)
+    g = torch.empty(3, 4, device=c2w.device)
+    gk = torch.empty(4, device=c2w.device) if want_intr else None
+    fix = lambda t: None if t is None else _f32(t)
+    g_o, g_d, g_v = fix(g_o), fix(g_d), fix(g_v)
+    L.check(lib.nefes_raygen_k_bwd(H, W, _intr(intr), _chk(c2w, "c2w"), row0, nrows, _chk(g_o, "g_o"), _chk(g_d, "g_d"),
+                                   _chk(g_v, "g_v"), _chk(ws, "ws", torch.uint8), _chk(g, "g_c2w"), _chk(gk, "g_intr"), _stream()),
+            "nefes_raygen_k_bwd")
+    return g, gk
+
+
+class RayGenK(torch.autograd.Function):
+    """RayGen for a pinhole camera with intrinsics: apply(c2w, intr, H, W, row0, nrows) -> (o, d, v), backward to the pose and -- when
+    `intr` asks for it -- to (fx, fy, cx, cy).  `intr` is read from device memory by the kernels (as_intrinsics)."""
+
+    @staticmethod
+    def forward(ctx, c2w, intr, H, W, row0, nrows):
+        o, d, v = raygen_k_fwd(H, W, intr, c2w, row0, nrows)
+        ctx.save_for_backward(c2w, intr)
+        ctx.geom = (H, W, row0, nrows)
+        return o, d, v
+
+    @staticmethod
+    def backward(ctx, g_o, g_d, g_v):
+        c2w, intr = ctx.saved_tensors
+        H, W, row0, nrows = ctx.geom
+        g, gk = raygen_k_bwd(H, W, intr, c2w, row0, nrows, g_o, g_d, g_v, want_intr=ctx.needs_input_grad[1])
+        if not (tuple(c2w.shape) == (3, 4) and c2w.dtype == torch.float32):
+            out = torch.zeros_like(c2w)
+            out[:3, :4] = g
+            g = out
+        return g, gk, None, None, None, None
+
+
 class NdcRays(torch.autograd.Function):
     """ndc_rays (ray_utils.py:27-44)."""
 

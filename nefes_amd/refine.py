@@ -120,7 +120,8 @@ class PoseRefiner:
 
     def __init__(self, render_kwargs, args, hwf, near, far, tinyscale=4, lr_r=0.01, lr_t=0.1, lietorch=False,
                  upsample=False, per_pixel=False, world_setup=None, graph=True, device="cuda", adam_capturable=None,
-                 fused_glue=True, images=1, pose_model=None, svd_reg=False, learning_rate=1e-5, bn_running_stats=True):
+                 fused_glue=True, images=1, pose_model=None, svd_reg=False, learning_rate=1e-5, bn_running_stats=True,
+                 intrinsics=None, learn_focal=False, lr_f=1e-3):
         self.kw, self.args = dict(render_kwargs), args
         # False: FusionNet's train-mode BatchNorm leaves its running statistics and batch counter alone in this refiner's iterations
         # (nothing in the loop reads them; the reference never puts the net in eval mode).  REQUIRED for refiners that share a
@@ -155,13 +156,32 @@ class PoseRefiner:
             self.apr_opt = self._apr_adam(learning_rate)
             self._rgb = self._x_rgb = None
         self.model = LearnPose(self.B, True, True, init_c2w=torch.eye(4)[None].repeat(self.B, 1, 1), lietorch=lietorch).to(self.dev)
+        # intrinsics: the camera (fx, fy, cx, cy) of the RENDERED (h, w) image (resized_intrinsics maps a full-resolution K there), one
+        # for all images or [B, 4]; None = (focal / ts, centred), on the focal kernels.  It lives in ONE persistent float32 device tensor,
+        # self.intrinsics, which the ray kernels read from memory when they run: a captured iteration follows in-place updates of it.
+        self.intrinsics, self.log_f = None, None
+        if learn_focal:
+            if pose_model is not None or self.B > 1:
+                raise NotImplementedError("nefes_amd: learn_focal is built for LearnPose mode with one image (no pose_model=, images=1)")
+            if not self.fused_glue or lietorch:
+                raise NotImplementedError("nefes_amd: learn_focal is optimised by ops.FusedAdam (fused_glue=True, lietorch=False)")
+            if intrinsics is None:
+                intrinsics = (self.focal, self.focal, float(self.w * .5), float(self.h * .5))
+        if intrinsics is not None:
+            if not self.fused_glue:
+                raise NotImplementedError("nefes_amd: PoseRefiner(intrinsics=...) runs on the fused glue kernels (fused_glue=True)")
+            self.intrinsics = _camera_buffer(intrinsics, self.B, self.dev)
+        if learn_focal:
+            # NeRF--'s LearnFocal next to LearnPose: one scalar, the rendered camera is (fx e^log_f, fy e^log_f, cx, cy)
+            self.log_f = nn.Parameter(torch.zeros(1, device=self.dev))
+            self._f_mask = torch.tensor([1., 1., 0., 0.], device=self.dev)
         # fused_glue: the pose chain, the crop and the feature loss as library kernels (ops.pose_compose, the windowed
         # ops.bicubic_upsample, ops.cosine_feature_loss) and one fused Adam launch -- ~80 launches per iteration instead of ~215.
         # False keeps the torch expressions (the tests compare the two).
         # fused glue: Adam over (r, t) with (lr_r, lr_t) as ONE launch (ops.FusedAdam: the two parameters and their gradients are
         # views of flat buffers, the pose kernel's backward writes the gradients there); otherwise torch.optim.Adam, two groups
         if self.fused_glue and not lietorch:
-            self.opt = ops.FusedAdam([(self.model.r, lr_r), (self.model.t, lr_t)])
+            self.opt = ops.FusedAdam([(self.model.r, lr_r), (self.model.t, lr_t)] + ([(self.log_f, lr_f)] if learn_focal else []))
         else:
             self.opt = torch.optim.Adam([{"params": [self.model.r], "lr": lr_r}, {"params": [self.model.t], "lr": lr_t}],
                                         capturable=bool(graph) if adam_capturable is None else bool(adam_capturable),
@@ -174,13 +194,24 @@ class PoseRefiner:
         self.graph, self.apr_graph = None, None
 
     # one iteration on the static buffers -------------------------------------------------------------------------
-    def _loss(self):
-        """DFM_optimization_NFF (:310-337): pose -> render -> affine colour transform -> fusion CNN -> feature loss.
-        Returns (scalar to differentiate, per-image losses [B] or the same scalar).  One image on the fused glue: the library's loss
-        kernel writes its value straight into the static buffer self.loss (`out=`: no 4-byte copy launch per iteration); everything
-        else (images=B, the torch expressions) returns its own tensor and the callers copy it."""
+    def _camera(self):
+        """{} (the focal kernels), or render()'s `intrinsics=` keyword: self.intrinsics itself, or with learn_focal its first two
+        entries times e^log_f (three element-wise torch launches; exp(0) = 1 and x * 1 = x, so the principal point passes exactly)."""
+        if self.intrinsics is None:
+            return {}
+        if self.log_f is None:
+            return {"intrinsics": self.intrinsics}
+        return {"intrinsics": self.intrinsics * torch.exp(self.log_f * self._f_mask)}
+
+    def features(self):
+        """The fused features [B, C, h, w] the loss compares with the target, at the refiner's current state (pose, camera, log_f):
+        what a caller renders a synthetic target with."""
+        with torch.no_grad():
+            return self._fused().detach().clone()
+
+    def _fused(self):
+        """pose -> render -> affine colour transform -> fusion CNN: the fused features [B, C, h, w] of the current state."""
         B = self.B
-        out = self.loss if (B == 1 and self.fused_glue) else None
         track = self.bn_running_stats                      # this refiner's calls only: the shared FusionNet's own setting is not touched
         if self.apr is not None:                           # train_on_batch :91-97
             c2w = self.apr(self.photo).reshape(1, 3, 4)
@@ -208,10 +239,11 @@ class PoseRefiner:
             kw = dict(kw, feat_as_gmap=True)               # honoured only where render() takes the factored head (extras["feat_is_gmap"])
         if B == 1:
             # (a view, not c2w[0]: indexing costs a zero fill and a copy in the backward)
-            rgb, _, _, ex = render(self.h, self.w, self.focal, c2w=c2w.reshape(3, 4), near=self.near, far=self.far, img_idx=self.hist, **kw)
+            rgb, _, _, ex = render(self.h, self.w, self.focal, c2w=c2w.reshape(3, 4), near=self.near, far=self.far, img_idx=self.hist, **kw,
+                                   **self._camera())
             feat = ex["feat_map"]
         else:
-            rgb, _, _, ex = render_poses(self.h, self.w, self.focal, c2w, near=self.near, far=self.far, **kw)
+            rgb, _, _, ex = render_poses(self.h, self.w, self.focal, c2w, near=self.near, far=self.far, **kw, **self._camera())
             rgb, feat = rgb.reshape(-1, 3), ex["feat_map"].reshape(-1, ex["feat_map"].shape[-1])
         gmap = bool(ex.get("feat_is_gmap", False))
         if fused_input:
@@ -233,6 +265,16 @@ class PoseRefiner:
             if self.apr is not None:
                 self._rgb, self._x_rgb = rgb.detach(), None
             _, _, fused = self.coarse.run_fusion_net(rgb, feat, self.h, self.w, B, per_image_norm=B > 1, track_stats=track)
+        return fused
+
+    def _loss(self):
+        """DFM_optimization_NFF (:310-337): pose -> render -> affine colour transform -> fusion CNN -> feature loss.
+        Returns (scalar to differentiate, per-image losses [B] or the same scalar).  One image on the fused glue: the library's loss
+        kernel writes its value straight into the static buffer self.loss (`out=`: no 4-byte copy launch per iteration); everything
+        else (images=B, the torch expressions) returns its own tensor and the callers copy it."""
+        B = self.B
+        out = self.loss if (B == 1 and self.fused_glue) else None
+        fused = self._fused()
         if self.upsample and self.fused_glue and not self.per_pixel and self.FUSED_UPSAMPLED_LOSS:
             # up-sampling, crop and feature loss in one pass each way: the 34 MB up-sampled image is never written (ops.upsampled_cosine_loss)
             if self._uses_prepared_target():
@@ -316,8 +358,8 @@ class PoseRefiner:
         """Loss at the current (r, t) and its gradient, written into the parameters' static .grad buffers (no optimizer step).
         The gradients are copied over the previous ones: nothing has to be zeroed between iterations."""
         loss, per_image = self._loss()
-        gr, gt = torch.autograd.grad(loss, [self.model.r, self.model.t], grad_outputs=self._one_like(loss))
-        for p, g in ((self.model.r, gr), (self.model.t, gt)):
+        params = [self.model.r, self.model.t] + ([] if self.log_f is None else [self.log_f])
+        for p, g in zip(params, torch.autograd.grad(loss, params, grad_outputs=self._one_like(loss))):
             if p.grad is None:
                 p.grad = torch.empty_like(p)
             if g.data_ptr() != p.grad.data_ptr():          # (the fused pose kernel writes the parameters' .grad itself)
@@ -346,6 +388,8 @@ class PoseRefiner:
         with torch.no_grad():
             self.model.r.zero_()
             self.model.t.zero_()
+            if self.log_f is not None:
+                self.log_f.zero_()
             self.model.init_c2w.copy_(init_c2w.reshape(self.B, 4, 4))
             self.target.copy_(feature_target.reshape(self.target.shape))
             if self._uses_prepared_target():
@@ -372,7 +416,9 @@ class PoseRefiner:
         if not apr:
             return _Mode(False, on_device=lambda job: tuple(t.to(self.dev) for t in job), set_state=self._reset, iteration=self._iteration,
                          prepare=lambda m, job: first_use(m) and self._run(m, job, iters=0), read=self._refined_pose,
-                         read_own=self._refined_pose, finish=lambda pose, _, __, losses: (pose, losses))
+                         read_own=self._refined_pose,
+                         finish=lambda pose, _, __, losses: ((pose, losses) if self.log_f is None
+                                                             else (pose, losses, self.log_f.detach().clone())))
         if self.apr is None:
             raise RuntimeError("nefes_amd: PoseRefiner was built without pose_model=")
 
@@ -440,8 +486,8 @@ class PoseRefiner:
         return m.finish(m.read(), before, checks, losses)
 
     def refine(self, init_c2w, feature_target, hist, iters=50):
-        """One image (images=1): (refined 4x4 c2w, losses [iters]).  A batch (images=B): init_c2w [B,4,4], feature_target
-        [B,C,h,w], hist [B,10] -> (refined poses [B,4,4], losses [iters,B]), each image as if refined alone."""
+        """One image (images=1): (refined 4x4 c2w, losses [iters]) -- with learn_focal (refined c2w, losses, log_f [1]).
+        A batch (images=B): init_c2w [B,4,4], feature_target [B,C,h,w], hist [B,10] -> (refined poses [B,4,4], losses [iters,B]), each image as if refined alone."""
         return self._run(self._mode(), (init_c2w, feature_target, hist), iters)
 
     refine_batch = refine
@@ -541,6 +587,37 @@ class PoseRefiner:
         info = dict(psnr=(first, last), ssim=(first, last), retreat=bool)).  PoseRefiner(graph=True): the iteration is captured on
         first use and replayed (the regression network must be capturable: no host reads, static shapes)."""
         return self._run(self._mode(apr=True, verification=verification), (photo, feature_target, hist), iters)
+
+
+def _camera_buffer(intrinsics, B, device):
+    """PoseRefiner's persistent camera: float32 [4] on the device, or [B, 4] for a table of one camera per image.  A device tensor of
+    that form is kept as it is (the caller's in-place updates reach the captured iteration); host values are validated
+    (ops.as_intrinsics)."""
+    if not torch.is_tensor(intrinsics):
+        import numpy as np
+        intrinsics = torch.from_numpy(np.asarray(intrinsics, dtype=np.float64))
+    if intrinsics.dim() == 2 and tuple(intrinsics.shape) != (3, 3):
+        if tuple(intrinsics.shape) != (B, 4):
+            raise ValueError(f"nefes_amd: PoseRefiner(intrinsics=...) takes one camera or [{B}, 4], one per image; got {tuple(intrinsics.shape)}")
+        if intrinsics.device.type != "cpu":
+            if intrinsics.dtype != torch.float32 or not intrinsics.is_contiguous():
+                raise ValueError("nefes_amd: a table of intrinsics on the device must be contiguous float32")
+            return intrinsics.detach()
+        return torch.stack([ops.as_intrinsics(r, device) for r in intrinsics.unbind(0)])
+    return ops.as_intrinsics(intrinsics, device).detach()
+
+
+def resized_intrinsics(K, from_hw, to_hw):
+    """The camera (fx, fy, cx, cy) of an image resized from (H, W) to (h, w) under the align_corners=False convention of F.interpolate
+    and of the loop's bicubic up-sampling -- pixel x of the small image looks where (x + 0.5) W / w - 0.5 of the large one does:
+        fx' = fx w / W,  cx' = (cx + 0.5) w / W - 0.5,  and fy', cy' likewise with h / H.
+    K: (fx, fy, cx, cy) or a 3 x 3 matrix, host values.  Returns a tuple of four floats (float64 arithmetic)."""
+    import numpy as np
+    a = np.asarray(K.detach().cpu().numpy() if torch.is_tensor(K) else K, dtype=np.float64)
+    fx, fy, cx, cy = (a[0, 0], a[1, 1], a[0, 2], a[1, 2]) if a.shape == (3, 3) else a
+    (H, W), (h, w) = from_hw, to_hw
+    sx, sy = float(w) / float(W), float(h) / float(H)
+    return (float(fx * sx), float(fy * sy), float((cx + 0.5) * sx - 0.5), float((cy + 0.5) * sy - 0.5))
 
 
 _nothing = lambda *args: None

@@ -289,12 +289,29 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     return _cat_parts([render_rays(rays_flat[i:i + step], **kwargs) for i in range(0, rays_flat.shape[0], step)])
 
 
-def _rays_for(H, W, focal, c2w, c2w_staticcam, row_range):
+def _rays_for(H, W, focal, c2w, c2w_staticcam, row_range, intr=None):
     row0, nrows = (0, H) if row_range is None else row_range
+    if intr is not None:                                            # a camera with intrinsics (ops.as_intrinsics): `focal` is not read
+        rays_o, rays_d, viewdirs = ops.RayGenK.apply(c2w.to(_DEV), intr, H, W, row0, nrows)
+        if c2w_staticcam is not None:
+            rays_o, rays_d, _ = ops.RayGenK.apply(c2w_staticcam.to(_DEV), intr, H, W, row0, nrows)
+        return rays_o, rays_d, viewdirs
     rays_o, rays_d, viewdirs = ops.RayGen.apply(c2w.to(_DEV), H, W, float(focal), row0, nrows)
     if c2w_staticcam is not None:                                   # rays of the static camera, view directions of c2w (:211-216)
         rays_o, rays_d, _ = ops.RayGen.apply(c2w_staticcam.to(_DEV), H, W, float(focal), row0, nrows)
     return rays_o, rays_d, viewdirs
+
+
+def _refuse_intrinsics(intrinsics, ndc, rays_only=False):
+    """What `intrinsics=` cannot be combined with, said before anything touches the device."""
+    if intrinsics is None:
+        return
+    if rays_only:
+        raise ValueError("nefes_amd: render(intrinsics=...) with rays=: the rays are the caller's, there is no camera to apply the "
+                         "intrinsics to (pass c2w=, or build the rays with ops.raygen_k_fwd)")
+    if ndc:
+        raise NotImplementedError("nefes_amd: render(intrinsics=..., ndc=True): the NDC warp (ray_utils.py:27-44) assumes a centred "
+                                  "principal point and one focal length; pass ndc=False (no shipped NeFeS config uses NDC)")
 
 
 def _render_batch(rays_o, rays_d, viewdirs, near, far, chunk, kwargs, cfg):
@@ -320,14 +337,21 @@ def _render_batch(rays_o, rays_d, viewdirs, near, far, chunk, kwargs, cfg):
 
 
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
-           c2w_staticcam=None, img_idx=torch.Tensor(0), row_range=None, **kwargs):
-    """Reference signature (rendering.py:197-200) + `row_range=(row0, nrows)` for ray-batch sharding.
-    Returns [rgb_map [N,3], disp_map [N], acc_map [N], extras dict]."""
+           c2w_staticcam=None, img_idx=torch.Tensor(0), row_range=None, intrinsics=None, **kwargs):
+    """Reference signature (rendering.py:197-200) + `row_range=(row0, nrows)` for ray-batch sharding + `intrinsics=`.
+    Returns [rgb_map [N,3], disp_map [N], acc_map [N], extras dict].
+
+    `intrinsics` (fx, fy, cx, cy) of the rendered H x W image -- a float32 [4] device tensor, a 4-sequence or a 3 x 3 K
+    (ops.as_intrinsics) -- replaces `focal` and the centred principal point for the rays of `c2w` and of `c2w_staticcam`.  The kernels
+    read it from device memory when they run: a device tensor is used as is, so in-place updates reach a captured graph and a tensor
+    that requires a gradient gets one."""
     if not use_viewdirs:
         raise NotImplementedError("nefes_amd: the NeFeS field always uses view directions (use_viewdirs=True)")
     cfg = _cfg(kwargs)
+    _refuse_intrinsics(intrinsics, ndc, rays_only=c2w is None)
     if c2w is not None:
-        rays_o, rays_d, viewdirs = _rays_for(int(H), int(W), focal, c2w, c2w_staticcam, row_range)
+        intr = None if intrinsics is None else ops.as_intrinsics(intrinsics, _DEV)
+        rays_o, rays_d, viewdirs = _rays_for(int(H), int(W), focal, c2w, c2w_staticcam, row_range, intr)
     else:
         rays_o, rays_d = rays
         rays_o, rays_d = rays_o.to(_DEV).reshape(-1, 3).float(), rays_d.to(_DEV).reshape(-1, 3).float()
@@ -341,19 +365,37 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     return [all_ret[k] for k in k_extract] + [{k: v for k, v in all_ret.items() if k not in k_extract}]
 
 
-def render_poses(H, W, focal, poses, chunk=1024 * 32, ndc=True, near=0., far=1., use_viewdirs=False, **kwargs):
+def _cameras(intrinsics, B):
+    """B cameras for render_poses: None each, the one camera B times, or the rows of a [B, 4] table."""
+    if intrinsics is None:
+        return [None] * B
+    if not torch.is_tensor(intrinsics):
+        import numpy as np
+        intrinsics = torch.from_numpy(np.asarray(intrinsics, dtype=np.float64))
+    shape = tuple(intrinsics.shape)
+    if len(shape) == 2 and shape != (3, 3):         # (a row of a contiguous [B, 4] device tensor is a view: used as is)
+        if shape != (B, 4):
+            raise ValueError(f"nefes_amd: render_poses(intrinsics=...) takes one camera or [{B}, 4], one per pose; got {shape}")
+        return [ops.as_intrinsics(r, _DEV) for r in intrinsics.unbind(0)]
+    return [ops.as_intrinsics(intrinsics, _DEV)] * B
+
+
+def render_poses(H, W, focal, poses, chunk=1024 * 32, ndc=True, near=0., far=1., use_viewdirs=False, intrinsics=None, **kwargs):
     """Several camera poses in ONE launch sequence (the reference's render_path loops render() per
     pose, rendering.py:270-273): rays of all B poses are generated (one small kernel per pose) and concatenated, then
     every heavy kernel -- coarse field, compositing, sampling, fine field, compositing -- runs once over B*H*W rays.
     poses [B,3,4] (or [B,4,4]).  Returns [rgb [B,H*W,3], disp [B,H*W], acc [B,H*W], extras {k: [B,H*W,...]}];
-    differentiable w.r.t. `poses` like render()."""
+    differentiable w.r.t. `poses` like render().  `intrinsics`: one camera for all poses (as render() takes it) or [B, 4], one per
+    pose; read from device memory by the ray kernels, differentiable when it is a device tensor that requires a gradient."""
     if not use_viewdirs:
         raise NotImplementedError("nefes_amd: the NeFeS field always uses view directions (use_viewdirs=True)")
     cfg = _cfg(kwargs)
+    _refuse_intrinsics(intrinsics, ndc)
     H, W = int(H), int(W)
     B = poses.shape[0]
     p34 = poses if tuple(poses.shape[-2:]) == (3, 4) else poses[:, :3, :4]
-    parts = [_rays_for(H, W, focal, c, None, None) for c in p34.unbind(0)]      # unbind: one stack in the backward, no fills
+    cams = _cameras(intrinsics, B)
+    parts = [_rays_for(H, W, focal, c, None, None, k) for c, k in zip(p34.unbind(0), cams)]      # unbind: one stack in the backward, no fills
     rays_o, rays_d, viewdirs = (torch.cat([p[k] for p in parts], 0) for k in range(3))
     if ndc:
         rays_o, rays_d = ops.NdcRays.apply(rays_o, rays_d, H, W, float(focal), 1.)
