@@ -8,7 +8,7 @@
 // with no FMA contraction.  The CDF itself is built as torch's CPU path does: pdf = (w+1e-5)/sum,
 // running sum accumulated in f64 and rounded to f32 per element.
 #include "../../include/nefes_hip.h"
-#include "wave.h"
+#include "composite.h"
 
 #define SP_MAX_NC 256
 #define SP_MAX_S 512
@@ -165,15 +165,15 @@ __global__ __launch_bounds__(256) void sample_pdf_merge_kernel(int N, int Nc, in
 
 // =====================================================================================================================
 // The coarse pass behind its field kernel as ONE launch (round 4): compositing variant D (weights of the sigma-only coarse pass,
-// nerfh_nff.py:83-89 / composite.hip composite_fwd4_kernel) + sample_pdf + sort(cat[z_vals, z_samples]) per ray, for
-// Nc = 64 RW coarse samples (RW = 1, 2, 4).  A ray occupies 16 RW lanes with four consecutive coarse samples each, as in
-// composite.hip's four-samples-per-lane kernels -- 4 / RW rays per wave, 16 / RW per workgroup -- so the coarse weights never
+// nerfh_nff.py:83-89 / composite.hip composite_fwd_kernel) + sample_pdf + sort(cat[z_vals, z_samples]) per ray, for
+// Nc = 64 RW coarse samples (RW = 1, 2, 4).  A ray occupies 16 RW lanes with four consecutive coarse samples each: the layout
+// FourPerLane<RW> of composite.h -- 4 / RW rays per wave, 16 / RW per workgroup -- so the coarse weights never
 // travel to HBM and back (79 MB written by one launch and read by the next at the headline shape) and a 64-entry CDF no longer
 // leaves three quarters of a wave idle.  `z` is one row of Nc depths per ray (z_stride = Nc) or one row shared by every ray
 // (z_stride = 0: scalar near / far without jitter, rendering.py:96-100 -- the row is then never materialised per ray at all).
-// Same arithmetic, statement for statement, as composite_fwd4_kernel (transmittance: f64 running products in the same association)
-// and sample_pdf_merge_kernel (f64 sums are exact here, so their association does not matter): z_fine is bit-identical to the three
-// launches it replaces (tests/test_gpu_surface.py).
+// The weights come from the same two pieces as composite_fwd_kernel<FourPerLane<RW>>'s (composite.h: sample_alpha and the layout's
+// exclusive running product), the rest repeats sample_pdf_merge_kernel's arithmetic (f64 sums are exact here, so their association
+// does not matter): z_fine is bit-identical to the three launches it replaces (tests/test_gpu_surface.py).
 // =====================================================================================================================
 // LDS floats per ray (16-byte aligned rows): cb [2 Nc] = {cdf_k, bins_k} pairs; zp [Nc + 8] = the coarse depths behind four -inf and
 // in front of +inf sentinels; s2 [2 Ni] = {sample_i, count_i} pairs; sorted [S] (the counters of the inverse-CDF histogram live
@@ -187,13 +187,11 @@ __global__ __launch_bounds__(256) void coarse_sample_kernel(int N, int Ni, const
                                                             float* z_samples, float* weights_out) {
     constexpr int LPR = Seg<RW>::LPR, RPW = Seg<RW>::RPW, Nc = 64 * RW, nb = Nc - 1, np_ = Nc - 2;
     extern __shared__ __attribute__((aligned(16))) float smem_cs[];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int sub = lane / LPR, sl = lane - sub * LPR;
+    const FourPerLane<RW> lay(N, Nc);                             // idle lanes shadow the last ray (loads in bounds, nothing stored)
+    const int lane = lay.lane, wv = threadIdx.x >> 6, sub = lay.seg, sl = lay.sl, ray = lay.ray;
+    const bool live = lay.live;
     const int S = Nc + Ni, S4 = (S + 3) / 4 * 4;
     const int slot = wv * RPW + sub;                              // ray slot inside the workgroup
-    const int ray_raw = (blockIdx.x * 4 + wv) * RPW + sub;
-    const bool live = ray_raw < N;
-    const int ray = live ? ray_raw : N - 1;                       // idle lanes shadow the last ray (loads in bounds, nothing stored)
     float* cb = smem_cs + (size_t)slot * coarse_sample_lds_floats(Nc, Ni);
     float* zp = cb + 2 * Nc;                                      // z_k at zp[4 + k]
     float* s2 = zp + Nc + 8;
@@ -213,31 +211,19 @@ __global__ __launch_bounds__(256) void coarse_sample_kernel(int N, int Ni, const
     }
     const uint64_t seg_mask = LPR == 64 ? ~0ull : (((1ull << LPR) - 1ull) << (sub * LPR));
 
-    // ---- compositing, variant D: weights w_k = alpha_k * prod_{j<k} (1 - alpha_j)  (composite.hip ray_forward4, sigma_only) ----
+    // ---- compositing, variant D: weights w_k = alpha_k * prod_{j<k} (1 - alpha_j), on the pieces of composite.hip's kernels ----
     const int s0 = 4 * sl;
-    const float4 z4 = ld4(z + (size_t)ray * z_stride + s0);
-    const float4 ss4 = ld4(sigma + (size_t)ray * Nc + s0);
-    const float z_next = RW == 1 ? row_next(z4.x) : __shfl_down(z4.x, 1);     // (unused by a ray's last lane)
-    float a_c[4], w[4], zz[4];
-    double om[4];
+    float zz[4], z1[4], ss[4], w[4];
+    lay.load_z(z + (size_t)ray * z_stride, zz, z1);
+    lay.load_row(sigma, (size_t)ray * Nc, ss);
+    const float z_next = z1[3];                                               // (unused by a ray's last lane)
+    Ray<4> r;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float z0 = el(z4, k);
-        const float z1 = k < 3 ? el(z4, k + 1) : z_next;
-        zz[k] = z0;
-        const float dl = (s0 + k == Nc - 1) ? 1e2f : (z1 - z0);
-        const float e_c = expf(-(dl * (el(ss4, k) + 0.f)));
-        a_c[k] = 1.f - e_c;
-        om[k] = (double)(1.f - a_c[k]);
-    }
-    {
-        const double p0 = om[0], p1 = p0 * om[1], p2 = p1 * om[2], p3 = p2 * om[3];
-        const double inc = RW == 1 ? row_incl_prod(p3) : seg_incl_prod<RW>(p3, sl);
-        const double prev = RW == 1 ? row_prev(inc, 1.0) : __shfl_up(inc, 1);
-        const double E = sl == 0 ? 1.0 : prev;
-        w[0] = a_c[0] * (float)E; w[1] = a_c[1] * (float)(E * p0); w[2] = a_c[2] * (float)(E * p1); w[3] = a_c[3] * (float)(E * p2);
-    }
-    if (weights_out && live) *(float4*)(weights_out + (size_t)ray * Nc + s0) = make_float4(w[0], w[1], w[2], w[3]);
+    for (int k = 0; k < 4; ++k) sample_alpha(false, true, s0 + k == Nc - 1, zz[k], z1[k], ss[k], 0.f, r, k);
+    lay.excl_prod([&](int k) { return (double)(1.f - r.a_c[k]); }, r.T);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = r.a_c[k] * r.T[k];
+    if (weights_out && live) lay.store_row(weights_out, (size_t)ray * Nc, w);
 
     // ---- bins = z_mid, cdf = [0, cumsum((w[1:-1] + 1e-5) / sum)]  (rendering.py:26-29,132-134; sample_pdf_merge_kernel) ----
     double part = 0.0;
@@ -265,7 +251,7 @@ __global__ __launch_bounds__(256) void coarse_sample_kernel(int N, int Ni, const
     }
     *(float4*)(cb + 2 * s0) = make_float4(cd[0], bn[0], cd[1], bn[1]);
     *(float4*)(cb + 2 * s0 + 4) = make_float4(cd[2], bn[2], cd[3], bn[3]);
-    *(float4*)(zp + 4 + s0) = z4;
+    *(float4*)(zp + 4 + s0) = make_float4(zz[0], zz[1], zz[2], zz[3]);
     if (sl == 0) *(float4*)zp = make_float4(-inf, -inf, -inf, -inf);
     if (sl == LPR - 1) *(float4*)(zp + 4 + Nc) = make_float4(inf, inf, inf, inf);
     __builtin_amdgcn_wave_barrier();

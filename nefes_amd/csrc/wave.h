@@ -83,8 +83,8 @@ __device__ __forceinline__ void wave_rev_affine(double& m, double& a, int lane) 
 }
 __device__ __forceinline__ double lane_bcast(double v, int src) { return __shfl(v, src); }
 
-// ---- rays that occupy RW rows of 16 lanes, four consecutive samples per lane (composite.hip's four-samples-per-lane kernels and
-// ---- the fused coarse-pass sampler of sample_pdf.hip): 4 / RW rays share a wave -----------------------------------------------
+// ---- rays that occupy RW rows of 16 lanes, four consecutive samples per lane (FourPerLane<RW> of composite.h: the compositing
+// ---- kernels and the fused coarse-pass sampler of sample_pdf.hip): 4 / RW rays share a wave ------------------------------------
 template <int RW> struct Seg {
     static constexpr int LPR = 16 * RW;              // lanes per ray
     static constexpr int RPW = 4 / RW;               // rays per wave (RW = 3: one ray, the fourth row idles)
@@ -128,8 +128,6 @@ __device__ __forceinline__ void seg_rev_affine(double& m, double& a, int sl) {
         }
     }
 }
-__device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ float el(const float4& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w)); }
 // inclusive prefix sum over the lanes of a ray (sl = lane index inside the ray)
 template <int RW>
 __device__ __forceinline__ double seg_incl_sum(double v, int sl) {
@@ -142,7 +140,8 @@ __device__ __forceinline__ double seg_incl_sum(double v, int sl) {
 }
 
 // ---- the same scans for a ray that occupies exactly ONE row of 16 lanes (RW = 1), on DPP row shifts: register to register, no
-// ---- ds_bpermute round trips (the fused coarse-pass sampler is bound by LDS instructions).  Same Hillis-Steele tree, same results.
+// ---- ds_bpermute round trips (the fused coarse-pass sampler is bound by LDS instructions).  Same Hillis-Steele tree, same results:
+// ---- FourPerLane<1> scans its transmittance on these, in the compositing kernels and in the sampler alike.
 template <int CTRL>
 __device__ __forceinline__ double dpp_shr_keep(double v, double keep) {      // lane i <- lane i - k of its row; `keep` where there is none
     int lo = __double2loint(v), hi = __double2hiint(v);

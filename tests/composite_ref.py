@@ -285,7 +285,7 @@ ALONE_S = (130, 192)
 SPLIT_C = (64, 65, 97, 128, 131)
 SPLIT_S = (64, 192, 100)
 MISALIGNED = tuple((tag, S) for S in (64, 128) for tag in ("A", "D"))
-DEEP_S = (300, 380, 440, 500)       # composite_fwd/bwd_kernel<5>, <6>, <7>, <8>: five to eight passes
+DEEP_S = (300, 380, 440, 500)       # composite_fwd/bwd_kernel<OnePerLane<5>>, <6>, <7>, <8>: five to eight passes
 DEEP_ALONE_S = (320, 500)
 DEEP_VARIANTS = ("A", "B", "C")
 

@@ -1,9 +1,9 @@
-"""The compositing kernels (csrc/composite.hip: composite_fwd/bwd_kernel<1..8>, composite_fwd4/bwd4_kernel<1..4>) against the float64
+"""The compositing kernels (csrc/composite.hip: composite_fwd/bwd_kernel<OnePerLane<1..8>> and <FourPerLane<1..4>>) against the float64
 oracle, PER RAY and PER GROUP (each map; of d raw the static colour rows, the feature rows, static sigma, the transient colour rows,
 transient sigma and the beta row), with the fp32 oracle's own error beside every number and tests/composite_ref.py's
 bound = max(4 E, 1.5 e_ref) as the limit.  Inputs, scales, constants and the case list live in tests/composite_ref.py, which
 tests/test_composite_ref.py checks on the CPU.  Sizes stay at N <= 37 and C <= 131; S <= 256 except for the five-to-eight-pass
-cases (S = 300 .. 500), which are what reaches composite_fwd/bwd_kernel<5..8>.
+cases (S = 300 .. 500), which are what reaches composite_fwd/bwd_kernel<OnePerLane<5..8>>.
 
 What each test is for: ragged S (one sample per lane, Q = 1..4, every variant, disp included), the same at Q = 5..8 for variants
 A, B and C, four samples per lane with disp and ray counts that leave segments, waves and blocks partly idle, every upstream
@@ -218,7 +218,7 @@ def test_no_write_past_n(ops, tag, S, N):
 
 
 # ---- the same inputs give the same bits ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("S", [130, 192])          # composite_fwd/bwd_kernel<3>; composite_fwd4/bwd4_kernel<3>
+@pytest.mark.parametrize("S", [130, 192])          # composite_fwd/bwd_kernel<OnePerLane<3>>; <FourPerLane<3>>
 def test_repeatable(ops, S):
     case = R.alone_case("A", S)
     bits = lambda t: t.contiguous().view(torch.int32)

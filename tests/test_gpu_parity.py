@@ -144,7 +144,7 @@ def test_composite_matches_reference(golden, ops, tag):
 @pytest.mark.parametrize("S", [64, 128, 192, 256])
 @pytest.mark.parametrize("tag", ["A", "B", "C", "D"])
 def test_composite_four_samples_per_lane_matches_oracle(ops, tag, S):
-    """S a multiple of 64 takes the four-samples-per-lane kernels (csrc/composite.hip: composite_fwd4 / bwd4; 4 / (S/64) rays
+    """S a multiple of 64 takes the four-samples-per-lane kernels (csrc/composite.hip: composite_fwd / bwd_kernel<FourPerLane<S/64>>; 4 / (S/64) rays
     share a wave): every map and d raw against the float64 oracle (raw2outputs_NeRFH_NFF restated, oracle/ref_cpu.py) with the
     fp32 oracle beside it (three-way rule), on rays that include saturated alphas, zero density, and a ray count that fills
     neither the last wave nor the last workgroup."""

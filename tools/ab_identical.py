@@ -18,7 +18,13 @@ on one library.  37 rays x 24 samples = seven tiles, the last ragged.
 prints, instead, the digests of what the refinement loop of nefes_amd/refine.py returns (pose, loss curve, the numbers of `info`) at
 REFINE_CASES, 6 iterations each, on the scene of tests/golden/refine50.npz (30 x 40 rays, 64 + 64 samples, 8 x 128 networks, C = 128):
 for A/B revisions of the HOST code on one library.  Only PoseRefiner's constructor, refine, refine_apr, refine_concurrently and
-refine_apr_concurrently are called."""
+refine_apr_concurrently are called.
+    NEFES_HIP_LIB=<lib> python tools/ab_identical.py --composite
+prints, instead, the digests of every output of nefes_composite_fwd and nefes_composite_bwd (csrc/composite.hip) at every run of
+tests/composite_ref.py's case list -- ragged, deep, four-per-lane, every upstream alone, the channel split, and the misaligned cases on
+each of their three pointer offsets: every forward map and the whole g_raw_t -- and of every output of ops.coarse_sample (csrc/sample_pdf.hip)
+at Nc = 64, 128, 256 on a shared depth row and on per-ray depths.  Output buffers carry eight rays of padding, are filled with a fixed
+pattern before the call and digested whole, byte for byte (NaN sign and payload bits included)."""
 import ctypes as C
 import hashlib, os, sys
 import torch
@@ -370,7 +376,52 @@ def run_refine():
     PoseRefiner.PREPARED_TARGET = default_prepared
 
 
+def run_composite():
+    from tests import composite_ref as R
+    PAD, FILL = 8, 0.123
+
+    def offset(t):                              # the tensor 4 bytes into a larger buffer: a pointer that is not 16-byte aligned
+        buf = torch.zeros(t.numel() + 8, device=dev)
+        buf[1:1 + t.numel()] = t.reshape(-1)
+        return buf[1:1 + t.numel()].view(t.shape)
+
+    runs = [(c, only, ()) for c, only in R.all_runs()]
+    runs += [(R.misaligned_case(tag, S), None, mis) for tag, S in R.MISALIGNED for mis in (("raw_t",), ("z",), ("raw_t", "z"))]
+    for case, only, mis in runs:
+        tag, n, s, c = case["tag"], case["N"], case["S"], case["C"]
+        flags, rows = R.FLAGS[tag] | (R.WHITE_BKGD if case["white"] else 0), R.n_rows(tag, c)
+        raw_t, zz = case["raw"].permute(0, 2, 1).contiguous().to(dev), case["z"].to(dev)
+        raw_t, zz = (offset(raw_t) if "raw_t" in mis else raw_t), (offset(zz) if "z" in mis else zz)
+        full = lambda *sh: torch.full((n + PAD, *sh), FILL, device=dev)
+        outs = {"acc": full(), "weights": full(s)}
+        if tag != "D":
+            outs.update(rgb=full(3), feat=full(c), disp=full(), depth=full(), beta=full())
+        ups = {k: v.contiguous().to(dev) for k, v in case["ups"].items() if k in R.maps_of(case) and only in (None, k)}
+        g_raw_t = full(rows, s)
+        o, u = (lambda k: P(outs.get(k))), (lambda k: P(ups.get(k)))
+        st = torch.cuda.current_stream().cuda_stream
+        L.check(lib.nefes_composite_fwd(n, s, c, flags, 0.1, P(raw_t), P(zz), o("rgb"), o("feat"), o("disp"), o("acc"), o("depth"), o("weights"),
+                                        o("beta"), st), "nefes_composite_fwd")
+        L.check(lib.nefes_composite_bwd(n, s, c, flags, P(raw_t), P(zz), u("rgb"), u("feat"), u("disp"), u("acc"), u("depth"), u("weights"),
+                                        u("beta"), P(g_raw_t), st), "nefes_composite_bwd")
+        name = f"{tag}{'w' if case['white'] else ''} S{s} N{n} C{c} seed {case['seed']}" + (f" only {only}" if only else "") + \
+               (" misaligned " + "+".join(mis) if mis else "")
+        out(name, **outs, g_raw_t=g_raw_t)
+    gs = torch.Generator(device='cpu').manual_seed(11)
+    n, ni = 37, 128
+    for nc in (64, 128, 256):
+        centre = torch.rand(n, 1, generator=gs) * nc
+        sig = (4.0 * torch.exp(-0.5 * ((torch.arange(nc)[None] - centre) / 3.0) ** 2)).contiguous().to(dev)
+        z_rays = torch.sort(torch.rand(n, nc, generator=gs) * 4, -1)[0].to(dev)
+        for what, zz in (("shared depth row", ops.coarse_depth_row(nc, 0., 4., False, dev)), ("per-ray depths", z_rays)):
+            z_fine, z_samples, weights = ops.coarse_sample(sig, zz, ni, want_samples=True, want_weights=True)
+            out(f"coarse_sample Nc{nc} Ni{ni} N{n} {what}", z_fine=z_fine, z_samples=z_samples, weights=weights)
+
+
 print("# lib", os.environ.get("NEFES_HIP_LIB") or "shipped", "ABI", L.ABI_VERSION)
+if "--composite" in sys.argv[1:]:
+    run_composite()
+    sys.exit(0)
 if "--refine" in sys.argv[1:]:
     run_refine()
     sys.exit(0)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Kernel time and HBM-side rate of the compositing and sampling kernels at the benchmark shapes (algorithmic bytes of SURVEY.md
-section 8d / DESIGN.md section 4.2-4.3).  NEFES_HIP_LIB selects a side build for A/B runs."""
+section 8d / DESIGN.md section 4.2-4.3), and at one shape of the one-sample-per-lane kernels.  NEFES_HIP_LIB selects a side build for
+A/B runs."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -22,8 +23,9 @@ def timed(fn, n=20):
     return s.elapsed_time(e) / n
 
 
+# (the last shape has more than 256 samples, as a user's 64 + 256: it reaches the one-sample-per-lane kernels, five passes)
 for name, N, S, C, Nc in (("G-metric 640x480, 64+128, C=16", 307200, 192, 16, 64), ("G-ref 80x60, 64+64, C=128", 4800, 128, 128, 64),
-                          ("G-ref x 8 images", 38400, 128, 128, 64)):
+                          ("G-ref x 8 images", 38400, 128, 128, 64), ("320x240, 64+256, C=16 (Q = 5)", 76800, 320, 16, 64)):
     R = 3 + C + 6
     g = torch.Generator(device=dev).manual_seed(1)
     raw_t = torch.randn(N, R, S, device=dev, generator=g) * 0.5
