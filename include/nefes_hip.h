@@ -580,6 +580,39 @@ int nefes_uppixcos_loss_fwd(int G, int C, int h, int w, int OH, int OW, int crop
 int nefes_uppixcos_loss_bwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const double* scratch,
                             const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt, const int* ty_first,
                             const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream);
+/* The four losses above with a VALIDITY MASK (the reference's masked_feature_loss, dm/DFM_pose_refine.py:257-288; `--semantic`: the
+ * loader's 0/1 mask of static pixels): mask dev uint8, one byte per pixel and group (image), shared by the group's Cg channels --
+ * [G,P], or [G, OH-2crop, OW-2crop] for the up-sampled forms; a pixel is valid iff its byte != 0 (rows need no alignment: bytes are
+ * read).  Channel-wise: the three sums of every channel run over the valid pixels only, loss = sum_g (1 - mean of the group's Cg
+ * cosines); per-pixel: loss = sum_g (1 - sum_p m_p cos_p / sum_p m_p).  Masked-out pixels of a, b / target are never read (a select:
+ * Inf / NaN there change nothing), d loss / d a is exactly 0 there, and masked-out up-sampled pixels contribute nothing to g_x.  An
+ * all-ones mask gives the bits of the unmasked kernels (G = 1 for the channel-wise ones).  A group without a valid pixel: cos = 0
+ * (loss contribution 1) and a zero gradient channel-wise, NaN per-pixel.  float64 sums in a fixed order, no atomics.
+ * scratch: nefes_cosine_loss_scratch_doubles(G * Cg) for the channel-wise forms; the per-pixel forms keep the groups' counts of valid
+ * pixels for the backward: nefes_pixcos_masked_scratch_doubles / nefes_uppixcos_masked_scratch_doubles (first G doubles: the mean
+ * cosines).  There is no prepared-target (Gram) form: sum_p m_p up_p^2 does not separate into the two axes. */
+int nefes_cosine_loss_masked_fwd(int G, int Cg, int64_t P, const float* a, const float* b, const uint8_t* mask, double* scratch, float* loss,
+                                 void* stream);
+int nefes_cosine_loss_masked_bwd(int G, int Cg, int64_t P, const float* a, const float* b, const uint8_t* mask, const double* scratch,
+                                 const float* g_loss, float* g_a, void* stream);
+int nefes_upcos_loss_masked_fwd(int G, int Cg, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                const uint8_t* mask, double* scratch, float* loss, void* stream);
+int nefes_upcos_loss_masked_bwd(int G, int Cg, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                const uint8_t* mask, const double* scratch, const float* g_loss, const int* tx_first, const int* tx_count,
+                                const float* tx_wt, const int* ty_first, const int* ty_count, const float* ty_wt, int T, float* tmp,
+                                float* g_x, void* stream);
+size_t nefes_pixcos_masked_scratch_doubles(int G, int64_t P);
+int nefes_pixcos_loss_masked_fwd(int G, int C, int64_t P, const float* a, const float* b, const uint8_t* mask, double* scratch, float* loss,
+                                 void* stream);
+int nefes_pixcos_loss_masked_bwd(int G, int C, int64_t P, const float* a, const float* b, const uint8_t* mask, const double* scratch,
+                                 const float* g_loss, float* g_a, void* stream);
+size_t nefes_uppixcos_masked_scratch_doubles(int G, int OH, int OW, int crop);
+int nefes_uppixcos_loss_masked_fwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                   const uint8_t* mask, double* scratch, float* loss, void* stream);
+int nefes_uppixcos_loss_masked_bwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                   const uint8_t* mask, const double* scratch, const float* g_loss, const int* tx_first,
+                                   const int* tx_count, const float* tx_wt, const int* ty_first, const int* ty_count, const float* ty_wt,
+                                   int T, float* tmp, float* g_x, void* stream);
 /* The same loss for a FIXED target (the refinement loop holds the query image's features for all opt_iter iterations of an image:
  * DFM_APR_refine.py:100-131), through the Gram matrices of the up-sampling.  Per channel up = Uy X Ux^T, so
  *     <up, target> = <X, Tt>, Tt = Uy^T target Ux;   |up|^2 = <X, Gy X Gx>, Gy = Uy^T Uy, Gx = Ux^T Ux;   |target|^2 a constant,

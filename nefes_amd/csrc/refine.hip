@@ -412,14 +412,22 @@ __global__ void svd_reg_bwd_kernel(int n, const double* __restrict__ save, const
 // ---- cosine feature loss -------------------------------------------------------------------------------------------------
 constexpr int kParts = 8;      // blocks per channel
 
+// MASKED (the reference's masked_feature_loss, dm/DFM_pose_refine.py:257-288; `--semantic`): one uint8 per pixel and GROUP (image) of Cg
+// channels, valid iff != 0.  A masked-out pixel is never READ (a select, not a product with 0: Inf / NaN there leave every result
+// alone), the sums run over the valid pixels in the order the unmasked instance walks them -- an all-ones mask gives its bits -- and
+// d loss / d a is exactly 0 there.  The unmasked instances ignore `mask` and `Cg`.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void cosine_partial_kernel(int C, long P, const float* __restrict__ a, const float* __restrict__ b,
+                                                             const uint8_t* __restrict__ mask, int Cg,
                                                              double* __restrict__ part) {      // part [C][kParts][3]
     const int c = blockIdx.x / kParts, q = blockIdx.x % kParts;
     const long per = (P + kParts - 1) / kParts, lo = q * per, hi = lo + per < P ? lo + per : P;
     const float* pa = a + (long)c * P;
     const float* pb = b + (long)c * P;
+    const uint8_t* pm = MASKED ? mask + (long)(c / Cg) * P : nullptr;
     double dab = 0, daa = 0, dbb = 0;
     for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        if (MASKED && !pm[i]) continue;
         const double x = pa[i], y = pb[i];
         dab += x * y;
         daa += x * x;
@@ -467,13 +475,53 @@ __global__ __launch_bounds__(256) void cosine_final_kernel(int C, double eps, co
     if (threadIdx.x == 0) *loss = (float)(1.0 - sh[0] / C);
 }
 
-// g_a[c][p] = -g_loss / C * d cos_c / d a[c][p]
+// The same for G groups of Cg channels: loss = sum_g (1 - mean of the group's Cg cosines); one group: cosine_final_kernel's bits.  A
+// channel without a valid pixel has all three sums 0: cos = 0 (both norms clamped at eps), as the reference's expression gives.
+__global__ __launch_bounds__(256) void cosine_final_groups_kernel(int G, int Cg, double eps, const double* __restrict__ part,
+                                                                  double* __restrict__ stats, float* __restrict__ loss) {
+    __shared__ double sh[256];
+    double total = 0;
+    for (int g = 0; g < G; ++g) {
+        double acc = 0;
+        for (int cc = threadIdx.x; cc < Cg; cc += 256) {
+            const long c = (long)g * Cg + cc;
+            double dab = 0, daa = 0, dbb = 0;
+            for (int q = 0; q < kParts; ++q) {
+                const double* o = part + (c * kParts + q) * 3;
+                dab += o[0]; daa += o[1]; dbb += o[2];
+            }
+            const double na = sqrt(daa), nb = sqrt(dbb);
+            const double cs = dab / ((na > eps ? na : eps) * (nb > eps ? nb : eps));
+            stats[c * 4 + 0] = dab; stats[c * 4 + 1] = na; stats[c * 4 + 2] = nb; stats[c * 4 + 3] = cs;
+            acc += cs;
+        }
+        sh[threadIdx.x] = acc;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+            __syncthreads();
+        }
+        total += 1.0 - sh[0] / Cg;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = (float)total;
+}
+
+// g_a[c][p] = -g_loss / C * d cos_c / d a[c][p]   (MASKED: C planes in groups of Cg, the mean over the group's Cg; 0 where masked out)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void cosine_bwd_kernel(int C, long P, double eps, const float* __restrict__ a, const float* __restrict__ b,
-                                                         const double* __restrict__ stats, const float* __restrict__ g_loss,
-                                                         float* __restrict__ g_a) {
+                                                         const uint8_t* __restrict__ mask, int Cg, const double* __restrict__ stats,
+                                                         const float* __restrict__ g_loss, float* __restrict__ g_a) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)C * P) return;
     const int c = (int)(idx / P);
+    if (MASKED) {
+        if (!mask[(long)(c / Cg) * P + idx % P]) {
+            g_a[idx] = 0.f;
+            return;
+        }
+        C = Cg;
+    }
     const double dab = stats[c * 4 + 0], na = stats[c * 4 + 1], nb = stats[c * 4 + 2];
     const double nbc = nb > eps ? nb : eps;
     const double k = -(double)g_loss[0] / C;
@@ -510,7 +558,9 @@ __device__ __forceinline__ float up_value(const float* plane, int w, int h, cons
     return rows[0] * ty.w[0] + rows[1] * ty.w[1] + rows[2] * ty.w[2] + rows[3] * ty.w[3];
 }
 
-__global__ __launch_bounds__(256) void upcos_partial_kernel(UpCosArgs a, double* __restrict__ part) {      // part [C][kParts][3]
+template <bool MASKED>      // mask [C / Cg][CH][CW]: see cosine_partial_kernel
+__global__ __launch_bounds__(256) void upcos_partial_kernel(UpCosArgs a, const uint8_t* __restrict__ mask, int Cg,
+                                                            double* __restrict__ part) {      // part [C][kParts][3]
     using namespace nefes_bicubic;
     extern __shared__ float plane[];
     const int c = blockIdx.x / kParts, q = blockIdx.x % kParts;
@@ -526,7 +576,9 @@ __global__ __launch_bounds__(256) void upcos_partial_kernel(UpCosArgs a, double*
 #pragma unroll
         for (int m = 0; m < 4; ++m) xs[m] = clampi(tx.base - 1 + m, a.w);
         const float* pb = a.target + (long)c * a.CH * a.CW + j;
+        const uint8_t* pm = MASKED ? mask + (long)(c / Cg) * a.CH * a.CW + j : nullptr;
         for (int r = r_lo; r < r_hi; ++r) {
+            if (MASKED && !pm[(long)r * a.CW]) continue;
             const Taps ty = taps_of(a.sy, r + a.o0);
             float rows[4];
 #pragma unroll
@@ -561,9 +613,12 @@ __global__ __launch_bounds__(256) void upcos_partial_kernel(UpCosArgs a, double*
 // One workgroup per (channel, up-sampled row of the window): the row's gradient d loss / d up[c][oy][:] is formed in LDS from the
 // interpolated values and the target row, and gathered along x onto the w source columns: tmp[c][oy - o0][0..w).  The gather
 // along y (bicubic_gather_kernel of upsample.hip, inner = w) finishes the job.
+// MASKED: a masked-out up-sampled pixel contributes nothing to the gather (its gs is 0 and its target is not read); the mean is over
+// the group's Cg channels.
+template <bool MASKED>
 __global__ __launch_bounds__(128) void upcos_bwd_rows_kernel(UpCosArgs a, double eps, const double* __restrict__ stats,
                                                              const float* __restrict__ g_loss, nefes_bicubic::GatherTable gx,
-                                                             float* __restrict__ tmp) {
+                                                             const uint8_t* __restrict__ mask, int Cg, float* __restrict__ tmp) {
     using namespace nefes_bicubic;
     extern __shared__ float lds[];
     float* rows = lds;                 // [4][w] the four source rows of this up-sampled row
@@ -575,11 +630,16 @@ __global__ __launch_bounds__(128) void upcos_bwd_rows_kernel(UpCosArgs a, double
     __syncthreads();
     const double dab = stats[c * 4 + 0], na = stats[c * 4 + 1], nb = stats[c * 4 + 2];
     const double nbc = nb > eps ? nb : eps;
-    const double k = -(double)g_loss[0] / a.C;
+    const double k = -(double)g_loss[0] / (MASKED ? Cg : a.C);
     // d cos / d a = b / (|a||b|) - (a.b) a / (|a|^3 |b|)  (a clamped norm is a constant): two factors per channel, not per pixel
     const double k1 = na > eps ? k / (na * nbc) : k / (eps * nbc), k2 = na > eps ? k * dab / (na * na * na * nbc) : 0.0;
     const float* pb = a.target + ((long)c * a.CH + r) * a.CW;
+    const uint8_t* pm = MASKED ? mask + ((long)(c / Cg) * a.CH + r) * a.CW : nullptr;
     for (int j = threadIdx.x; j < a.CW; j += 128) {
+        if (MASKED && !pm[j]) {
+            gs[j] = 0.f;
+            continue;
+        }
         const Taps tx = taps_of(a.sx, j + a.o0);
         int xs[4];
 #pragma unroll
@@ -664,14 +724,25 @@ __device__ __forceinline__ void pix_finish(double (*sh)[kPixSlices][kPixCols], d
     pix_block_sum(red, kPixCols);
 }
 
+// MASKED (mask [G][P] uint8, see cosine_partial_kernel): a masked-out pixel is not read, leaves no stats (the backward does not read them
+// either) and adds nothing to the workgroup's sum; the workgroup's count of valid pixels goes to cnt [G][nb] beside part, and the mean
+// is over the group's valid pixels (none: 0 / 0 = NaN, what the reference's mean of an empty tensor gives).
+template <bool MASKED>
 __global__ __launch_bounds__(kPixBlock) void pixcos_fwd_kernel(int C, long P, double eps, const float* __restrict__ a, const float* __restrict__ b,
-                                                               double* __restrict__ stats, double* __restrict__ part) {
+                                                               const uint8_t* __restrict__ mask, double* __restrict__ stats,
+                                                               double* __restrict__ part, double* __restrict__ cnt) {
     __shared__ double sh[3][kPixSlices][kPixCols];
     const int g = blockIdx.y, sl = threadIdx.x / kPixCols;
     const long p = (long)blockIdx.x * kPixCols + threadIdx.x % kPixCols;
     const int per = (C + kPixSlices - 1) / kPixSlices, c0 = sl * per, c1 = c0 + per < C ? c0 + per : C;
     double dab = 0, daa = 0, dbb = 0;
-    if (p < P) {
+    bool live = p < P;
+    if (MASKED) {
+        live = live && mask[(long)g * P + p] != 0;
+        const int n = __syncthreads_count(live && sl == 0);
+        if (threadIdx.x == 0) cnt[(long)g * gridDim.x + blockIdx.x] = (double)n;
+    }
+    if (live) {
         const float* pa = a + (long)g * C * P + p;
         const float* pb = b + (long)g * C * P + p;
 #pragma unroll 4
@@ -682,16 +753,28 @@ __global__ __launch_bounds__(kPixBlock) void pixcos_fwd_kernel(int C, long P, do
             dbb += y * y;
         }
     }
-    pix_finish(sh, dab, daa, dbb, p < P, eps, stats + (long)g * 3 * P + p, P);
+    pix_finish(sh, dab, daa, dbb, live, eps, stats + (long)g * 3 * P + p, P);
     if (threadIdx.x == 0) part[(long)g * gridDim.x + blockIdx.x] = sh[0][0][0];
 }
 
 // mean[g] = (sum of the group's nb partials) / P;  loss = sum_g (1 - mean[g])
-__global__ __launch_bounds__(256) void pixcos_final_kernel(int G, int nb, double P, const double* __restrict__ part, double* __restrict__ mean,
-                                                           float* __restrict__ loss) {
+// MASKED: P is the group's count of valid pixels, the sum of its nb entries of cnt (whole numbers: exact in any order), kept in
+// count[g] for the backward.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void pixcos_final_kernel(int G, int nb, double P, const double* __restrict__ part, const double* __restrict__ cnt,
+                                                           double* __restrict__ mean, double* __restrict__ count, float* __restrict__ loss) {
     __shared__ double sh[256];
     double total = 0;
     for (int g = 0; g < G; ++g) {
+        if (MASKED) {
+            double n = 0;
+            for (int i = threadIdx.x; i < nb; i += 256) n += cnt[(long)g * nb + i];
+            sh[threadIdx.x] = n;
+            pix_block_sum(sh, 256);
+            P = sh[0];
+            __syncthreads();
+            if (threadIdx.x == 0) count[g] = P;
+        }
         double acc = 0;
         for (int i = threadIdx.x; i < nb; i += 256) acc += part[(long)g * nb + i];
         sh[threadIdx.x] = acc;
@@ -716,14 +799,20 @@ __device__ __forceinline__ PixK pix_factors(double k, double dab, double na, dou
     return r;
 }
 
+template <bool MASKED>      // count [G]: the groups' valid pixels (pixcos_final_kernel)
 __global__ __launch_bounds__(256) void pixcos_bwd_kernel(long n, int C, long P, double eps, const float* __restrict__ a, const float* __restrict__ b,
+                                                         const uint8_t* __restrict__ mask, const double* __restrict__ count,
                                                          const double* __restrict__ stats, const float* __restrict__ g_loss,
                                                          float* __restrict__ g_a) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n) return;
     const long p = idx % P, g = idx / (P * C);
+    if (MASKED && !mask[g * P + p]) {
+        g_a[idx] = 0.f;
+        return;
+    }
     const double* st = stats + g * 3 * P + p;
-    const PixK f = pix_factors(-(double)g_loss[0] / (double)P, st[0], st[P], st[2 * P], eps);
+    const PixK f = pix_factors(-(double)g_loss[0] / (MASKED ? count[g] : (double)P), st[0], st[P], st[2 * P], eps);
     g_a[idx] = (float)(f.k1 * (double)b[idx] - f.k2 * (double)a[idx]);
 }
 
@@ -733,8 +822,10 @@ __global__ __launch_bounds__(256) void pixcos_bwd_kernel(long n, int C, long P, 
 // computes its x taps and clamped source columns once and interpolates every channel's value with up_value's expression and order
 // (x first, then y: the value bicubic_up_fwd_kernel would have written, bit for bit) from the channel's four source rows in x (2.4 MB
 // at the loop's shape: L2) -- the target row is the only HBM read.  part [G][CH][segments].
-__global__ __launch_bounds__(kPixBlock) void uppixcos_fwd_kernel(UpCosArgs a, int Cg, double eps, double* __restrict__ stats,
-                                                                 double* __restrict__ part) {
+template <bool MASKED>      // mask [G][CH][CW], cnt beside part: see pixcos_fwd_kernel
+__global__ __launch_bounds__(kPixBlock) void uppixcos_fwd_kernel(UpCosArgs a, int Cg, double eps, const uint8_t* __restrict__ mask,
+                                                                 double* __restrict__ stats, double* __restrict__ part,
+                                                                 double* __restrict__ cnt) {
     using namespace nefes_bicubic;
     __shared__ double sh[3][kPixSlices][kPixCols];
     const int r = blockIdx.x, seg = blockIdx.y, g = blockIdx.z, sl = threadIdx.x / kPixCols;
@@ -742,7 +833,13 @@ __global__ __launch_bounds__(kPixBlock) void uppixcos_fwd_kernel(UpCosArgs a, in
     const long P = (long)a.CH * a.CW, plane = (long)a.h * a.w;
     const int per = (Cg + kPixSlices - 1) / kPixSlices, c0 = sl * per, c1 = c0 + per < Cg ? c0 + per : Cg;
     double dab = 0, daa = 0, dbb = 0;
-    if (j < a.CW) {
+    bool live = j < a.CW;
+    if (MASKED) {
+        live = live && mask[(long)g * P + (long)r * a.CW + j] != 0;
+        const int n = __syncthreads_count(live && sl == 0);
+        if (threadIdx.x == 0) cnt[((long)g * a.CH + r) * gridDim.y + seg] = (double)n;
+    }
+    if (live) {
         const Taps ty = taps_of(a.sy, r + a.o0), tx = taps_of(a.sx, j + a.o0);
         long ro[4];
         int xs[4];
@@ -769,14 +866,16 @@ __global__ __launch_bounds__(kPixBlock) void uppixcos_fwd_kernel(UpCosArgs a, in
             dbb += yv * yv;
         }
     }
-    pix_finish(sh, dab, daa, dbb, j < a.CW, eps, stats + (long)g * 3 * P + (long)r * a.CW + j, P);
+    pix_finish(sh, dab, daa, dbb, live, eps, stats + (long)g * 3 * P + (long)r * a.CW + j, P);
     if (threadIdx.x == 0) part[((long)g * a.CH + r) * gridDim.y + seg] = sh[0][0][0];
 }
 
 // Backward: upcos_bwd_rows_kernel with the two factors read per pixel from the stats instead of per channel; one workgroup per
 // (plane = group * Cg + channel, window row), gathered along x into tmp [G*C, CH, w]; upcos_gather_rows_kernel finishes along y.
+template <bool MASKED>      // count [G]: the groups' valid pixels; a masked-out pixel's gs is 0, its stats and target are not read
 __global__ __launch_bounds__(128) void uppixcos_bwd_rows_kernel(UpCosArgs a, int Cg, double eps, const double* __restrict__ stats,
                                                                 const float* __restrict__ g_loss, nefes_bicubic::GatherTable gx,
+                                                                const uint8_t* __restrict__ mask, const double* __restrict__ count,
                                                                 float* __restrict__ tmp) {
     using namespace nefes_bicubic;
     extern __shared__ float lds[];
@@ -788,10 +887,15 @@ __global__ __launch_bounds__(128) void uppixcos_bwd_rows_kernel(UpCosArgs a, int
     for (int i = threadIdx.x; i < 4 * a.w; i += 128) rows[i] = src[(long)clampi(ty.base - 1 + i / a.w, a.h) * a.w + i % a.w];
     __syncthreads();
     const long P = (long)a.CH * a.CW;
-    const double k = -(double)g_loss[0] / (double)P;
+    const double k = -(double)g_loss[0] / (MASKED ? count[c / Cg] : (double)P);
     const double* st = stats + (long)(c / Cg) * 3 * P + (long)r * a.CW;
     const float* pb = a.target + ((long)c * a.CH + r) * a.CW;
+    const uint8_t* pm = MASKED ? mask + (long)(c / Cg) * P + (long)r * a.CW : nullptr;
     for (int j = threadIdx.x; j < a.CW; j += 128) {
+        if (MASKED && !pm[j]) {
+            gs[j] = 0.f;
+            continue;
+        }
         const Taps tx = taps_of(a.sx, j + a.o0);
         int xs[4];
 #pragma unroll
@@ -1047,38 +1151,73 @@ extern "C" int nefes_psnr_ssim(int C, int H, int W, const float* x, int64_t x_ro
     return (int)hipGetLastError();
 }
 
-extern "C" int nefes_upcos_loss_fwd(int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, double* scratch,
-                                    float* loss, void* stream) {
+// The channel-wise losses, unmasked (G = 1, Cg = C, mask = null) and masked (C = G * Cg planes): one body per entry-point pair
+template <bool MASKED>
+static int upcos_loss_fwd(int G, int Cg, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const uint8_t* mask,
+                          double* scratch, float* loss, void* stream) {
     const int CH = OH - 2 * crop, CW = OW - 2 * crop;
-    if (C <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !loss) return NEFES_E_BADARG;
+    if (G <= 0 || Cg <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !loss || (MASKED && !mask))
+        return NEFES_E_BADARG;
     if ((size_t)h * w * 4 > 96 * 1024) return NEFES_E_UNSUPPORTED;           // the channel's plane is staged in LDS
+    if ((long)G * Cg * kParts > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    const int C = G * Cg;
     UpCosArgs a{C, h, w, OH, OW, crop, CH, CW, (float)h / OH, (float)w / OW, x, target};
     double* part = scratch + (size_t)C * 4;
     const size_t lds = (size_t)h * w * 4;
-    hipError_t e = hipFuncSetAttribute((const void*)upcos_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)upcos_partial_kernel<MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(upcos_partial_kernel, dim3(C * kParts), dim3(256), lds, (hipStream_t)stream, a, part);
-    hipLaunchKernelGGL(cosine_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, C, 1e-6, (const double*)part, scratch, loss);
+    hipLaunchKernelGGL(upcos_partial_kernel<MASKED>, dim3(C * kParts), dim3(256), lds, (hipStream_t)stream, a, mask, Cg, part);
+    if (MASKED)
+        hipLaunchKernelGGL(cosine_final_groups_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, G, Cg, 1e-6, (const double*)part, scratch, loss);
+    else
+        hipLaunchKernelGGL(cosine_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, C, 1e-6, (const double*)part, scratch, loss);
     return (int)hipGetLastError();
 }
+extern "C" int nefes_upcos_loss_fwd(int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, double* scratch,
+                                    float* loss, void* stream) {
+    return upcos_loss_fwd<false>(1, C, h, w, OH, OW, crop, x, target, nullptr, scratch, loss, stream);
+}
+extern "C" int nefes_upcos_loss_masked_fwd(int G, int Cg, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                           const uint8_t* mask, double* scratch, float* loss, void* stream) {
+    return upcos_loss_fwd<true>(G, Cg, h, w, OH, OW, crop, x, target, mask, scratch, loss, stream);
+}
 
-extern "C" int nefes_upcos_loss_bwd(int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const double* scratch,
-                                    const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt, const int* ty_first,
-                                    const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream) {
+template <bool MASKED>
+static int upcos_loss_bwd(int G, int Cg, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const uint8_t* mask,
+                          const double* scratch, const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt,
+                          const int* ty_first, const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream) {
     const int CH = OH - 2 * crop, CW = OW - 2 * crop;
-    if (C <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !g_loss || !tmp || !g_x) return NEFES_E_BADARG;
+    if (G <= 0 || Cg <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !g_loss || !tmp || !g_x ||
+        (MASKED && !mask))
+        return NEFES_E_BADARG;
     if (!tx_first || !tx_count || !tx_wt || !ty_first || !ty_count || !ty_wt || T <= 0) return NEFES_E_BADARG;
+    if ((long)G * Cg * CH > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    const int C = G * Cg;
     const nefes_bicubic::GatherTable gx{tx_first, tx_count, tx_wt, T}, gy{ty_first, ty_count, ty_wt, T};
     UpCosArgs a{C, h, w, OH, OW, crop, CH, CW, (float)h / OH, (float)w / OW, x, target};
     const size_t lds = (size_t)(4 * w + CW) * 4;
     if (lds > 96 * 1024) return NEFES_E_UNSUPPORTED;
-    hipError_t e = hipFuncSetAttribute((const void*)upcos_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)upcos_bwd_rows_kernel<MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(upcos_bwd_rows_kernel, dim3((unsigned)((long)C * CH)), dim3(128), lds, (hipStream_t)stream, a, 1e-6, scratch, g_loss, gx, tmp);
+    hipLaunchKernelGGL(upcos_bwd_rows_kernel<MASKED>, dim3((unsigned)((long)C * CH)), dim3(128), lds, (hipStream_t)stream, a, 1e-6, scratch, g_loss,
+                       gx, mask, Cg, tmp);
     const long n = (long)C * h * w;                    // g_x[c][y][x] = sum over the window's rows oy of Wy(oy -> y) tmp[c][oy - o0][x]
     hipLaunchKernelGGL(upcos_gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long)C, h, CH, (long)w, gy,
                        (const float*)tmp, g_x);
     return (int)hipGetLastError();
+}
+extern "C" int nefes_upcos_loss_bwd(int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const double* scratch,
+                                    const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt, const int* ty_first,
+                                    const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream) {
+    return upcos_loss_bwd<false>(1, C, h, w, OH, OW, crop, x, target, nullptr, scratch, g_loss, tx_first, tx_count, tx_wt, ty_first, ty_count,
+                                 ty_wt, T, tmp, g_x, stream);
+}
+extern "C" int nefes_upcos_loss_masked_bwd(int G, int Cg, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                           const uint8_t* mask, const double* scratch, const float* g_loss, const int* tx_first,
+                                           const int* tx_count, const float* tx_wt, const int* ty_first, const int* ty_count, const float* ty_wt,
+                                           int T, float* tmp, float* g_x, void* stream) {
+    return upcos_loss_bwd<true>(G, Cg, h, w, OH, OW, crop, x, target, mask, scratch, g_loss, tx_first, tx_count, tx_wt, ty_first, ty_count, ty_wt,
+                                T, tmp, g_x, stream);
 }
 
 // scratch of the per-pixel loss (doubles): mean [G] | stats [G][3][P] | one partial per forward workgroup
@@ -1089,50 +1228,100 @@ extern "C" size_t nefes_uppixcos_scratch_doubles(int G, int OH, int OW, int crop
     const int CH = OH - 2 * crop, CW = OW - 2 * crop;
     return G > 0 && crop >= 0 && CH > 0 && CW > 0 ? (size_t)G * (1 + 3 * (size_t)CH * CW + (size_t)CH * ((CW + kPixCols - 1) / kPixCols)) : 0;
 }
+// masked: the unmasked layout | the workgroups' counts of valid pixels (one per partial) | count [G]
+extern "C" size_t nefes_pixcos_masked_scratch_doubles(int G, int64_t P) {
+    return G > 0 && P > 0 ? nefes_pixcos_scratch_doubles(G, P) + (size_t)G * (1 + (size_t)((P + kPixCols - 1) / kPixCols)) : 0;
+}
+extern "C" size_t nefes_uppixcos_masked_scratch_doubles(int G, int OH, int OW, int crop) {
+    const int CH = OH - 2 * crop, CW = OW - 2 * crop;
+    return G > 0 && crop >= 0 && CH > 0 && CW > 0
+               ? nefes_uppixcos_scratch_doubles(G, OH, OW, crop) + (size_t)G * (1 + (size_t)CH * ((CW + kPixCols - 1) / kPixCols))
+               : 0;
+}
 
-extern "C" int nefes_pixcos_loss_fwd(int G, int C, int64_t P, const float* a, const float* b, double* scratch, float* loss, void* stream) {
-    if (G <= 0 || G > 65535 || C <= 0 || P <= 0 || !a || !b || !scratch || !loss) return NEFES_E_BADARG;
+// The per-pixel losses, unmasked (mask = null) and masked: one body per entry-point pair
+template <bool MASKED>
+static int pixcos_loss_fwd(int G, int C, int64_t P, const float* a, const float* b, const uint8_t* mask, double* scratch, float* loss,
+                           void* stream) {
+    if (G <= 0 || G > 65535 || C <= 0 || P <= 0 || !a || !b || !scratch || !loss || (MASKED && !mask)) return NEFES_E_BADARG;
     const int64_t nb = (P + kPixCols - 1) / kPixCols;
     if (nb > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
     double* stats = scratch + G;
     double* part = stats + (size_t)G * 3 * P;
-    hipLaunchKernelGGL(pixcos_fwd_kernel, dim3((unsigned)nb, (unsigned)G), dim3(kPixBlock), 0, (hipStream_t)stream, C, (long)P, 1e-6, a, b, stats, part);
-    hipLaunchKernelGGL(pixcos_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, G, (int)nb, (double)P, (const double*)part, scratch, loss);
+    double* cnt = MASKED ? part + (size_t)G * nb : nullptr;
+    double* count = MASKED ? cnt + (size_t)G * nb : nullptr;
+    hipLaunchKernelGGL(pixcos_fwd_kernel<MASKED>, dim3((unsigned)nb, (unsigned)G), dim3(kPixBlock), 0, (hipStream_t)stream, C, (long)P, 1e-6, a, b,
+                       mask, stats, part, cnt);
+    hipLaunchKernelGGL(pixcos_final_kernel<MASKED>, dim3(1), dim3(256), 0, (hipStream_t)stream, G, (int)nb, (double)P, (const double*)part,
+                       (const double*)cnt, scratch, count, loss);
     return (int)hipGetLastError();
 }
+extern "C" int nefes_pixcos_loss_fwd(int G, int C, int64_t P, const float* a, const float* b, double* scratch, float* loss, void* stream) {
+    return pixcos_loss_fwd<false>(G, C, P, a, b, nullptr, scratch, loss, stream);
+}
+extern "C" int nefes_pixcos_loss_masked_fwd(int G, int C, int64_t P, const float* a, const float* b, const uint8_t* mask, double* scratch,
+                                            float* loss, void* stream) {
+    return pixcos_loss_fwd<true>(G, C, P, a, b, mask, scratch, loss, stream);
+}
 
-extern "C" int nefes_pixcos_loss_bwd(int G, int C, int64_t P, const float* a, const float* b, const double* scratch, const float* g_loss,
-                                     float* g_a, void* stream) {
-    if (G <= 0 || G > 65535 || C <= 0 || P <= 0 || !a || !b || !scratch || !g_loss || !g_a) return NEFES_E_BADARG;
+template <bool MASKED>
+static int pixcos_loss_bwd(int G, int C, int64_t P, const float* a, const float* b, const uint8_t* mask, const double* scratch,
+                           const float* g_loss, float* g_a, void* stream) {
+    if (G <= 0 || G > 65535 || C <= 0 || P <= 0 || !a || !b || !scratch || !g_loss || !g_a || (MASKED && !mask)) return NEFES_E_BADARG;
     const long n = (long)G * C * P;
     if ((n + 255) / 256 > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
-    hipLaunchKernelGGL(pixcos_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, C, (long)P, 1e-6, a, b,
-                       scratch + G, g_loss, g_a);
+    const int64_t nb = (P + kPixCols - 1) / kPixCols;
+    const double* count = MASKED ? scratch + (size_t)G * (1 + 3 * (size_t)P + 2 * (size_t)nb) : nullptr;
+    hipLaunchKernelGGL(pixcos_bwd_kernel<MASKED>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, C, (long)P, 1e-6, a, b,
+                       mask, count, scratch + G, g_loss, g_a);
     return (int)hipGetLastError();
 }
+extern "C" int nefes_pixcos_loss_bwd(int G, int C, int64_t P, const float* a, const float* b, const double* scratch, const float* g_loss,
+                                     float* g_a, void* stream) {
+    return pixcos_loss_bwd<false>(G, C, P, a, b, nullptr, scratch, g_loss, g_a, stream);
+}
+extern "C" int nefes_pixcos_loss_masked_bwd(int G, int C, int64_t P, const float* a, const float* b, const uint8_t* mask, const double* scratch,
+                                            const float* g_loss, float* g_a, void* stream) {
+    return pixcos_loss_bwd<true>(G, C, P, a, b, mask, scratch, g_loss, g_a, stream);
+}
 
-extern "C" int nefes_uppixcos_loss_fwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
-                                       double* scratch, float* loss, void* stream) {
+template <bool MASKED>
+static int uppixcos_loss_fwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const uint8_t* mask,
+                             double* scratch, float* loss, void* stream) {
     const int CH = OH - 2 * crop, CW = OW - 2 * crop;
-    if (G <= 0 || G > 65535 || C <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !loss) return NEFES_E_BADARG;
+    if (G <= 0 || G > 65535 || C <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !loss ||
+        (MASKED && !mask))
+        return NEFES_E_BADARG;
     if ((long)G * C > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
     UpCosArgs a{G * C, h, w, OH, OW, crop, CH, CW, (float)h / OH, (float)w / OW, x, target};
     double* stats = scratch + G;
     double* part = stats + (size_t)G * 3 * CH * CW;
     const int nseg = (CW + kPixCols - 1) / kPixCols;
     if (nseg > 65535 || (long)CH * nseg > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
-    hipLaunchKernelGGL(uppixcos_fwd_kernel, dim3((unsigned)CH, (unsigned)nseg, (unsigned)G), dim3(kPixBlock), 0, (hipStream_t)stream, a, C, 1e-6, stats,
-                       part);
-    hipLaunchKernelGGL(pixcos_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, G, CH * nseg, (double)CH * CW, (const double*)part, scratch,
-                       loss);
+    double* cnt = MASKED ? part + (size_t)G * CH * nseg : nullptr;
+    double* count = MASKED ? cnt + (size_t)G * CH * nseg : nullptr;
+    hipLaunchKernelGGL(uppixcos_fwd_kernel<MASKED>, dim3((unsigned)CH, (unsigned)nseg, (unsigned)G), dim3(kPixBlock), 0, (hipStream_t)stream, a, C,
+                       1e-6, mask, stats, part, cnt);
+    hipLaunchKernelGGL(pixcos_final_kernel<MASKED>, dim3(1), dim3(256), 0, (hipStream_t)stream, G, CH * nseg, (double)CH * CW, (const double*)part,
+                       (const double*)cnt, scratch, count, loss);
     return (int)hipGetLastError();
 }
+extern "C" int nefes_uppixcos_loss_fwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                       double* scratch, float* loss, void* stream) {
+    return uppixcos_loss_fwd<false>(G, C, h, w, OH, OW, crop, x, target, nullptr, scratch, loss, stream);
+}
+extern "C" int nefes_uppixcos_loss_masked_fwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                              const uint8_t* mask, double* scratch, float* loss, void* stream) {
+    return uppixcos_loss_fwd<true>(G, C, h, w, OH, OW, crop, x, target, mask, scratch, loss, stream);
+}
 
-extern "C" int nefes_uppixcos_loss_bwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
-                                       const double* scratch, const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt,
-                                       const int* ty_first, const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream) {
+template <bool MASKED>
+static int uppixcos_loss_bwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target, const uint8_t* mask,
+                             const double* scratch, const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt,
+                             const int* ty_first, const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream) {
     const int CH = OH - 2 * crop, CW = OW - 2 * crop;
-    if (G <= 0 || G > 65535 || C <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !g_loss || !tmp || !g_x)
+    if (G <= 0 || G > 65535 || C <= 0 || h <= 0 || w <= 0 || crop < 0 || CH <= 0 || CW <= 0 || !x || !target || !scratch || !g_loss || !tmp || !g_x ||
+        (MASKED && !mask))
         return NEFES_E_BADARG;
     if (!tx_first || !tx_count || !tx_wt || !ty_first || !ty_count || !ty_wt || T <= 0) return NEFES_E_BADARG;
     const long planes = (long)G * C, n = planes * h * w;
@@ -1141,13 +1330,28 @@ extern "C" int nefes_uppixcos_loss_bwd(int G, int C, int h, int w, int OH, int O
     UpCosArgs a{(int)planes, h, w, OH, OW, crop, CH, CW, (float)h / OH, (float)w / OW, x, target};
     const size_t lds = (size_t)(4 * w + CW) * 4;
     if (lds > 96 * 1024) return NEFES_E_UNSUPPORTED;
-    hipError_t e = hipFuncSetAttribute((const void*)uppixcos_bwd_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)uppixcos_bwd_rows_kernel<MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(uppixcos_bwd_rows_kernel, dim3((unsigned)(planes * CH)), dim3(128), lds, (hipStream_t)stream, a, C, 1e-6, scratch + G, g_loss,
-                       gx, tmp);
+    const size_t nparts = (size_t)CH * ((CW + kPixCols - 1) / kPixCols);
+    const double* count = MASKED ? scratch + (size_t)G * (1 + 3 * (size_t)CH * CW + 2 * nparts) : nullptr;
+    hipLaunchKernelGGL(uppixcos_bwd_rows_kernel<MASKED>, dim3((unsigned)(planes * CH)), dim3(128), lds, (hipStream_t)stream, a, C, 1e-6, scratch + G,
+                       g_loss, gx, mask, count, tmp);
     hipLaunchKernelGGL(upcos_gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, planes, h, CH, (long)w, gy,
                        (const float*)tmp, g_x);
     return (int)hipGetLastError();
+}
+extern "C" int nefes_uppixcos_loss_bwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                       const double* scratch, const float* g_loss, const int* tx_first, const int* tx_count, const float* tx_wt,
+                                       const int* ty_first, const int* ty_count, const float* ty_wt, int T, float* tmp, float* g_x, void* stream) {
+    return uppixcos_loss_bwd<false>(G, C, h, w, OH, OW, crop, x, target, nullptr, scratch, g_loss, tx_first, tx_count, tx_wt, ty_first, ty_count,
+                                    ty_wt, T, tmp, g_x, stream);
+}
+extern "C" int nefes_uppixcos_loss_masked_bwd(int G, int C, int h, int w, int OH, int OW, int crop, const float* x, const float* target,
+                                              const uint8_t* mask, const double* scratch, const float* g_loss, const int* tx_first,
+                                              const int* tx_count, const float* tx_wt, const int* ty_first, const int* ty_count,
+                                              const float* ty_wt, int T, float* tmp, float* g_x, void* stream) {
+    return uppixcos_loss_bwd<true>(G, C, h, w, OH, OW, crop, x, target, mask, scratch, g_loss, tx_first, tx_count, tx_wt, ty_first, ty_count, ty_wt,
+                                   T, tmp, g_x, stream);
 }
 
 extern "C" int nefes_bicubic_gram(int n_in, int n_out, int o0, int n_win, double* G, void* stream) {
@@ -1292,7 +1496,7 @@ extern "C" size_t nefes_cosine_loss_scratch_doubles(int C) { return C > 0 ? (siz
 extern "C" int nefes_cosine_loss_fwd(int C, int64_t P, const float* a, const float* b, double* scratch, float* loss, void* stream) {
     if (C <= 0 || P <= 0 || !a || !b || !scratch || !loss) return NEFES_E_BADARG;
     double* part = scratch + (size_t)C * 4;
-    hipLaunchKernelGGL(cosine_partial_kernel, dim3(C * kParts), dim3(256), 0, (hipStream_t)stream, C, (long)P, a, b, part);
+    hipLaunchKernelGGL(cosine_partial_kernel<false>, dim3(C * kParts), dim3(256), 0, (hipStream_t)stream, C, (long)P, a, b, nullptr, C, part);
     hipLaunchKernelGGL(cosine_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, C, 1e-6, (const double*)part, scratch, loss);
     return (int)hipGetLastError();
 }
@@ -1301,8 +1505,30 @@ extern "C" int nefes_cosine_loss_bwd(int C, int64_t P, const float* a, const flo
                                      float* g_a, void* stream) {
     if (C <= 0 || P <= 0 || !a || !b || !scratch || !g_loss || !g_a) return NEFES_E_BADARG;
     const long n = (long)C * P;
-    hipLaunchKernelGGL(cosine_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, C, (long)P, 1e-6, a, b,
-                       scratch, g_loss, g_a);
+    hipLaunchKernelGGL(cosine_bwd_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, C, (long)P, 1e-6, a, b,
+                       nullptr, C, scratch, g_loss, g_a);
+    return (int)hipGetLastError();
+}
+
+// masked: a, b [G, Cg, P], mask [G, P]; loss = sum_g (1 - mean of the group's Cg cosines over its valid pixels)
+extern "C" int nefes_cosine_loss_masked_fwd(int G, int Cg, int64_t P, const float* a, const float* b, const uint8_t* mask, double* scratch,
+                                            float* loss, void* stream) {
+    if (G <= 0 || Cg <= 0 || P <= 0 || !a || !b || !mask || !scratch || !loss) return NEFES_E_BADARG;
+    if ((long)G * Cg * kParts > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    const int C = G * Cg;
+    double* part = scratch + (size_t)C * 4;
+    hipLaunchKernelGGL(cosine_partial_kernel<true>, dim3(C * kParts), dim3(256), 0, (hipStream_t)stream, C, (long)P, a, b, mask, Cg, part);
+    hipLaunchKernelGGL(cosine_final_groups_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, G, Cg, 1e-6, (const double*)part, scratch, loss);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nefes_cosine_loss_masked_bwd(int G, int Cg, int64_t P, const float* a, const float* b, const uint8_t* mask, const double* scratch,
+                                            const float* g_loss, float* g_a, void* stream) {
+    if (G <= 0 || Cg <= 0 || P <= 0 || !a || !b || !mask || !scratch || !g_loss || !g_a) return NEFES_E_BADARG;
+    const long n = (long)G * Cg * P;
+    if ((long)G * Cg > 0x7fffffffl || (n + 255) / 256 > 0x7fffffffl) return NEFES_E_UNSUPPORTED;
+    hipLaunchKernelGGL(cosine_bwd_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, G * Cg, (long)P, 1e-6, a, b,
+                       mask, Cg, scratch, g_loss, g_a);
     return (int)hipGetLastError();
 }
 

@@ -177,6 +177,16 @@ SIGNATURES = {
     "nefes_uppixcos_scratch_doubles": (_sz, [_i, _i, _i, _i]),
     "nefes_uppixcos_loss_fwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "nefes_uppixcos_loss_bwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "nefes_cosine_loss_masked_fwd": (_i, [_i, _i, C.c_int64, _p, _p, _p, _p, _p, _p]),
+    "nefes_cosine_loss_masked_bwd": (_i, [_i, _i, C.c_int64, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_upcos_loss_masked_fwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "nefes_upcos_loss_masked_bwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "nefes_pixcos_masked_scratch_doubles": (_sz, [_i, C.c_int64]),
+    "nefes_pixcos_loss_masked_fwd": (_i, [_i, _i, C.c_int64, _p, _p, _p, _p, _p, _p]),
+    "nefes_pixcos_loss_masked_bwd": (_i, [_i, _i, C.c_int64, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_uppixcos_masked_scratch_doubles": (_sz, [_i, _i, _i, _i]),
+    "nefes_uppixcos_loss_masked_fwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "nefes_uppixcos_loss_masked_bwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "nefes_train_loss_scratch_doubles": (_sz, [_i]),
     "nefes_train_loss_fwd": (_i, [C.POINTER(NefesTrainLossDesc)] + [_p] * 13),
     "nefes_train_loss_bwd": (_i, [C.POINTER(NefesTrainLossDesc)] + [_p] * 20),

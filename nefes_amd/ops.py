@@ -1666,6 +1666,74 @@ def _loss_buffer(out, device):
     return out.detach()            # (a new tensor object on the same storage: autograd attaches this call's history to it, not to the buffer)
 
 
+def _groups_of(planes, groups, what):
+    G = int(groups)
+    if G < 1 or planes % G:
+        raise ValueError(f"nefes_amd: {what}: {planes} leading channels do not split into {groups} groups")
+    return G
+
+
+def _loss_mask(mask, G, spatial, device, what):
+    """The validity mask of a feature loss as the kernels read it: uint8 [G, pixels] on the inputs' device, contiguous -- one byte per
+    pixel and group (image), shared by the group's channels; valid iff != 0.  Checked BEFORE anything is launched; nothing is converted
+    or copied here (PoseRefiner thresholds an image's mask once, into its own buffer)."""
+    spatial = tuple(int(v) for v in spatial)
+    P = 1
+    for v in spatial:
+        P *= v
+    ok_shapes = {(G,) + spatial, (G, P), (G, 1) + spatial} | ({spatial, (P,)} if G == 1 else set())
+    wrong = ("is not a tensor" if not torch.is_tensor(mask)
+             else f"is on {mask.device}, the inputs on {device}" if mask.device != torch.device(device)
+             else f"is {mask.dtype} (one uint8 per pixel: threshold it once, e.g. (m > 0).to(torch.uint8))" if mask.dtype != torch.uint8
+             else f"has shape {tuple(mask.shape)}, not {(G,) + spatial} (one plane per group, shared by its channels)"
+             if tuple(mask.shape) not in ok_shapes
+             else "is not contiguous" if not mask.is_contiguous() else None)
+    if wrong:
+        raise ValueError(f"nefes_amd: {what}: the mask {wrong}")
+    return mask.detach().reshape(G, P)
+
+
+class MaskedCosineFeatureLoss(torch.autograd.Function):
+    """masked_feature_loss (dm/DFM_pose_refine.py:257-288, per_pixel=False) on [G*Cg, ...] maps with a uint8 mask [G, pixels]: per group
+    1 - mean over its channels of the cosine similarity over its VALID pixels, summed over the groups (csrc/refine.hip MASKED instances)."""
+
+    @staticmethod
+    def forward(ctx, a, b, mask, groups, out=None):
+        G = _groups_of(a.shape[0], groups, "cosine_feature_loss")
+        Cg = a.shape[0] // G
+        af, bf = _f32(a).reshape(G * Cg, -1), _f32(b).reshape(G * Cg, -1)
+        if af.shape != bf.shape:
+            raise ValueError(f"nefes_amd: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
+        mk = _loss_mask(mask, G, a.shape[1:], af.device, "cosine_feature_loss")
+        lib = L.load()
+        scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(G * Cg), dtype=torch.float64, device=af.device)
+        loss = _loss_buffer(out, af.device)
+        with _timed("cosine_loss_masked_fwd"):
+            L.check(lib.nefes_cosine_loss_masked_fwd(G, Cg, af.shape[1], _chk(af, "a"), _chk(bf, "b"), _chk(mk, "mask", torch.uint8),
+                                                     _chk(scratch, "scratch", torch.float64), _chk(loss, "loss"), _stream()),
+                    "nefes_cosine_loss_masked_fwd")
+        ctx.save_for_backward(af, bf, mk, scratch)
+        ctx.cfg = (a.shape, G, Cg)
+        cos = scratch[:4 * G * Cg].view(G * Cg, 4)[:, 3]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(cos)
+        return loss, cos
+
+    @staticmethod
+    def backward(ctx, g, _g_cos):
+        if g is None:
+            return (None,) * 5
+        af, bf, mk, scratch = ctx.saved_tensors
+        shape, G, Cg = ctx.cfg
+        gf = _f32(g).reshape(1)
+        g_a = torch.empty_like(af)
+        with _timed("cosine_loss_masked_bwd"):
+            L.check(L.load().nefes_cosine_loss_masked_bwd(G, Cg, af.shape[1], _chk(af, "a"), _chk(bf, "b"), _chk(mk, "mask", torch.uint8),
+                                                          _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), _chk(g_a, "g_a"),
+                                                          _stream()), "nefes_cosine_loss_masked_bwd")
+        return g_a.reshape(shape), None, None, None, None
+
+
 class CosineFeatureLoss(torch.autograd.Function):
     """feature_loss (dm/DFM_pose_refine.py:211-233, per_pixel=False) on [C, ...] maps: 1 - mean over channels of the cosine
     similarity over pixels; two launches forward, one backward (to `a` only: the target carries no gradient)."""
@@ -1701,12 +1769,25 @@ class CosineFeatureLoss(torch.autograd.Function):
         return g_a.reshape(ctx.shape), None, None
 
 
-def cosine_feature_loss(a, b, return_cos=False, out=None):
+def cosine_feature_loss(a, b, return_cos=False, out=None, groups=1, mask=None):
     """1 - mean over the leading (channel) dimension of the cosine similarity over everything else; `return_cos` adds the
     per-channel similarities (float64, no gradient) -- per-image losses of a batch folded into the channel dimension.
     `out`: a 0-d float32 tensor on the inputs' device that does not require grad; the forward kernel writes the value there and the
-    returned loss shares its storage (None: a fresh tensor)."""
+    returned loss shares its storage (None: a fresh tensor).
+    `groups` = G > 1: the leading dimension is G groups (images) of C channels and the value is the SUM over the groups of each one's
+    loss.  `mask`: uint8 [G, ...pixels] on the inputs' device, one plane per group shared by its channels -- the sums of every channel
+    run over the pixels with mask != 0 only (the reference's masked_feature_loss); values at the others are never read and their
+    gradient is exactly 0.  None: today's unmasked kernels (G > 1: their mean over all G*C channels times G -- the same number)."""
+    if mask is not None:
+        loss, cos = MaskedCosineFeatureLoss.apply(a, b, mask, groups, out)
+        return (loss, cos) if return_cos else loss
+    G = _groups_of(a.shape[0], groups, "cosine_feature_loss")
+    if G > 1 and out is not None:
+        raise ValueError("nefes_amd: cosine_feature_loss: `out` takes the kernel's own value; with groups > 1 and no mask the sum over "
+                         "the groups is formed after it")
     loss, cos = CosineFeatureLoss.apply(a, b, out)
+    if G > 1:
+        loss = loss * float(G)
     return (loss, cos) if return_cos else loss
 
 
@@ -1801,10 +1882,69 @@ class UpsampledCosineLoss(torch.autograd.Function):
         return g_x.reshape(shape), None, None, None, None, None
 
 
-def upsampled_cosine_loss(x, target, size, crop=0, return_cos=False, out=None):
+class MaskedUpsampledCosineLoss(torch.autograd.Function):
+    """UpsampledCosineLoss for G groups with a uint8 mask [G, OH-2crop, OW-2crop] of the up-sampled, cropped pixels: MaskedCosineFeatureLoss
+    of the up-sampled image without the up-sampled image.  One-pass kernels only: sum_p m_p up_p^2 does not separate into the two axes, so
+    there is no prepared-target (Gram) form."""
+
+    @staticmethod
+    def forward(ctx, x, target, mask, OH, OW, crop, groups, out=None):
+        xf = _f32(x)
+        GC, h, w = xf.shape[-3:]
+        G = _groups_of(GC, groups, "upsampled_cosine_loss")
+        if xf.numel() != GC * h * w:
+            raise ValueError(f"nefes_amd: features {tuple(x.shape)} are not [C,h,w] (or [1,C,h,w]) maps")
+        CH, CW = OH - 2 * crop, OW - 2 * crop
+        xf = xf.reshape(GC, h, w)
+        tf = _f32(target).reshape(GC, CH, CW)
+        mk = _loss_mask(mask, G, (CH, CW), xf.device, "upsampled_cosine_loss")
+        lib = L.load()
+        scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(GC), dtype=torch.float64, device=xf.device)
+        loss = _loss_buffer(out, xf.device)
+        with _timed("upcos_loss_masked_fwd"):
+            L.check(lib.nefes_upcos_loss_masked_fwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
+                                                    _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
+                                                    _chk(loss, "loss"), _stream()), "nefes_upcos_loss_masked_fwd")
+        ctx.save_for_backward(xf, tf, mk, scratch)
+        ctx.cfg = (x.shape, OH, OW, crop, G)
+        cos = scratch[:4 * GC].view(GC, 4)[:, 3]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(cos)
+        return loss, cos
+
+    @staticmethod
+    def backward(ctx, g, _g_cos):
+        if g is None:
+            return (None,) * 8
+        xf, tf, mk, scratch = ctx.saved_tensors
+        shape, OH, OW, crop, G = ctx.cfg
+        GC, h, w = xf.shape
+        gf = _f32(g).reshape(1)
+        tmp = torch.empty(GC, OH - 2 * crop, w, device=xf.device)
+        g_x = torch.empty_like(xf)
+        (fx, cx, wx, T), (fy, cy, wy, _) = bicubic_gather_tables(h, w, OH, OW, crop, xf.device)
+        with _timed("upcos_loss_masked_bwd"):
+            L.check(L.load().nefes_upcos_loss_masked_bwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
+                                                         _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
+                                                         _chk(gf, "g_loss"), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), fy.data_ptr(),
+                                                         cy.data_ptr(), wy.data_ptr(), T, _chk(tmp, "tmp"), _chk(g_x, "g_x"), _stream()),
+                    "nefes_upcos_loss_masked_bwd")
+        return (g_x.reshape(shape),) + (None,) * 7
+
+
+def upsampled_cosine_loss(x, target, size, crop=0, return_cos=False, out=None, groups=1, mask=None):
     """1 - mean over channels of the cosine similarity (over pixels) between the bicubically up-sampled, cropped x and target.
-    `out` as in cosine_feature_loss."""
+    `out`, `groups` and `mask` (uint8 [groups, OH-2crop, OW-2crop]: of the up-sampled, cropped pixels) as in cosine_feature_loss."""
+    if mask is not None:
+        loss, cos = MaskedUpsampledCosineLoss.apply(x, target, mask, int(size[0]), int(size[1]), int(crop), int(groups), out)
+        return (loss, cos) if return_cos else loss
+    G = _groups_of(x.shape[-3], groups, "upsampled_cosine_loss")
+    if G > 1 and out is not None:
+        raise ValueError("nefes_amd: upsampled_cosine_loss: `out` takes the kernel's own value; with groups > 1 and no mask the sum over "
+                         "the groups is formed after it")
     loss, cos = UpsampledCosineLoss.apply(x, target, int(size[0]), int(size[1]), int(crop), out)
+    if G > 1:
+        loss = loss * float(G)
     return (loss, cos) if return_cos else loss
 
 
@@ -1849,11 +1989,56 @@ class PixelCosineLoss(torch.autograd.Function):
         return g_a.reshape(ctx.shape), None, None, None
 
 
-def pixel_cosine_loss(a, b, groups=1, return_cos=False, out=None):
+class MaskedPixelCosineLoss(torch.autograd.Function):
+    """masked_feature_loss (dm/DFM_pose_refine.py:257-288) with per_pixel=True: PixelCosineLoss with the mean over each group's VALID
+    pixels (uint8 mask [G, pixels]); a group without one gives NaN, as the reference's mean of an empty tensor."""
+
+    @staticmethod
+    def forward(ctx, a, b, mask, groups, out=None):
+        G = _groups_of(a.shape[0], groups, "pixel_cosine_loss")
+        Cc = a.shape[0] // G
+        af, bf = _f32(a).reshape(G, Cc, -1), _f32(b).reshape(G, Cc, -1)
+        if af.shape != bf.shape:
+            raise ValueError(f"nefes_amd: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
+        mk = _loss_mask(mask, G, a.shape[1:], af.device, "pixel_cosine_loss")
+        lib = L.load()
+        P = af.shape[2]
+        scratch = torch.empty(lib.nefes_pixcos_masked_scratch_doubles(G, P), dtype=torch.float64, device=af.device)
+        loss = _loss_buffer(out, af.device)
+        with _timed("pixcos_loss_masked_fwd"):
+            L.check(lib.nefes_pixcos_loss_masked_fwd(G, Cc, P, _chk(af, "a"), _chk(bf, "b"), _chk(mk, "mask", torch.uint8),
+                                                     _chk(scratch, "scratch", torch.float64), _chk(loss, "loss"), _stream()),
+                    "nefes_pixcos_loss_masked_fwd")
+        ctx.save_for_backward(af, bf, mk, scratch)
+        ctx.shape = a.shape
+        cos = scratch[:G]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(cos)
+        return loss, cos
+
+    @staticmethod
+    def backward(ctx, g, _g_cos):
+        if g is None:
+            return (None,) * 5
+        af, bf, mk, scratch = ctx.saved_tensors
+        gf = _f32(g).reshape(1)
+        g_a = torch.empty_like(af)
+        with _timed("pixcos_loss_masked_bwd"):
+            L.check(L.load().nefes_pixcos_loss_masked_bwd(af.shape[0], af.shape[1], af.shape[2], _chk(af, "a"), _chk(bf, "b"),
+                                                          _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
+                                                          _chk(gf, "g_loss"), _chk(g_a, "g_a"), _stream()), "nefes_pixcos_loss_masked_bwd")
+        return g_a.reshape(ctx.shape), None, None, None, None
+
+
+def pixel_cosine_loss(a, b, groups=1, return_cos=False, out=None, mask=None):
     """The per-pixel feature loss (`--per_pixel`): a, b [groups * C, ...]; per group 1 - mean over pixels of the cosine similarity over
     its C channels (torch.nn.CosineSimilarity(dim=0, eps=1e-6)), summed over the groups -- every group's value and gradient are what a
     call on that group alone gives.  `return_cos` adds the per-group mean cosines (float64, no gradient); `out` as in
-    cosine_feature_loss."""
+    cosine_feature_loss.  `mask`: uint8 [groups, ...pixels]; the mean is over the group's pixels with mask != 0 (values at the others are
+    never read, their gradient is exactly 0); None: today's unmasked kernels."""
+    if mask is not None:
+        loss, cos = MaskedPixelCosineLoss.apply(a, b, mask, groups, out)
+        return (loss, cos) if return_cos else loss
     loss, cos = PixelCosineLoss.apply(a, b, groups, out)
     return (loss, cos) if return_cos else loss
 
@@ -1903,8 +2088,61 @@ class UpsampledPixelCosineLoss(torch.autograd.Function):
         return g_x.reshape(shape), None, None, None, None, None, None
 
 
-def upsampled_pixel_cosine_loss(x, target, size, crop=0, groups=1, return_cos=False, out=None):
-    """pixel_cosine_loss of the bicubically up-sampled, cropped x against target, one pass each way.  `out` as in cosine_feature_loss."""
+class MaskedUpsampledPixelCosineLoss(torch.autograd.Function):
+    """UpsampledPixelCosineLoss with a uint8 mask [G, OH-2crop, OW-2crop] of the up-sampled, cropped pixels (MaskedPixelCosineLoss of the
+    up-sampled image without the up-sampled image)."""
+
+    @staticmethod
+    def forward(ctx, x, target, mask, OH, OW, crop, groups, out=None):
+        xf = _f32(x)
+        GC, h, w = xf.shape[-3:]
+        G = int(groups)
+        if G < 1 or GC % G or xf.numel() != GC * h * w:
+            raise ValueError(f"nefes_amd: features {tuple(x.shape)} do not split into {groups} groups of [C,h,w] maps")
+        CH, CW = OH - 2 * crop, OW - 2 * crop
+        xf = xf.reshape(GC, h, w)
+        tf = _f32(target).reshape(GC, CH, CW)
+        mk = _loss_mask(mask, G, (CH, CW), xf.device, "upsampled_pixel_cosine_loss")
+        lib = L.load()
+        scratch = torch.empty(lib.nefes_uppixcos_masked_scratch_doubles(G, OH, OW, crop), dtype=torch.float64, device=xf.device)
+        loss = _loss_buffer(out, xf.device)
+        with _timed("uppixcos_loss_masked_fwd"):
+            L.check(lib.nefes_uppixcos_loss_masked_fwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
+                                                       _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
+                                                       _chk(loss, "loss"), _stream()), "nefes_uppixcos_loss_masked_fwd")
+        ctx.save_for_backward(xf, tf, mk, scratch)
+        ctx.cfg = (x.shape, OH, OW, crop, G)
+        cos = scratch[:G]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(cos)
+        return loss, cos
+
+    @staticmethod
+    def backward(ctx, g, _g_cos):
+        if g is None:
+            return (None,) * 8
+        xf, tf, mk, scratch = ctx.saved_tensors
+        shape, OH, OW, crop, G = ctx.cfg
+        GC, h, w = xf.shape
+        gf = _f32(g).reshape(1)
+        tmp = torch.empty(GC, OH - 2 * crop, w, device=xf.device)
+        g_x = torch.empty_like(xf)
+        (fx, cx, wx, T), (fy, cy, wy, _) = bicubic_gather_tables(h, w, OH, OW, crop, xf.device)
+        with _timed("uppixcos_loss_masked_bwd"):
+            L.check(L.load().nefes_uppixcos_loss_masked_bwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
+                                                            _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
+                                                            _chk(gf, "g_loss"), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), fy.data_ptr(),
+                                                            cy.data_ptr(), wy.data_ptr(), T, _chk(tmp, "tmp"), _chk(g_x, "g_x"), _stream()),
+                    "nefes_uppixcos_loss_masked_bwd")
+        return (g_x.reshape(shape),) + (None,) * 7
+
+
+def upsampled_pixel_cosine_loss(x, target, size, crop=0, groups=1, return_cos=False, out=None, mask=None):
+    """pixel_cosine_loss of the bicubically up-sampled, cropped x against target, one pass each way.  `out` as in cosine_feature_loss;
+    `mask` (uint8 [groups, OH-2crop, OW-2crop]: of the up-sampled, cropped pixels) as in pixel_cosine_loss."""
+    if mask is not None:
+        loss, cos = MaskedUpsampledPixelCosineLoss.apply(x, target, mask, int(size[0]), int(size[1]), int(crop), int(groups), out)
+        return (loss, cos) if return_cos else loss
     loss, cos = UpsampledPixelCosineLoss.apply(x, target, int(size[0]), int(size[1]), int(crop), int(groups), out)
     return (loss, cos) if return_cos else loss
 

@@ -42,6 +42,38 @@ def feature_loss(feature_rgb, feature_target, img_in=True, per_pixel=False):
     return 1 - cos(feature_rgb, feature_target).mean()
 
 
+def masked_feature_loss(feature_rgb, feature_target, mask, img_in=True, per_pixel=False):
+    """dm/DFM_pose_refine.py:257-288 (`--semantic`): feature_loss over the pixels with mask > 0 only -- in SELECT form: the reference
+    compacts both maps with torch.nonzero (a host read, and shapes that change per image: nothing a captured loop can replay); here the
+    masked-out pixels are replaced by zeros, which add nothing to the three sums of a channel (per channel: the same value), and the
+    per-pixel mean is sum_p m_p cos_p / sum_p m_p.  Values at masked-out pixels never reach the result or a gradient (torch.where
+    selects, forward and backward).  No valid pixel: 1 per channel-wise (every cosine is 0 / eps^2), NaN per pixel (0 / 0), as the
+    reference.  mask: [1,H,W], [H,W] or flat, any dtype."""
+    if img_in:
+        C = feature_rgb.shape[0]
+        feature_rgb, feature_target = feature_rgb.reshape(C, -1), feature_target.reshape(C, -1)
+    valid = (mask.reshape(1, -1) > 0).to(feature_rgb.device)
+    fr = torch.where(valid, feature_rgb, torch.zeros((), dtype=feature_rgb.dtype, device=feature_rgb.device))
+    ft = torch.where(valid, feature_target, torch.zeros((), dtype=feature_target.dtype, device=feature_target.device))
+    if not per_pixel:
+        return 1 - nn.CosineSimilarity(dim=1, eps=1e-6)(fr, ft).mean()
+    cos = nn.CosineSimilarity(dim=0, eps=1e-6)(fr, ft)
+    cos = torch.where(valid[0], cos, torch.zeros((), dtype=cos.dtype, device=cos.device))
+    return 1 - cos.sum() / valid.sum().to(cos.dtype)
+
+
+def full_resolution_mask(mask_lowres, size, crop=10):
+    """The loader's (H/ts, W/ts) mask of static pixels in the form the `upsample=True` loop compares at: nearest-neighbour up-sampling
+    to size = (H, W), `crop` pixels dropped on every side, thresholded (> 0) to uint8 [H-2crop, W-2crop] (a leading batch dimension is
+    kept).  Plain torch, once per image."""
+    H, W = int(size[0]), int(size[1])
+    m = torch.as_tensor(mask_lowres)
+    lead = m.shape[:-2]
+    m = (m.reshape((-1, 1) + tuple(m.shape[-2:])) > 0).float()
+    m = nn.functional.interpolate(m, size=(H, W), mode="nearest")[:, 0, crop:H - crop, crop:W - crop]
+    return (m > 0).to(torch.uint8).reshape(tuple(lead) + tuple(m.shape[-2:])).contiguous()
+
+
 HIP_SVD_REG = os.environ.get("NEFES_HIP_SVD_REG", "1") != "0"
 
 
@@ -102,7 +134,11 @@ class PoseRefiner:
     the optimizer is Adam(lr=`learning_rate`) over a deep copy of that network per image (:209-212), and `refine_apr` returns what
     `DFM_post_processing` records for the image: the refined network's pose, or the initial one when the verification step
     finds PSNR or SSIM of the up-sampled render lower after the loop than before (:233-250).  The network itself is the
-    caller's (a CNN outside this path); implies `upsample=True`."""
+    caller's (a CNN outside this path); implies `upsample=True`.
+
+    `masked=True` is the reference's `--semantic` (masked_feature_loss, dm/DFM_pose_refine.py:257-288): the feature loss runs over the
+    pixels of the image's mask that are > 0 -- `refine(..., mask=)` / `refine_apr(..., mask=)`, in the target's spatial shape -- on the
+    masked loss kernels, in every form of the loop; no mask given means all valid."""
 
     FUSED_UPSAMPLED_LOSS = True      # False: bicubic up-sampling and cosine loss as separate kernels (the tests compare the two)
     # The loop's target is fixed for all iterations of an image: its share of the up-sampled loss (Uy^T target Ux, |target|^2) is
@@ -121,7 +157,7 @@ class PoseRefiner:
     def __init__(self, render_kwargs, args, hwf, near, far, tinyscale=4, lr_r=0.01, lr_t=0.1, lietorch=False,
                  upsample=False, per_pixel=False, world_setup=None, graph=True, device="cuda", adam_capturable=None,
                  fused_glue=True, images=1, pose_model=None, svd_reg=False, learning_rate=1e-5, bn_running_stats=True,
-                 intrinsics=None, learn_focal=False, lr_f=1e-3):
+                 intrinsics=None, learn_focal=False, lr_f=1e-3, masked=False):
         self.kw, self.args = dict(render_kwargs), args
         # False: FusionNet's train-mode BatchNorm leaves its running statistics and batch counter alone in this refiner's iterations
         # (nothing in the loop reads them; the reference never puts the net in eval mode).  REQUIRED for refiners that share a
@@ -190,6 +226,13 @@ class PoseRefiner:
         self.target = torch.zeros(self.C, th, tw, device=self.dev) if self.B == 1 else torch.zeros(self.B, self.C, th, tw, device=self.dev)
         self.hist = torch.zeros(self.B, 10, device=self.dev)
         self.loss = torch.zeros((), device=self.dev) if self.B == 1 else torch.zeros(self.B, device=self.dev)
+        # masked (`--semantic`, masked_feature_loss): the feature loss runs over the pixels of self.mask that are != 0 -- ONE persistent
+        # uint8 buffer [B, th, tw] (the target's spatial shape, one plane per image shared by its channels) that the masked loss kernels
+        # read in place on every iteration: a captured graph follows refine(..., mask=) from image to image.  The routes are the masked
+        # ones from construction on (all ones until a mask is given), and there is no prepared-target form of them
+        # (_uses_prepared_target), so what is captured does not depend on the images.
+        self.masked = bool(masked)
+        self.mask = torch.ones(self.B, th, tw, dtype=torch.uint8, device=self.dev) if self.masked else None
         self._affine = None            # static [1,12] buffer with the image's colour transform when the exposure network is frozen
         self.graph, self.apr_graph = None, None
 
@@ -275,6 +318,8 @@ class PoseRefiner:
         B = self.B
         out = self.loss if (B == 1 and self.fused_glue) else None
         fused = self._fused()
+        if self.masked:
+            return self._masked_loss(fused, out)
         if self.upsample and self.fused_glue and not self.per_pixel and self.FUSED_UPSAMPLED_LOSS:
             # up-sampling, crop and feature loss in one pass each way: the 34 MB up-sampled image is never written (ops.upsampled_cosine_loss)
             if self._uses_prepared_target():
@@ -316,6 +361,54 @@ class PoseRefiner:
             loss = feature_loss(fused, self.target, per_pixel=self.per_pixel)
         return loss, loss.detach()
 
+    def _masked_loss(self, fused, out):
+        """_loss's last step with self.mask (PoseRefiner(masked=True)): the masked one-pass kernels of the form the loop runs (up-sampled
+        or not, per pixel or per channel; `groups=B`: the kernels' value is already the sum over the images), or with fused_glue=False
+        the torch expression (masked_feature_loss).  self.target and self.mask are read on every iteration."""
+        B, C = self.B, self.C
+        if not self.fused_glue:
+            if self.upsample:
+                fused = ops.bicubic_upsample(fused, (self.H, self.W))[:, :, 10:-10, 10:-10]
+            loss = masked_feature_loss(fused[0], self.target, self.mask, per_pixel=self.per_pixel)
+            return loss, loss.detach()
+        if self.upsample and self.FUSED_UPSAMPLED_LOSS:
+            op = ops.upsampled_pixel_cosine_loss if self.per_pixel else ops.upsampled_cosine_loss
+            loss, cos = op(fused.reshape(B * C, self.h, self.w), self.target.reshape(B * C, self.H - 20, self.W - 20), (self.H, self.W), crop=10,
+                           groups=B, return_cos=True, out=out, mask=self.mask)
+        else:
+            if self.upsample:
+                fused = ops.bicubic_upsample(fused, (self.H, self.W), crop=10)
+            op = ops.pixel_cosine_loss if self.per_pixel else ops.cosine_feature_loss
+            loss, cos = op(fused.reshape(B * C, -1), self.target.reshape(B * C, -1), groups=B, return_cos=True, out=out,
+                           mask=self.mask.view(B, -1))
+        if B == 1:
+            return loss, loss.detach()
+        return loss, (1.0 - (cos if self.per_pixel else cos.view(B, C).mean(1))).float()
+
+    def _set_mask(self, mask):
+        """The image's validity mask into self.mask, IN PLACE (a captured iteration keeps reading the same buffer): thresholded `> 0`
+        once, from bool / uint8 / float, [th,tw] or [1,th,tw] (images=B: [B,th,tw] or [B,1,th,tw]); None: all valid.  An image without
+        a valid pixel is refused here -- one host read per call, outside the loop."""
+        if not self.masked:
+            if mask is not None:
+                raise ValueError("nefes_amd: this PoseRefiner was built without a mask buffer; construct it with PoseRefiner(..., masked=True) "
+                                 "to pass mask=")
+            return
+        with torch.no_grad():
+            if mask is None:
+                self.mask.fill_(1)
+                return
+            m = torch.as_tensor(mask)
+            th, tw = self.mask.shape[1:]
+            if tuple(m.shape) not in ({(th, tw), (1, th, tw), (1, 1, th, tw)} if self.B == 1 else {(self.B, th, tw), (self.B, 1, th, tw)}):
+                raise ValueError(f"nefes_amd: the mask has shape {tuple(m.shape)}; this refiner compares at {(th, tw)} "
+                                 f"({self.B} image(s): one plane each; refine.full_resolution_mask makes the up-sampled, cropped form)")
+            m = (m.to(self.dev) > 0).reshape(self.mask.shape)
+            empty = (~m.reshape(self.B, -1).any(1)).nonzero().flatten().tolist()
+            if empty:
+                raise ValueError(f"nefes_amd: the mask of image(s) {empty} has no valid pixel (mask > 0): nothing to refine against")
+            self.mask.copy_(m)
+
     def _ensure_upcos(self):
         """self._upcos (ops.UpcosTarget) with the target buffer's shape, built when there is none or the shape moved -- never under
         capture: its set-up launches would be replayed with every iteration."""
@@ -345,6 +438,8 @@ class PoseRefiner:
         the Gram kernel's LDS (ops.UpcosTarget.fits, known once the buffers exist); otherwise the one-pass kernels, which read
         self.target itself on every iteration."""
         if not (self.upsample and self.fused_glue and not self.per_pixel and self.FUSED_UPSAMPLED_LOSS and self.PREPARED_TARGET):
+            return False
+        if self.masked:                                    # sum_p m_p up_p^2 does not separate into the two axes: no Gram form
             return False
         return bool(self._ensure_upcos().fits)
 
@@ -384,7 +479,8 @@ class PoseRefiner:
             else:
                 self._affine.copy_(a)
 
-    def _reset(self, init_c2w, feature_target, hist):
+    def _reset(self, init_c2w, feature_target, hist, mask=None):
+        self._set_mask(mask)
         with torch.no_grad():
             self.model.r.zero_()
             self.model.t.zero_()
@@ -414,7 +510,8 @@ class PoseRefiner:
         """The _Mode record of `refine` (mode 3) or, apr=True, of `refine_apr` (mode 2) on this refiner."""
         first_use = lambda m: self.use_graph and getattr(self, m.slot) is None
         if not apr:
-            return _Mode(False, on_device=lambda job: tuple(t.to(self.dev) for t in job), set_state=self._reset, iteration=self._iteration,
+            return _Mode(False, on_device=lambda job: tuple(t if t is None else t.to(self.dev) for t in job), set_state=self._reset,
+                         iteration=self._iteration,
                          prepare=lambda m, job: first_use(m) and self._run(m, job, iters=0), read=self._refined_pose,
                          read_own=self._refined_pose,
                          finish=lambda pose, _, __, losses: ((pose, losses) if self.log_f is None
@@ -485,10 +582,19 @@ class PoseRefiner:
             self._step(m, i, iters, losses, checks)
         return m.finish(m.read(), before, checks, losses)
 
-    def refine(self, init_c2w, feature_target, hist, iters=50):
+    def _job(self, *job, mask=None):
+        """The job tuple of an image: with a fourth element, its mask, on a masked refiner (None: all valid)."""
+        if not self.masked:
+            self._set_mask(mask)                           # (raises for mask= on an unmasked refiner)
+            return job
+        return job + (None if mask is None else torch.as_tensor(mask),)
+
+    def refine(self, init_c2w, feature_target, hist, iters=50, mask=None):
         """One image (images=1): (refined 4x4 c2w, losses [iters]) -- with learn_focal (refined c2w, losses, log_f [1]).
-        A batch (images=B): init_c2w [B,4,4], feature_target [B,C,h,w], hist [B,10] -> (refined poses [B,4,4], losses [iters,B]), each image as if refined alone."""
-        return self._run(self._mode(), (init_c2w, feature_target, hist), iters)
+        A batch (images=B): init_c2w [B,4,4], feature_target [B,C,h,w], hist [B,10] -> (refined poses [B,4,4], losses [iters,B]), each image as if refined alone.
+        mask (PoseRefiner(masked=True)): the image's valid pixels, > 0, in the target's spatial shape [th,tw] or [1,th,tw] (a batch:
+        [B,th,tw]); None: all valid."""
+        return self._run(self._mode(), self._job(init_c2w, feature_target, hist, mask=mask), iters)
 
     refine_batch = refine
 
@@ -529,10 +635,12 @@ class PoseRefiner:
             pose = (self.apr if net is None else net)(self.photo).reshape(1, 3, 4)
             return (svd_reg(pose) if self.svd_reg else pose)[0]
 
-    def _apr_image_state(self, photo, feature_target, hist):
+    def _apr_image_state(self, photo, feature_target, hist, mask=None):
         """Per-image state of train_on_batch, written IN PLACE (a captured iteration keeps reading the same buffers): the query image, its
-        cropped features (:125), a fresh copy of the regression network (:209), the histogram and the colour transform's twelve numbers."""
+        cropped features (:125), a fresh copy of the regression network (:209), the histogram and the colour transform's twelve numbers;
+        on a masked refiner the image's mask of the cropped pixels."""
         dev = self.dev
+        self._set_mask(mask)
         with torch.no_grad():
             self.photo.copy_(photo.to(dev).reshape(self.photo.shape))
             self.target.copy_(feature_target.to(dev).reshape(self.C, self.H, self.W)[:, 10:-10, 10:-10])
@@ -545,8 +653,8 @@ class PoseRefiner:
             self.hist.copy_(hist.to(dev).reshape(1, 10))
             self._exposure_into_affine()
 
-    def _apr_set_state(self, photo, feature_target, hist):
-        self._apr_image_state(photo, feature_target, hist)
+    def _apr_set_state(self, photo, feature_target, hist, mask=None):
+        self._apr_image_state(photo, feature_target, hist, mask)
         self._apr_fresh_adam()
 
     def _apr_iteration(self):
@@ -581,12 +689,14 @@ class PoseRefiner:
                 pose = first
         return pose.detach().clone(), losses, info
 
-    def refine_apr(self, photo, feature_target, hist, iters=50, verification=True):
+    def refine_apr(self, photo, feature_target, hist, iters=50, verification=True, mask=None):
         """One query image, `pose_only=2`: `photo` [1,3,H,W], `feature_target` [C,H,W] (the query image's features at full
         resolution; cropped here as :125 does).  Returns (pose [3,4] in the regression network's coordinates, losses [iters],
         info = dict(psnr=(first, last), ssim=(first, last), retreat=bool)).  PoseRefiner(graph=True): the iteration is captured on
-        first use and replayed (the regression network must be capturable: no host reads, static shapes)."""
-        return self._run(self._mode(apr=True, verification=verification), (photo, feature_target, hist), iters)
+        first use and replayed (the regression network must be capturable: no host reads, static shapes).
+        mask (PoseRefiner(masked=True)): the valid pixels of the CROPPED full-resolution image, [H-20, W-20] (full_resolution_mask);
+        the verification step's PSNR / SSIM stay unmasked, as in the reference."""
+        return self._run(self._mode(apr=True, verification=verification), self._job(photo, feature_target, hist, mask=mask), iters)
 
 
 def _camera_buffer(intrinsics, B, device):
@@ -650,7 +760,7 @@ def _zero_optimizer_state(opt):
                     v.zero_()
 
 
-def _apr_kernels_bit_stable(r, photo, feature_target, hist, trials=6):
+def _apr_kernels_bit_stable(r, photo, feature_target, hist, mask=None, trials=6):
     """EMPIRICAL guard for refine_apr_concurrently.  The regression network, its backward, torch's Adam and the verification step are the
     CALLER'S / torch's kernels; next to another stream's field kernels such code is exposed to the packed-fp32 finding of DESIGN.md 4.7
     (hipcc vectorises torch's kernels the way it vectorised ours) -- whether a given network's kernels contain the affected forms cannot be
@@ -673,7 +783,7 @@ def _apr_kernels_bit_stable(r, photo, feature_target, hist, trials=6):
     side = torch.cuda.Stream(device=dev)
 
     def run(storm):
-        r._apr_set_state(photo, feature_target, hist)
+        r._apr_set_state(photo, feature_target, hist, mask)
         torch.cuda.synchronize(dev)
         keep = []
         if storm:
@@ -781,7 +891,8 @@ def refine_concurrently(refiners, jobs, iters=50):
     fraction of the CUs: alone on the device those 0.3 ms are idle silicon, next to another image's field kernels they are nearly
     free (two images: -8 % per image; tools/two_streams.py).  Every image walks exactly the trajectory it walks alone -- bit for bit
     (tests/test_gpu_streams.py; that test is also what found the packed-fp32 op_sel instruction of DESIGN.md 4.7).
-    jobs = [(init_c2w, feature_target, hist), ...] as PoseRefiner.refine takes them -> [(refined c2w, losses [iters]), ...] in job order.
+    jobs = [(init_c2w, feature_target, hist), ...] as PoseRefiner.refine takes them -> [(refined c2w, losses [iters]), ...] in job order;
+    a job for a PoseRefiner(masked=True) may carry the image's mask as a fourth element.
     More jobs than refiners: rounds of len(refiners) images (the last one smaller).
     Refiners that share a FusionNet are constructed with bn_running_stats=False, and every refiner runs on the library's own kernels
     (_check_concurrent refuses anything else: see there)."""
@@ -791,7 +902,8 @@ def refine_concurrently(refiners, jobs, iters=50):
 def refine_apr_concurrently(refiners, jobs, iters=50, verification=True, verify_kernels=True):
     """refine_apr for K query images at the same time (the shipped default mode, `pose_only = 2`): one PoseRefiner(pose_model=...) and
     one HIP stream per image, iterations replayed round-robin like refine_concurrently.  jobs = [(photo, feature_target, hist), ...] ->
-    [(pose [3,4], losses [iters], info), ...] in job order, each identical to what refine_apr returns for that image alone.
+    [(pose [3,4], losses [iters], info), ...] in job order, each identical to what refine_apr returns for that image alone; a fourth
+    element of a job is the image's mask (PoseRefiner(masked=True)).
     The regression network's kernels are the caller's: `verify_kernels` first TRIES them next to this library's field kernels
     (_apr_kernels_bit_stable) and raises if a result moves -- run such a network's images one after the other (refine_apr)."""
     def guard(refiners, jobs):

@@ -4,7 +4,8 @@ iteration is a replayed graph in production, so each of them costs its ~4 us of 
 source line that asked for them.  python tools/loop_ops.py [mode]
 With --launches, instead: the count of every device kernel, autograd Function and HIP runtime call of that iteration (the launch census
 two revisions of the host code are compared by: profiles/refine_one_loop/README.md).  python tools/loop_ops.py [mode] --launches
---per-pixel: the refiner is built with per_pixel=True (the reference's `--per_pixel` feature loss; profiles/per_pixel_loss/README.md)."""
+--per-pixel: the refiner is built with per_pixel=True (the reference's `--per_pixel` feature loss; profiles/per_pixel_loss/README.md).
+--masked: the refiner is built with masked=True (the masked feature loss, all pixels valid; profiles/masked_loss/README.md)."""
 import os, sys, collections
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,7 +13,10 @@ from torch.profiler import profile, ProfilerActivity
 import bench
 from nefes_amd import refine as R
 
-argv = [a for a in sys.argv[1:] if a not in ("--launches", "--per-pixel")]
+argv = [a for a in sys.argv[1:] if a not in ("--launches", "--per-pixel", "--masked")]
+if "--masked" in sys.argv[1:]:
+    import functools
+    R.PoseRefiner.__init__ = functools.partialmethod(R.PoseRefiner.__init__, masked=True)
 if "--per-pixel" in sys.argv[1:]:
     import functools
     R.PoseRefiner.__init__ = functools.partialmethod(R.PoseRefiner.__init__, per_pixel=True)
