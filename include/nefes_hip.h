@@ -134,6 +134,22 @@ int nefes_raygen_k_fwd(int H, int W, const float* intr, const float* c2w, int ro
 size_t nefes_raygen_k_bwd_workspace(int n_rays);
 int nefes_raygen_k_bwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, const float* g_rays_o,
                        const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr, void* stream);
+/* The same rays at a LIST of pixels instead of the frame's grid.  px: dev, float32 [n, 2] rows (x, y) = (column, row) in get_rays' own
+ * pixel convention -- an integer coordinate is that pixel, there is no half-pixel offset; fractional coordinates and points outside the
+ * frame are legal.  px and intr are both read from device memory when the kernel runs.  Outputs dev [n, 3].  The arithmetic per ray is
+ * nefes_raygen_k_fwd's operation for operation (one kernel body): with px the row-major integer pixels of rows [row0, row0+nrows) the
+ * rays and the 12 + 4 gradient numbers equal nefes_raygen_k_fwd / _bwd's bit for bit.  backward: as nefes_raygen_k_bwd (g_* and g_intr
+ * may be NULL); workspace: dev, >= nefes_raygen_px_bwd_workspace(n) bytes (= nefes_raygen_k_bwd_workspace(n)). */
+int nefes_raygen_px_fwd(int n, const float* px, const float* intr, const float* c2w, float* rays_o, float* rays_d, float* viewdirs,
+                        void* stream);
+size_t nefes_raygen_px_bwd_workspace(int n);
+int nefes_raygen_px_bwd(int n, const float* px, const float* intr, const float* c2w, const float* g_rays_o, const float* g_rays_d,
+                        const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr, void* stream);
+/* Bilinear sample of map [C, H, W] (dev) at the same kind of list: out [C, n] (dev), channel-major as the feature-loss kernels read it.
+ * (x, y) is clamped to [0, W-1] x [0, H-1] before the split into cell and fraction, and the second tap's index to the last column /
+ * row: at an integer coordinate the result is the map's value exactly, and nothing outside the map is read for any input.  Forward
+ * only (it samples targets). */
+int nefes_sample_px(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream);
 /* ndc_rays (:27-44) and its backward to (rays_o, rays_d). */
 int nefes_ndc_fwd(int H, int W, float focal, float near, int n, const float* rays_o, const float* rays_d, float* out_o,
                   float* out_d, void* stream);

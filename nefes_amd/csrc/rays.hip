@@ -120,20 +120,42 @@ extern "C" int nefes_raygen_bwd(int H, int W, float focal, const float* c2w, int
 // iteration follows a camera that is updated in place between replays, and the backward can hand a gradient to it.  With
 // intr = (focal, focal, (float)(W*.5), (float)(H*.5)) every operation below is the one the focal kernels above perform, in the
 // same order, so rays and the twelve pose sums are theirs bit for bit.
-__device__ __forceinline__ void pixel_dir_k(const float* __restrict__ intr, int row, int col, float (&dc)[3]) {
-    // dirs = [(i - cx)/fx, -(j - cy)/fy, -1]
-    dc[0] = __fdiv_rn(__fsub_rn((float)col, intr[2]), intr[0]);
-    dc[1] = -__fdiv_rn(__fsub_rn((float)row, intr[3]), intr[1]);
+//
+// Where ray idx's pixel (x, y) = (column, row) comes from -- the per-ray bodies below are written once over it:
+//   GridPixels: the frame's rows from row0 on, row-major (raygen_k);
+//   ListPixels: a float32 [n, 2] list in device memory, read when the kernel runs like the camera (raygen_px).  Any value is legal:
+//               an integer coordinate is that pixel (no half-pixel offset), fractions and points outside the frame are rays too.
+struct GridPixels {
+    int W, row0;
+    __device__ __forceinline__ void operator()(int idx, float& x, float& y) const {
+        x = (float)(idx % W);
+        y = (float)(row0 + idx / W);
+    }
+};
+struct ListPixels {
+    const float* px;
+    __device__ __forceinline__ void operator()(int idx, float& x, float& y) const {
+        x = px[(size_t)idx * 2];
+        y = px[(size_t)idx * 2 + 1];
+    }
+};
+
+__device__ __forceinline__ void pixel_dir_k(const float* __restrict__ intr, float x, float y, float (&dc)[3]) {
+    // dirs = [(x - cx)/fx, -(y - cy)/fy, -1]
+    dc[0] = __fdiv_rn(__fsub_rn(x, intr[2]), intr[0]);
+    dc[1] = -__fdiv_rn(__fsub_rn(y, intr[3]), intr[1]);
     dc[2] = -1.f;
 }
 
-__global__ __launch_bounds__(256) void raygen_k_fwd_kernel(int W, const float* __restrict__ intr, const float* __restrict__ c2w,
-                                                           int row0, int n, float* rays_o, float* rays_d, float* viewdirs) {
+template <class Pixels>
+__global__ __launch_bounds__(256) void raygen_k_fwd_kernel(Pixels pixel, const float* __restrict__ intr, const float* __restrict__ c2w,
+                                                           int n, float* rays_o, float* rays_d, float* viewdirs) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= n) return;
-    const int row = row0 + idx / W, col = idx % W;
+    float x, y;
+    pixel(idx, x, y);
     float dc[3];
-    pixel_dir_k(intr, row, col, dc);
+    pixel_dir_k(intr, x, y, dc);
     float d[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -152,10 +174,11 @@ __global__ __launch_bounds__(256) void raygen_k_fwd_kernel(int W, const float* _
 
 // stage 1: per-block partial of 16 sums (f64) -- the 12 pose-gradient sums of raygen_bwd_kernel, formed exactly as there, then
 // d L/d (fx, fy, cx, cy); stage 2: fixed-order final sum.  With gd the gradient reaching rays_d and R_a column a of the rotation:
-//     d dirs_0 / d fx = -(col - cx)/fx^2 = -dirs_0/fx     d dirs_0 / d cx = -1/fx
-//     d dirs_1 / d fy = +(row - cy)/fy^2 = -dirs_1/fy     d dirs_1 / d cy = +1/fy
-__global__ __launch_bounds__(256) void raygen_k_bwd_kernel(int W, const float* __restrict__ intr, const float* __restrict__ c2w,
-                                                           int row0, int n, const float* g_o, const float* g_d, const float* g_v,
+//     d dirs_0 / d fx = -(x - cx)/fx^2 = -dirs_0/fx     d dirs_0 / d cx = -1/fx
+//     d dirs_1 / d fy = +(y - cy)/fy^2 = -dirs_1/fy     d dirs_1 / d cy = +1/fy
+template <class Pixels>
+__global__ __launch_bounds__(256) void raygen_k_bwd_kernel(Pixels pixel, const float* __restrict__ intr, const float* __restrict__ c2w,
+                                                           int n, const float* g_o, const float* g_d, const float* g_v,
                                                            double* partial) {
     __shared__ double red[4][16];
     double s[16];
@@ -164,9 +187,10 @@ __global__ __launch_bounds__(256) void raygen_k_bwd_kernel(int W, const float* _
     const float fx = intr[0], fy = intr[1];
     const float ifx = __fdiv_rn(1.f, fx), ify = __fdiv_rn(1.f, fy);
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
-        const int row = row0 + idx / W, col = idx % W;
+        float x, y;
+        pixel(idx, x, y);
         float dc[3];
-        pixel_dir_k(intr, row, col, dc);
+        pixel_dir_k(intr, x, y, dc);
         float gd[3] = {0.f, 0.f, 0.f};
         if (g_d)
 #pragma unroll
@@ -217,14 +241,29 @@ __global__ void raygen_k_bwd_final(const double* partial, int nblocks, float* g_
     else if (g_intr) g_intr[k - 12] = (float)s;
 }
 
+template <class Pixels>
+static int raygen_k_fwd_launch(Pixels pixel, const float* intr, const float* c2w, int n, float* rays_o, float* rays_d, float* viewdirs,
+                               void* stream) {
+    hipLaunchKernelGGL(raygen_k_fwd_kernel<Pixels>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pixel, intr, c2w, n,
+                       rays_o, rays_d, viewdirs);
+    return (int)hipGetLastError();
+}
+template <class Pixels>
+static int raygen_k_bwd_launch(Pixels pixel, const float* intr, const float* c2w, int n, const float* g_rays_o, const float* g_rays_d,
+                               const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr, void* stream) {
+    const int nb = raygen_blocks(n);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(raygen_k_bwd_kernel<Pixels>, dim3(nb), dim3(256), 0, st, pixel, intr, c2w, n, g_rays_o, g_rays_d, g_viewdirs,
+                       (double*)workspace);
+    hipLaunchKernelGGL(raygen_k_bwd_final, dim3(1), dim3(64), 0, st, (const double*)workspace, nb, g_c2w, g_intr);
+    return (int)hipGetLastError();
+}
+
 extern "C" int nefes_raygen_k_fwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, float* rays_o,
                                   float* rays_d, float* viewdirs, void* stream) {
     if (!intr || !c2w || !rays_o || !rays_d || H <= 0 || W <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > H)
         return NEFES_E_BADARG;
-    const int n = nrows * W;
-    hipLaunchKernelGGL(raygen_k_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, W, intr, c2w, row0, n,
-                       rays_o, rays_d, viewdirs);
-    return (int)hipGetLastError();
+    return raygen_k_fwd_launch(GridPixels{W, row0}, intr, c2w, nrows * W, rays_o, rays_d, viewdirs, stream);
 }
 extern "C" size_t nefes_raygen_k_bwd_workspace(int n_rays) { return (size_t)raygen_blocks(n_rays) * 16 * sizeof(double); }
 extern "C" int nefes_raygen_k_bwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, const float* g_rays_o,
@@ -232,11 +271,51 @@ extern "C" int nefes_raygen_k_bwd(int H, int W, const float* intr, const float* 
                                   void* stream) {
     if (!intr || !c2w || !workspace || !g_c2w || H <= 0 || W <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > H)
         return NEFES_E_BADARG;
-    const int n = nrows * W, nb = raygen_blocks(n);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(raygen_k_bwd_kernel, dim3(nb), dim3(256), 0, st, W, intr, c2w, row0, n, g_rays_o, g_rays_d, g_viewdirs,
-                       (double*)workspace);
-    hipLaunchKernelGGL(raygen_k_bwd_final, dim3(1), dim3(64), 0, st, (const double*)workspace, nb, g_c2w, g_intr);
+    return raygen_k_bwd_launch(GridPixels{W, row0}, intr, c2w, nrows * W, g_rays_o, g_rays_d, g_viewdirs, workspace, g_c2w, g_intr,
+                               stream);
+}
+
+// the same rays and sums at a list of pixels px [n, 2] = (x, y) in device memory (ListPixels)
+extern "C" int nefes_raygen_px_fwd(int n, const float* px, const float* intr, const float* c2w, float* rays_o, float* rays_d,
+                                   float* viewdirs, void* stream) {
+    if (!px || !intr || !c2w || !rays_o || !rays_d || n <= 0) return NEFES_E_BADARG;
+    return raygen_k_fwd_launch(ListPixels{px}, intr, c2w, n, rays_o, rays_d, viewdirs, stream);
+}
+extern "C" size_t nefes_raygen_px_bwd_workspace(int n) { return nefes_raygen_k_bwd_workspace(n); }
+extern "C" int nefes_raygen_px_bwd(int n, const float* px, const float* intr, const float* c2w, const float* g_rays_o,
+                                   const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr,
+                                   void* stream) {
+    if (!px || !intr || !c2w || !workspace || !g_c2w || n <= 0) return NEFES_E_BADARG;
+    return raygen_k_bwd_launch(ListPixels{px}, intr, c2w, n, g_rays_o, g_rays_d, g_viewdirs, workspace, g_c2w, g_intr, stream);
+}
+
+// ---- bilinear sample of a [C, H, W] map at a pixel list (the targets of a sparse feature loss) ----------------------------------
+// out[c, i] = map[c] at px[i] = (x, y), channel-major as the loss kernels read it.  (x, y) is clamped to the frame first, then split
+// into cell and fraction; the second tap's index is clamped to the last column / row, so x = W-1 reads nothing past the row.  Each
+// interpolation is a + f (b - a): at an integer coordinate f = 0 and the value is the map's own, exactly.  A NaN coordinate clamps
+// to 0 (fmaxf returns the other operand): no index leaves the map for any input.
+__global__ __launch_bounds__(256) void sample_px_kernel(int C, int H, int W, const float* __restrict__ map, int n,
+                                                        const float* __restrict__ px, float* out) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)C * n) return;
+    const int i = (int)(t % n);
+    const size_t c = t / n;
+    const float x = fminf(fmaxf(px[(size_t)i * 2], 0.f), (float)(W - 1));
+    const float y = fminf(fmaxf(px[(size_t)i * 2 + 1], 0.f), (float)(H - 1));
+    const int x0 = (int)x, y0 = (int)y;                      // x, y >= 0: truncation is the floor
+    const int x1 = x0 + 1 < W ? x0 + 1 : W - 1, y1 = y0 + 1 < H ? y0 + 1 : H - 1;
+    const float fx = __fsub_rn(x, (float)x0), fy = __fsub_rn(y, (float)y0);
+    const float* m = map + c * (size_t)H * W;
+    const float m00 = m[(size_t)y0 * W + x0], m01 = m[(size_t)y0 * W + x1], m10 = m[(size_t)y1 * W + x0], m11 = m[(size_t)y1 * W + x1];
+    const float top = __fadd_rn(m00, __fmul_rn(fx, __fsub_rn(m01, m00)));
+    const float bot = __fadd_rn(m10, __fmul_rn(fx, __fsub_rn(m11, m10)));
+    out[t] = __fadd_rn(top, __fmul_rn(fy, __fsub_rn(bot, top)));
+}
+extern "C" int nefes_sample_px(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream) {
+    if (!map || !px || !out || C <= 0 || H <= 0 || W <= 0 || n <= 0) return NEFES_E_BADARG;
+    const size_t total = (size_t)C * n;
+    hipLaunchKernelGGL(sample_px_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, C, H, W, map, n, px,
+                       out);
     return (int)hipGetLastError();
 }
 

@@ -96,6 +96,10 @@ SIGNATURES = {
     "nefes_raygen_k_fwd": (_i, [_i, _i, _p, _p, _i, _i, _p, _p, _p, _p]),
     "nefes_raygen_k_bwd_workspace": (_sz, [_i]),
     "nefes_raygen_k_bwd": (_i, [_i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_raygen_px_fwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_raygen_px_bwd_workspace": (_sz, [_i]),
+    "nefes_raygen_px_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "nefes_sample_px": (_i, [_i, _i, _i, _p, _i, _p, _p, _p]),
     "nefes_ndc_fwd": (_i, [_i, _i, _f, _f, _i, _p, _p, _p, _p, _p]),
     "nefes_ndc_bwd": (_i, [_i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_coarse_depths": (_i, [_i, _i, _f, _f, _i, _p, _p, _p, _p]),

@@ -211,6 +211,107 @@ class RayGenK(torch.autograd.Function):
         return g, gk, None, None, None, None
 
 
+def as_pixels(x, device):
+    """A pixel set as the float32 [K, 2] tensor of (x, y) = (column, row) on `device` that the raygen_px / sample_px kernels READ FROM DEVICE
+    MEMORY when they run (a captured graph follows in-place updates of it).  get_rays' own convention: an integer coordinate is that
+    pixel, there is no half-pixel offset; fractional coordinates and points outside the frame are legal.  Forms:
+      - a contiguous float32 [K, 2] tensor already on `device`: used as is -- no copy, no sync, no check of its values;
+      - an integer tensor [K, 2] (any device): converted on its device, no host read;
+      - a host sequence, numpy array or host tensor [K, 2]: converted; the values must be finite.
+    Anything else on a device raises (reading it back to convert it would be a host sync)."""
+    dev = torch.device(device)
+    if torch.is_tensor(x):
+        ok_shape = x.dim() == 2 and x.shape[1] == 2 and x.shape[0] > 0
+        here = x.device.type == dev.type and (dev.index is None or x.device.index == dev.index)
+        if here and x.dtype == torch.float32 and ok_shape and x.is_contiguous():
+            return x
+        integer = not (x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool)
+        if ok_shape and integer:
+            return x.detach().to(dev, torch.float32).contiguous()
+        if x.device.type != "cpu":
+            raise ValueError(f"nefes_amd: pixels on a device must be a contiguous float32 (or an integer) [K, 2] tensor of (x, y) on {dev}; got "
+                             f"{x.dtype} {tuple(x.shape)} on {x.device}")
+    import numpy as np
+    a = np.asarray(x.detach().numpy() if torch.is_tensor(x) else x, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] == 0:
+        raise ValueError(f"nefes_amd: pixels must be [K, 2] rows of (x, y) = (column, row); got shape {a.shape}")
+    if not np.isfinite(a).all():
+        k = int(np.argwhere(~np.isfinite(a))[0][0])
+        raise ValueError(f"nefes_amd: pixel {k} = ({float(a[k, 0])!r}, {float(a[k, 1])!r}) is not finite")
+    return torch.tensor(np.ascontiguousarray(a), dtype=torch.float32, device=dev)
+
+
+def _px(px):
+    if px.dim() != 2 or px.shape[1] != 2 or px.shape[0] == 0:
+        raise RuntimeError(f"nefes_amd: `px` must be [K, 2] rows of (x, y); got {tuple(px.shape)}")
+    return _chk(px.detach(), "px")
+
+
+def raygen_px_fwd(px, intr, c2w):
+    """raygen_k_fwd at the pixel list px (as_pixels) instead of the frame's grid: (rays_o, rays_d, viewdirs), each [K, 3].  px and intr are
+    float32 DEVICE tensors the kernel reads when it runs."""
+    c2w = _f32(c2w[:3, :4])
+    n = px.shape[0]
+    o = torch.empty(n, 3, device=c2w.device)
+    d = torch.empty_like(o)
+    v = torch.empty_like(o)
+    L.check(L.load().nefes_raygen_px_fwd(n, _px(px), _intr(intr), _chk(c2w, "c2w"), _chk(o, "o"), _chk(d, "d"), _chk(v, "v"), _stream()),
+            "nefes_raygen_px_fwd")
+    return o, d, v
+
+
+def raygen_px_bwd(px, intr, c2w, g_o, g_d, g_v, want_intr=True):
+    """-> (g_c2w [3,4], g_intr [4] or None): raygen_k_bwd's 12 + 4 sums over the rays of px."""
+    lib = L.load()
+    c2w = _f32(c2w[:3, :4])
+    n = px.shape[0]
+    ws = torch.empty(lib.nefes_raygen_px_bwd_workspace(n), dtype=torch.uint8, device=c2w.device)
+    g = torch.empty(3, 4, device=c2w.device)
+    gk = torch.empty(4, device=c2w.device) if want_intr else None
+    fix = lambda t: None if t is None else _f32(t)
+    g_o, g_d, g_v = fix(g_o), fix(g_d), fix(g_v)
+    L.check(lib.nefes_raygen_px_bwd(n, _px(px), _intr(intr), _chk(c2w, "c2w"), _chk(g_o, "g_o"), _chk(g_d, "g_d"), _chk(g_v, "g_v"),
+                                    _chk(ws, "ws", torch.uint8), _chk(g, "g_c2w"), _chk(gk, "g_intr"), _stream()), "nefes_raygen_px_bwd")
+    return g, gk
+
+
+class RayGenPx(torch.autograd.Function):
+    """RayGenK at a pixel list: apply(c2w, intr, px) -> (o, d, v), each [K, 3]; backward to the pose and -- when `intr` asks for it -- to
+    (fx, fy, cx, cy).  The pixels are positions, not parameters: no gradient reaches them."""
+
+    @staticmethod
+    def forward(ctx, c2w, intr, px):
+        o, d, v = raygen_px_fwd(px, intr, c2w)
+        ctx.save_for_backward(c2w, intr, px)
+        return o, d, v
+
+    @staticmethod
+    def backward(ctx, g_o, g_d, g_v):
+        c2w, intr, px = ctx.saved_tensors
+        g, gk = raygen_px_bwd(px, intr, c2w, g_o, g_d, g_v, want_intr=ctx.needs_input_grad[1])
+        if not (tuple(c2w.shape) == (3, 4) and c2w.dtype == torch.float32):
+            out = torch.zeros_like(c2w)
+            out[:3, :4] = g
+            g = out
+        return g, gk, None
+
+
+def sample_pixels(map, px, out=None):
+    """Bilinear sample of a [C, H, W] float32 map at the pixel list px (as_pixels): [C, K], channel-major as the feature-loss kernels read
+    it.  Coordinates are clamped to the frame; at an integer coordinate the value is the map's own, exactly.  No gradient (it samples
+    targets).  `out`: a contiguous float32 [C, K] tensor on the map's device that the kernel writes (None: a fresh one)."""
+    if map.dim() != 3:
+        raise RuntimeError(f"nefes_amd: sample_pixels: `map` must be [C, H, W]; got {tuple(map.shape)}")
+    Cc, H, W = (int(v) for v in map.shape)
+    n = px.shape[0]
+    if out is None:
+        out = torch.empty(Cc, n, device=map.device)
+    elif tuple(out.shape) != (Cc, n):
+        raise RuntimeError(f"nefes_amd: sample_pixels: `out` must be [{Cc}, {n}]; got {tuple(out.shape)}")
+    L.check(L.load().nefes_sample_px(Cc, H, W, _chk(map.detach(), "map"), n, _px(px), _chk(out, "out"), _stream()), "nefes_sample_px")
+    return out
+
+
 class NdcRays(torch.autograd.Function):
     """ndc_rays (ray_utils.py:27-44)."""
 

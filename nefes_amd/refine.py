@@ -138,7 +138,14 @@ class PoseRefiner:
 
     `masked=True` is the reference's `--semantic` (masked_feature_loss, dm/DFM_pose_refine.py:257-288): the feature loss runs over the
     pixels of the image's mask that are > 0 -- `refine(..., mask=)` / `refine_apr(..., mask=)`, in the target's spatial shape -- on the
-    masked loss kernels, in every form of the loop; no mask given means all valid."""
+    masked loss kernels, in every form of the loop; no mask given means all valid.
+
+    `sparse=K` is the mode the reference announces as `--sparse_feature` and never built (dm/options.py:131-136): the LearnPose loop over K
+    pixels instead of a frame -- pose -> render(pixels=self.pixels) -> feat_map [K, C] -> [C, K] -> feature loss against the target's
+    features sampled at the same pixels; no colour transform and no FusionNet (the reference's non-fusion branch,
+    DFM_pose_refine.py:330-333, with img_in=False).  `refine(..., pixels=)` takes the [K, 2] points (x, y) of the rendered (h, w) frame
+    (None: K distinct integer pixels drawn with a generator seeded by `seed=`, among the mask's valid ones on a masked refiner);
+    `set_pixels` moves them in place, and a captured iteration follows."""
 
     FUSED_UPSAMPLED_LOSS = True      # False: bicubic up-sampling and cosine loss as separate kernels (the tests compare the two)
     # The loop's target is fixed for all iterations of an image: its share of the up-sampled loss (Uy^T target Ux, |target|^2) is
@@ -157,8 +164,11 @@ class PoseRefiner:
     def __init__(self, render_kwargs, args, hwf, near, far, tinyscale=4, lr_r=0.01, lr_t=0.1, lietorch=False,
                  upsample=False, per_pixel=False, world_setup=None, graph=True, device="cuda", adam_capturable=None,
                  fused_glue=True, images=1, pose_model=None, svd_reg=False, learning_rate=1e-5, bn_running_stats=True,
-                 intrinsics=None, learn_focal=False, lr_f=1e-3, masked=False):
+                 intrinsics=None, learn_focal=False, lr_f=1e-3, masked=False, sparse=None, seed=0):
         self.kw, self.args = dict(render_kwargs), args
+        self.sparse = None if sparse is None else int(sparse)
+        if self.sparse is not None:
+            _refuse_sparse(self.sparse, pose_model, images, upsample, fused_glue, lietorch)
         # False: FusionNet's train-mode BatchNorm leaves its running statistics and batch counter alone in this refiner's iterations
         # (nothing in the loop reads them; the reference never puts the net in eval mode).  REQUIRED for refiners that share a
         # FusionNet and run at the same time (refine_concurrently): the update is a read-modify-write of the shared module's buffers.
@@ -201,8 +211,9 @@ class PoseRefiner:
                 raise NotImplementedError("nefes_amd: learn_focal is built for LearnPose mode with one image (no pose_model=, images=1)")
             if not self.fused_glue or lietorch:
                 raise NotImplementedError("nefes_amd: learn_focal is optimised by ops.FusedAdam (fused_glue=True, lietorch=False)")
-            if intrinsics is None:
-                intrinsics = (self.focal, self.focal, float(self.w * .5), float(self.h * .5))
+        if (learn_focal or self.sparse is not None) and intrinsics is None:
+            # (sparse: the pixel-list ray kernel reads its camera from memory in any case; this is the centred one it would build)
+            intrinsics = (self.focal, self.focal, float(self.w * .5), float(self.h * .5))
         if intrinsics is not None:
             if not self.fused_glue:
                 raise NotImplementedError("nefes_amd: PoseRefiner(intrinsics=...) runs on the fused glue kernels (fused_glue=True)")
@@ -233,6 +244,16 @@ class PoseRefiner:
         # (_uses_prepared_target), so what is captured does not depend on the images.
         self.masked = bool(masked)
         self.mask = torch.ones(self.B, th, tw, dtype=torch.uint8, device=self.dev) if self.masked else None
+        if self.sparse is not None:
+            # sparse: ONE persistent pixel list [K, 2] that the ray kernel reads from memory on every iteration, the target's features
+            # sampled there [C, K] and -- masked -- the mask sampled there (nearest) [1, K]; set_pixels writes all three in place.  The
+            # image's whole feature frame (and mask) is kept for that: self._frame, self._frame_mask.
+            K = self.sparse
+            self.pixels = torch.zeros(K, 2, device=self.dev)
+            self.target = torch.zeros(self.C, K, device=self.dev)
+            self.mask = torch.ones(1, K, dtype=torch.uint8, device=self.dev) if self.masked else None
+            self._frame, self._frame_mask = None, None
+            self._draw = torch.Generator().manual_seed(int(seed))
         self._affine = None            # static [1,12] buffer with the image's colour transform when the exposure network is frozen
         self.graph, self.apr_graph = None, None
 
@@ -250,7 +271,30 @@ class PoseRefiner:
         """The fused features [B, C, h, w] the loss compares with the target, at the refiner's current state (pose, camera, log_f):
         what a caller renders a synthetic target with."""
         with torch.no_grad():
-            return self._fused().detach().clone()
+            return (self._sparse_features() if self.sparse is not None else self._fused()).detach().clone()
+
+    def _composed_pose(self):
+        """LearnPose + fix_coord_supp as one launch each way (ops.pose_compose): [B, 3, 4]; with the fused Adam its backward writes the
+        parameters' .grad itself."""
+        ws = self.world_setup or {"pose_scale": 1.0, "pose_scale2": 1.0, "move_all_cam_vec": (0., 0., 0.)}
+        into = (self.model.r.grad, self.model.t.grad) if isinstance(self.opt, ops.FusedAdam) else None
+        return ops.pose_compose(self.model.r, self.model.t, self.model.init_c2w, ws["pose_scale"], ws["move_all_cam_vec"],
+                                ws["pose_scale2"], grad_into=into)
+
+    def _sparse_features(self):
+        """sparse: pose -> render(pixels=self.pixels) -> feat_map [K, C] -> [C, K], the layout the loss kernels read (a torch
+        transposition: plumbing).  With sparse= in place of the frame, what features() returns."""
+        c2w = self._composed_pose()
+        _, _, _, ex = render(self.h, self.w, self.focal, c2w=c2w.reshape(3, 4), near=self.near, far=self.far, img_idx=self.hist,
+                             pixels=self.pixels, **self.kw, **self._camera())
+        return ex["feat_map"].t()
+
+    def _sparse_loss(self):
+        """_loss of PoseRefiner(sparse=K): the feature loss of the K rendered features against self.target [C, K] -- per channel over the
+        pixels, or per pixel over the channels -- on the existing loss kernels; masked: over the pixels with self.mask != 0."""
+        op = ops.pixel_cosine_loss if self.per_pixel else ops.cosine_feature_loss
+        loss = op(self._sparse_features(), self.target, out=self.loss, mask=self.mask)
+        return loss, loss.detach()
 
     def _fused(self):
         """pose -> render -> affine colour transform -> fusion CNN: the fused features [B, C, h, w] of the current state."""
@@ -266,10 +310,7 @@ class PoseRefiner:
                 if self.world_setup is not None:
                     c2w = fix_coord_supp(c2w, self.world_setup)
         elif self.fused_glue and not self.model.lietorch:
-            ws = self.world_setup or {"pose_scale": 1.0, "pose_scale2": 1.0, "move_all_cam_vec": (0., 0., 0.)}
-            into = (self.model.r.grad, self.model.t.grad) if isinstance(self.opt, ops.FusedAdam) else None
-            c2w = ops.pose_compose(self.model.r, self.model.t, self.model.init_c2w, ws["pose_scale"], ws["move_all_cam_vec"],
-                                   ws["pose_scale2"], grad_into=into)                     # [B,3,4]
+            c2w = self._composed_pose()                    # [B,3,4]
         else:
             c2w = self.model(0)[None, :3, :4]
             if self.world_setup is not None:
@@ -315,6 +356,8 @@ class PoseRefiner:
         Returns (scalar to differentiate, per-image losses [B] or the same scalar).  One image on the fused glue: the library's loss
         kernel writes its value straight into the static buffer self.loss (`out=`: no 4-byte copy launch per iteration); everything
         else (images=B, the torch expressions) returns its own tensor and the callers copy it."""
+        if self.sparse is not None:
+            return self._sparse_loss()
         B = self.B
         out = self.loss if (B == 1 and self.fused_glue) else None
         fused = self._fused()
@@ -479,15 +522,76 @@ class PoseRefiner:
             else:
                 self._affine.copy_(a)
 
-    def _reset(self, init_c2w, feature_target, hist, mask=None):
-        self._set_mask(mask)
+    def _frame_mask_of(self, mask):
+        """sparse: the image's mask as bool [h, w] on the device (None: no mask)."""
+        h, w = self.h, self.w
+        if mask is None:
+            return None
+        if not self.masked:
+            raise ValueError("nefes_amd: this PoseRefiner was built without a mask buffer; construct it with PoseRefiner(..., masked=True) "
+                             "to pass mask=")
+        m = torch.as_tensor(mask)
+        if m.numel() != h * w or tuple(m.shape[-2:]) != (h, w):
+            raise ValueError(f"nefes_amd: the mask has shape {tuple(m.shape)}; a sparse refiner samples it from the rendered frame {(h, w)}")
+        return (m.to(self.dev) > 0).reshape(h, w)
+
+    def _draw_pixels(self, frame_mask):
+        """sparse: K distinct integer pixels (x, y) of the rendered frame, uniform among the mask's valid ones, from the generator of the
+        constructor's seed: int64 [K, 2] on the host.  One host read of the mask, outside the loop."""
+        h, w = self.h, self.w
+        valid = torch.arange(h * w) if frame_mask is None else frame_mask.reshape(-1).nonzero().flatten().cpu()
+        if valid.numel() < self.sparse:
+            raise ValueError(f"nefes_amd: {self.sparse} distinct pixels asked for, the frame {(h, w)} has {valid.numel()} valid ones")
+        idx = valid[torch.randperm(valid.numel(), generator=self._draw)[:self.sparse]]
+        return torch.stack([idx % w, idx // w], -1)
+
+    def _set_frame(self, feature_target, mask, pixels):
+        """sparse: the image's feature frame [C, h, w] and mask (kept for set_pixels), then its pixels -- the given [K, 2] list, or drawn
+        (_draw_pixels)."""
+        h, w = self.h, self.w
+        frame = feature_target.to(self.dev, torch.float32)
+        if frame.numel() != self.C * h * w:
+            raise ValueError(f"nefes_amd: a sparse refiner samples its target from the rendered frame's features [{self.C}, {h}, {w}]; got "
+                             f"{tuple(feature_target.shape)}")
+        self._frame, self._frame_mask = frame.reshape(self.C, h, w).contiguous(), self._frame_mask_of(mask)
+        self.set_pixels(self._draw_pixels(self._frame_mask) if pixels is None else pixels)
+
+    def set_pixels(self, px):
+        """sparse: new pixels [K, 2] (ops.as_pixels) into self.pixels IN PLACE, and the image's target -- and mask, nearest -- re-sampled
+        there in place: a captured iteration reads all three from memory and follows without a re-capture."""
+        if self.sparse is None:
+            raise RuntimeError("nefes_amd: set_pixels needs a PoseRefiner(sparse=K)")
+        if self._frame is None:
+            raise RuntimeError("nefes_amd: set_pixels re-samples the image's target: give the refiner an image first (refine)")
+        px = ops.as_pixels(px, self.dev)
+        if tuple(px.shape) != (self.sparse, 2):
+            raise ValueError(f"nefes_amd: this refiner was built for {self.sparse} pixels [{self.sparse}, 2]; got {tuple(px.shape)}")
+        with torch.no_grad():
+            self.pixels.copy_(px)
+            ops.sample_pixels(self._frame, self.pixels, out=self.target)
+            if self.masked:
+                if self._frame_mask is None:
+                    self.mask.fill_(1)
+                else:
+                    xi = self.pixels[:, 0].round().clamp_(0, self.w - 1).long()
+                    yi = self.pixels[:, 1].round().clamp_(0, self.h - 1).long()
+                    self.mask.copy_(self._frame_mask[yi, xi].reshape(1, -1))
+                    if not bool(self.mask.any()):
+                        raise ValueError("nefes_amd: none of the pixels is valid in the image's mask (mask > 0): nothing to refine against")
+
+    def _reset(self, init_c2w, feature_target, hist, mask=None, pixels=None):
+        if self.sparse is None:
+            self._set_mask(mask)
         with torch.no_grad():
             self.model.r.zero_()
             self.model.t.zero_()
             if self.log_f is not None:
                 self.log_f.zero_()
             self.model.init_c2w.copy_(init_c2w.reshape(self.B, 4, 4))
-            self.target.copy_(feature_target.reshape(self.target.shape))
+            if self.sparse is not None:
+                self._set_frame(feature_target, mask, pixels)
+            else:
+                self.target.copy_(feature_target.reshape(self.target.shape))
             if self._uses_prepared_target():
                 self._sync_upcos()
             self.hist.copy_(hist.reshape(self.B, 10))
@@ -582,19 +686,28 @@ class PoseRefiner:
             self._step(m, i, iters, losses, checks)
         return m.finish(m.read(), before, checks, losses)
 
-    def _job(self, *job, mask=None):
-        """The job tuple of an image: with a fourth element, its mask, on a masked refiner (None: all valid)."""
+    def _job(self, *job, mask=None, pixels=None):
+        """The job tuple of an image: with a fourth element, its mask, on a masked refiner (None: all valid); on a sparse refiner a
+        fourth and a fifth, mask and pixels (None: drawn)."""
+        if self.sparse is not None:
+            # (drawn HERE, once per image: _run writes the image's state twice around a first capture)
+            px = self._draw_pixels(self._frame_mask_of(mask)) if pixels is None else pixels
+            return job + (None if mask is None else torch.as_tensor(mask), ops.as_pixels(px, self.dev))
+        if pixels is not None:
+            raise ValueError("nefes_amd: pixels= needs a PoseRefiner(sparse=K)")
         if not self.masked:
             self._set_mask(mask)                           # (raises for mask= on an unmasked refiner)
             return job
         return job + (None if mask is None else torch.as_tensor(mask),)
 
-    def refine(self, init_c2w, feature_target, hist, iters=50, mask=None):
+    def refine(self, init_c2w, feature_target, hist, iters=50, mask=None, pixels=None):
         """One image (images=1): (refined 4x4 c2w, losses [iters]) -- with learn_focal (refined c2w, losses, log_f [1]).
         A batch (images=B): init_c2w [B,4,4], feature_target [B,C,h,w], hist [B,10] -> (refined poses [B,4,4], losses [iters,B]), each image as if refined alone.
         mask (PoseRefiner(masked=True)): the image's valid pixels, > 0, in the target's spatial shape [th,tw] or [1,th,tw] (a batch:
-        [B,th,tw]); None: all valid."""
-        return self._run(self._mode(), self._job(init_c2w, feature_target, hist, mask=mask), iters)
+        [B,th,tw]); None: all valid.
+        pixels (PoseRefiner(sparse=K)): the [K, 2] points (x, y) of the rendered (h, w) frame to match at; feature_target is that frame's
+        features [C, h, w], sampled there once.  None: K distinct integer pixels are drawn."""
+        return self._run(self._mode(), self._job(init_c2w, feature_target, hist, mask=mask, pixels=pixels), iters)
 
     refine_batch = refine
 
@@ -697,6 +810,19 @@ class PoseRefiner:
         mask (PoseRefiner(masked=True)): the valid pixels of the CROPPED full-resolution image, [H-20, W-20] (full_resolution_mask);
         the verification step's PSNR / SSIM stay unmasked, as in the reference."""
         return self._run(self._mode(apr=True, verification=verification), self._job(photo, feature_target, hist, mask=mask), iters)
+
+
+def _refuse_sparse(K, pose_model, images, upsample, fused_glue, lietorch):
+    """What PoseRefiner(sparse=K) cannot be combined with, said by the constructor."""
+    if K < 1:
+        raise ValueError(f"nefes_amd: PoseRefiner(sparse={K}): the number of pixels must be positive")
+    for bad, what in ((pose_model is not None, "pose_model=: its verification step compares an image, and a sparse refiner renders none"),
+                      (int(images) > 1, "images > 1: one image at a time"),
+                      (bool(upsample), "upsample=True: there is no frame to up-sample; tinyscale=1 gives full-resolution pixels"),
+                      (not fused_glue, "fused_glue=False: the sparse loss runs on the library's loss kernels"),
+                      (bool(lietorch), "lietorch=True: the pose chain is ops.pose_compose")):
+        if bad:
+            raise NotImplementedError("nefes_amd: PoseRefiner(sparse=K) with " + what)
 
 
 def _camera_buffer(intrinsics, B, device):

@@ -289,7 +289,14 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     return _cat_parts([render_rays(rays_flat[i:i + step], **kwargs) for i in range(0, rays_flat.shape[0], step)])
 
 
-def _rays_for(H, W, focal, c2w, c2w_staticcam, row_range, intr=None):
+def _rays_for(H, W, focal, c2w, c2w_staticcam, row_range, intr=None, px=None):
+    if px is not None:                                              # the K rays of a pixel list (ops.as_pixels) replace the grid
+        if intr is None:                                            # the centred camera of the focal kernels, as a device tensor
+            intr = torch.tensor([float(focal), float(focal), float(W * .5), float(H * .5)], dtype=torch.float32, device=_DEV)
+        rays_o, rays_d, viewdirs = ops.RayGenPx.apply(c2w.to(_DEV), intr, px)
+        if c2w_staticcam is not None:                               # the same pixels for both cameras
+            rays_o, rays_d, _ = ops.RayGenPx.apply(c2w_staticcam.to(_DEV), intr, px)
+        return rays_o, rays_d, viewdirs
     row0, nrows = (0, H) if row_range is None else row_range
     if intr is not None:                                            # a camera with intrinsics (ops.as_intrinsics): `focal` is not read
         rays_o, rays_d, viewdirs = ops.RayGenK.apply(c2w.to(_DEV), intr, H, W, row0, nrows)
@@ -312,6 +319,21 @@ def _refuse_intrinsics(intrinsics, ndc, rays_only=False):
     if ndc:
         raise NotImplementedError("nefes_amd: render(intrinsics=..., ndc=True): the NDC warp (ray_utils.py:27-44) assumes a centred "
                                   "principal point and one focal length; pass ndc=False (no shipped NeFeS config uses NDC)")
+
+
+def _refuse_pixels(pixels, ndc, rays_only=False, row_range=None):
+    """What `pixels=` cannot be combined with, said before anything touches the device."""
+    if pixels is None:
+        return
+    if rays_only:
+        raise ValueError("nefes_amd: render(pixels=...) with rays=: the rays are the caller's, there is no camera to look through the "
+                         "pixels with (pass c2w=, or build the rays with ops.raygen_px_fwd)")
+    if row_range is not None:
+        raise ValueError("nefes_amd: render(pixels=..., row_range=...): row_range shards the frame's grid and pixels= replaces that grid; "
+                         "shard the pixel list itself (pixels=px[k0:k1])")
+    if ndc:
+        raise NotImplementedError("nefes_amd: render(pixels=..., ndc=True): the NDC warp (ray_utils.py:27-44) is built for the frame's own "
+                                  "centred grid; pass ndc=False (no shipped NeFeS config uses NDC)")
 
 
 def _render_batch(rays_o, rays_d, viewdirs, near, far, chunk, kwargs, cfg):
@@ -337,9 +359,14 @@ def _render_batch(rays_o, rays_d, viewdirs, near, far, chunk, kwargs, cfg):
 
 
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
-           c2w_staticcam=None, img_idx=torch.Tensor(0), row_range=None, intrinsics=None, **kwargs):
-    """Reference signature (rendering.py:197-200) + `row_range=(row0, nrows)` for ray-batch sharding + `intrinsics=`.
+           c2w_staticcam=None, img_idx=torch.Tensor(0), row_range=None, intrinsics=None, pixels=None, **kwargs):
+    """Reference signature (rendering.py:197-200) + `row_range=(row0, nrows)` for ray-batch sharding + `intrinsics=` + `pixels=`.
     Returns [rgb_map [N,3], disp_map [N], acc_map [N], extras dict].
+
+    `pixels` [K, 2] rows of (x, y) = (column, row) -- a float32 device tensor, used as is and read from device memory by the ray kernel,
+    or host values (ops.as_pixels) -- replaces the frame's grid by the K rays through those points; every output is [K, ...].  get_rays'
+    convention: an integer coordinate is that pixel (no half-pixel offset); fractions and points outside the frame are legal.  The
+    camera is `intrinsics` when given, else (focal, focal, W/2, H/2).
 
     `intrinsics` (fx, fy, cx, cy) of the rendered H x W image -- a float32 [4] device tensor, a 4-sequence or a 3 x 3 K
     (ops.as_intrinsics) -- replaces `focal` and the centred principal point for the rays of `c2w` and of `c2w_staticcam`.  The kernels
@@ -349,9 +376,11 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         raise NotImplementedError("nefes_amd: the NeFeS field always uses view directions (use_viewdirs=True)")
     cfg = _cfg(kwargs)
     _refuse_intrinsics(intrinsics, ndc, rays_only=c2w is None)
+    _refuse_pixels(pixels, ndc, rays_only=c2w is None, row_range=row_range)
     if c2w is not None:
         intr = None if intrinsics is None else ops.as_intrinsics(intrinsics, _DEV)
-        rays_o, rays_d, viewdirs = _rays_for(int(H), int(W), focal, c2w, c2w_staticcam, row_range, intr)
+        px = None if pixels is None else ops.as_pixels(pixels, _DEV)
+        rays_o, rays_d, viewdirs = _rays_for(int(H), int(W), focal, c2w, c2w_staticcam, row_range, intr, px)
     else:
         rays_o, rays_d = rays
         rays_o, rays_d = rays_o.to(_DEV).reshape(-1, 3).float(), rays_d.to(_DEV).reshape(-1, 3).float()
@@ -380,27 +409,47 @@ def _cameras(intrinsics, B):
     return [ops.as_intrinsics(intrinsics, _DEV)] * B
 
 
-def render_poses(H, W, focal, poses, chunk=1024 * 32, ndc=True, near=0., far=1., use_viewdirs=False, intrinsics=None, **kwargs):
+def _pixel_sets(pixels, B):
+    """B pixel lists for render_poses: None each, the one [K, 2] list B times, or the [K, 2] slices of a [B, K, 2] table (views of a
+    contiguous float32 device tensor: used as they are)."""
+    if pixels is None:
+        return [None] * B
+    if not torch.is_tensor(pixels):
+        import numpy as np
+        pixels = torch.from_numpy(np.asarray(pixels, dtype=np.float64))
+    if pixels.dim() == 3:
+        if pixels.shape[0] != B:
+            raise ValueError(f"nefes_amd: render_poses(pixels=...) takes one [K, 2] list or [{B}, K, 2], one per pose; got {tuple(pixels.shape)}")
+        return [ops.as_pixels(p, _DEV) for p in pixels.unbind(0)]
+    return [ops.as_pixels(pixels, _DEV)] * B
+
+
+def render_poses(H, W, focal, poses, chunk=1024 * 32, ndc=True, near=0., far=1., use_viewdirs=False, intrinsics=None, pixels=None,
+                 **kwargs):
     """Several camera poses in ONE launch sequence (the reference's render_path loops render() per
     pose, rendering.py:270-273): rays of all B poses are generated (one small kernel per pose) and concatenated, then
     every heavy kernel -- coarse field, compositing, sampling, fine field, compositing -- runs once over B*H*W rays.
     poses [B,3,4] (or [B,4,4]).  Returns [rgb [B,H*W,3], disp [B,H*W], acc [B,H*W], extras {k: [B,H*W,...]}];
     differentiable w.r.t. `poses` like render().  `intrinsics`: one camera for all poses (as render() takes it) or [B, 4], one per
-    pose; read from device memory by the ray kernels, differentiable when it is a device tensor that requires a gradient."""
+    pose; read from device memory by the ray kernels, differentiable when it is a device tensor that requires a gradient.  `pixels`
+    (render()'s keyword): one [K, 2] list shared by all poses or [B, K, 2], one per pose; every output is then [B, K, ...]."""
     if not use_viewdirs:
         raise NotImplementedError("nefes_amd: the NeFeS field always uses view directions (use_viewdirs=True)")
     cfg = _cfg(kwargs)
     _refuse_intrinsics(intrinsics, ndc)
+    _refuse_pixels(pixels, ndc)
     H, W = int(H), int(W)
     B = poses.shape[0]
     p34 = poses if tuple(poses.shape[-2:]) == (3, 4) else poses[:, :3, :4]
     cams = _cameras(intrinsics, B)
-    parts = [_rays_for(H, W, focal, c, None, None, k) for c, k in zip(p34.unbind(0), cams)]      # unbind: one stack in the backward, no fills
+    pxs = _pixel_sets(pixels, B)
+    parts = [_rays_for(H, W, focal, c, None, None, k, px) for c, k, px in zip(p34.unbind(0), cams, pxs)]      # unbind: one stack in the backward, no fills
     rays_o, rays_d, viewdirs = (torch.cat([p[k] for p in parts], 0) for k in range(3))
     if ndc:
         rays_o, rays_d = ops.NdcRays.apply(rays_o, rays_d, H, W, float(focal), 1.)
     all_ret = _render_batch(rays_o, rays_d, viewdirs, near, far, chunk, kwargs, cfg)
-    shp = lambda v: v.reshape(B, H * W, *v.shape[1:]) if torch.is_tensor(v) else v
+    n = H * W if pixels is None else pxs[0].shape[0]
+    shp = lambda v: v.reshape(B, n, *v.shape[1:]) if torch.is_tensor(v) else v
     k_extract = ["rgb_map", "disp_map", "acc_map"]
     return [shp(all_ret[k]) for k in k_extract] + [{k: shp(v) for k, v in all_ret.items() if k not in k_extract}]
 
