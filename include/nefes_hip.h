@@ -559,7 +559,8 @@ int nefes_psnr_ssim(int C, int H, int W, const float* x, int64_t x_row_stride, i
                     int64_t y_plane_stride, void* workspace, float* out, void* stream);
 /* feature_loss (DFM_pose_refine.py:211-233, per_pixel=False): loss = 1 - mean_c cos(a[c,:], b[c,:]), a, b dev [C,P] contiguous,
  * torch.nn.CosineSimilarity(dim=1, eps=1e-6) semantics, float64 accumulation.  scratch: dev doubles,
- * nefes_cosine_loss_scratch_doubles(C) of them, kept by the caller for the backward. */
+ * nefes_cosine_loss_scratch_doubles(C) of them, kept by the caller for the backward.  NEFES_E_UNSUPPORTED where the grid would pass
+ * 2^31 - 1 blocks (forward: 8 C; backward: C * P / 256), as the masked pair below returns it; such a call used to be launched. */
 size_t nefes_cosine_loss_scratch_doubles(int C);
 int nefes_cosine_loss_fwd(int C, int64_t P, const float* a, const float* b, double* scratch, float* loss, void* stream);
 /* g_a [C,P] = g_loss[0] * d loss / d a (g_loss: dev scalar). */

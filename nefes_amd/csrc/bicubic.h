@@ -1,4 +1,4 @@
-// Bicubic taps of ATen's upsample_bicubic2d (align_corners=False, A = -0.75): shared by upsample.hip and refine.hip.
+// Bicubic taps of ATen's upsample_bicubic2d (align_corners=False, A = -0.75): shared by upsample.hip and feature_loss.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -25,17 +25,19 @@ TIMERS = None
 
 
 class _timed:
+    """`with _timed(key)`: the launches inside go under TIMERS[key]; a key of None records nothing."""
+
     def __init__(self, name):
         self.name = name
 
     def __enter__(self):
-        if TIMERS is not None:
+        if TIMERS is not None and self.name is not None:
             self.t0 = torch.cuda.Event(enable_timing=True)
             self.t1 = torch.cuda.Event(enable_timing=True)
             self.t0.record()
 
     def __exit__(self, *exc):
-        if TIMERS is not None:
+        if TIMERS is not None and self.name is not None:
             self.t1.record()
             TIMERS.setdefault(self.name, []).append((self.t0, self.t1))
         return False
@@ -65,7 +67,8 @@ def _chk(t: Optional[torch.Tensor], name: str, dtype=torch.float32):
 
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().to(torch.float32).contiguous()
+    t = t.detach()             # (the usual case asks twice and converts nothing: .to and .contiguous each cost a dispatch)
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1794,80 +1797,112 @@ def _loss_mask(mask, G, spatial, device, what):
     return mask.detach().reshape(G, P)
 
 
-class MaskedCosineFeatureLoss(torch.autograd.Function):
-    """masked_feature_loss (dm/DFM_pose_refine.py:257-288, per_pixel=False) on [G*Cg, ...] maps with a uint8 mask [G, pixels]: per group
-    1 - mean over its channels of the cosine similarity over its VALID pixels, summed over the groups (csrc/refine.hip MASKED instances)."""
+# One of the four feature losses (csrc/feature_loss.hip), unmasked or masked, as FeatureLoss reads it: the public function's name, on
+# the up-sampled map?, per pixel?, its entry points and scratch query, its ops.TIMERS keys.
+_LossForm = collections.namedtuple("_LossForm", "what up per_pixel fwd bwd query timer_fwd timer_bwd")
+
+
+def _loss_form(stem, what, up, per_pixel, masked):
+    m = "_masked" if masked else ""
+    keyed = masked or stem != "cosine"                    # (the unmasked channel-wise pair has never had a TIMERS key)
+    return _LossForm(what, up, per_pixel, f"nefes_{stem}_loss{m}_fwd", f"nefes_{stem}_loss{m}_bwd",
+                     f"nefes_{stem}{m}_scratch_doubles" if per_pixel else "nefes_cosine_loss_scratch_doubles",
+                     f"{stem}_loss{m}_fwd" if keyed else None, f"{stem}_loss{m}_bwd" if keyed else None)
+
+
+_LOSS_FORMS = {(stem, masked): _loss_form(stem, what, up, per_pixel, masked) for masked in (False, True)
+               for stem, what, up, per_pixel in (("cosine", "cosine_feature_loss", False, False), ("upcos", "upsampled_cosine_loss", True, False),
+                                                 ("pixcos", "pixel_cosine_loss", False, True),
+                                                 ("uppixcos", "upsampled_pixel_cosine_loss", True, True))}
+
+
+def _loss_outputs(ctx, loss, scratch, per_pixel, G, GC):
+    """(loss, cos) as a feature-loss Function returns them.  `cos`: the float64 cosines the forward kernel left at the head of its
+    scratch (a view, no gradient) -- per channel [GC], column 3 of the stats [GC][4], or per pixel the mean per group [G]."""
+    cos = scratch[:G] if per_pixel else scratch[3:4 * GC:4]
+    ctx.set_materialize_grads(False)                      # no zero-filled gradient for `cos` in the backward
+    ctx.mark_non_differentiable(cos)
+    return loss, cos
+
+
+def _loss_maps(form, af, bf, mk, scratch):
+    """What every entry point of a form takes after its sizes: the two maps, the mask if there is one, the scratch -- checked."""
+    maps = (_chk(af, "x"), _chk(bf, "target")) if form.up else (_chk(af, "a"), _chk(bf, "b"))
+    if mk is not None:
+        maps += (_chk(mk, "mask", torch.uint8),)
+    return maps + (_chk(scratch, "scratch", torch.float64),)
+
+
+class FeatureLoss(torch.autograd.Function):
+    """The feature loss of the reference's refinement loop in one of its forms (`form`: a row of _LOSS_FORMS):
+    feature_loss / masked_feature_loss (dm/DFM_pose_refine.py:211-233, :257-288) on maps a, b [G*C, ...pixels] -- per group (image)
+    1 - mean over its channels of the cosine similarity over its (valid) pixels, or per pixel 1 - mean over its (valid) pixels of the
+    cosine similarity over its channels, summed over the G groups -- and the same of the bicubically up-sampled, cropped a [G*C, h, w]
+    (or [1, ., h, w]) against b [G*C, OH-2crop, OW-2crop] without the up-sampled image (`geom` = (OH, OW, crop); None: not up-sampled).
+    `mask`: uint8, one plane per group (_loss_mask); None: the unmasked entry points -- the channel-wise ones take all G*C channels as
+    ONE group (1 - their mean: the caller multiplies by G).  Two launches forward, one (up-sampled: two) backward, to `a` only: the
+    target carries no gradient.  Returns (loss, cos) (_loss_outputs).  Every check runs before anything is launched."""
 
     @staticmethod
-    def forward(ctx, a, b, mask, groups, out=None):
-        G = _groups_of(a.shape[0], groups, "cosine_feature_loss")
-        Cg = a.shape[0] // G
-        af, bf = _f32(a).reshape(G * Cg, -1), _f32(b).reshape(G * Cg, -1)
-        if af.shape != bf.shape:
-            raise ValueError(f"nefes_amd: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
-        mk = _loss_mask(mask, G, a.shape[1:], af.device, "cosine_feature_loss")
-        lib = L.load()
-        scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(G * Cg), dtype=torch.float64, device=af.device)
+    def forward(ctx, how, a, b, mask, out):
+        form, geom, groups = how
+        GC = a.shape[-3] if form.up else a.shape[0]
+        G = _groups_of(GC, groups, form.what)
+        one_group = mask is None and not form.per_pixel
+        if one_group and G > 1 and out is not None:
+            raise ValueError(f"nefes_amd: {form.what}: `out` takes the kernel's own value; with groups > 1 and no mask the sum over the "
+                             "groups is formed after it")
+        af = _f32(a)
+        if form.up:
+            h, w = af.shape[-2:]
+            if af.numel() != GC * h * w:
+                raise ValueError(f"nefes_amd: {form.what}: features {tuple(a.shape)} are not [C,h,w] (or [1,C,h,w]) maps")
+            OH, OW, crop = geom
+            spatial = (OH - 2 * crop, OW - 2 * crop)
+            af, bf = af.reshape(GC, h, w), _f32(b).reshape((GC,) + spatial)
+            sizes = (h, w, OH, OW, crop)
+        else:
+            af, bf = af.reshape(GC, -1), _f32(b).reshape(GC, -1)
+            if af.shape != bf.shape:
+                raise ValueError(f"nefes_amd: {form.what}: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
+            spatial, sizes = a.shape[1:], (af.shape[1],)
+        mk = None if mask is None else _loss_mask(mask, G, spatial, af.device, form.what)
         loss = _loss_buffer(out, af.device)
-        with _timed("cosine_loss_masked_fwd"):
-            L.check(lib.nefes_cosine_loss_masked_fwd(G, Cg, af.shape[1], _chk(af, "a"), _chk(bf, "b"), _chk(mk, "mask", torch.uint8),
-                                                     _chk(scratch, "scratch", torch.float64), _chk(loss, "loss"), _stream()),
-                    "nefes_cosine_loss_masked_fwd")
+        lib = L.load()
+        doubles = getattr(lib, form.query)(G, *(geom if form.up else sizes)) if form.per_pixel else lib.nefes_cosine_loss_scratch_doubles(GC)
+        scratch = torch.empty(doubles, dtype=torch.float64, device=af.device)
+        sizes = ((GC,) if one_group else (G, GC // G)) + sizes
+        with _timed(form.timer_fwd):
+            L.check(getattr(lib, form.fwd)(*sizes, *_loss_maps(form, af, bf, mk, scratch), _chk(loss, "loss"), _stream()), form.fwd)
         ctx.save_for_backward(af, bf, mk, scratch)
-        ctx.cfg = (a.shape, G, Cg)
-        cos = scratch[:4 * G * Cg].view(G * Cg, 4)[:, 3]
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
+        ctx.cfg = (form, a.shape, sizes)
+        return _loss_outputs(ctx, loss, scratch, form.per_pixel, G, GC)
 
     @staticmethod
     def backward(ctx, g, _g_cos):
         if g is None:
             return (None,) * 5
         af, bf, mk, scratch = ctx.saved_tensors
-        shape, G, Cg = ctx.cfg
+        form, shape, sizes = ctx.cfg
         gf = _f32(g).reshape(1)
+        if form.up:                                         # the row gradients are gathered along x into tmp, then along y into g_a
+            h, w, OH, OW, crop = sizes[-5:]
+            tmp = torch.empty(af.shape[0], OH - 2 * crop, w, device=af.device)
+            (fx, cx, wx, T), (fy, cy, wy, _) = bicubic_gather_tables(h, w, OH, OW, crop, af.device)
         g_a = torch.empty_like(af)
-        with _timed("cosine_loss_masked_bwd"):
-            L.check(L.load().nefes_cosine_loss_masked_bwd(G, Cg, af.shape[1], _chk(af, "a"), _chk(bf, "b"), _chk(mk, "mask", torch.uint8),
-                                                          _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), _chk(g_a, "g_a"),
-                                                          _stream()), "nefes_cosine_loss_masked_bwd")
-        return g_a.reshape(shape), None, None, None, None
+        with _timed(form.timer_bwd):
+            tables = (fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), fy.data_ptr(), cy.data_ptr(), wy.data_ptr(), T, _chk(tmp, "tmp")) if form.up else ()
+            L.check(getattr(L.load(), form.bwd)(*sizes, *_loss_maps(form, af, bf, mk, scratch), _chk(gf, "g_loss"), *tables, _chk(g_a, "g_a"),
+                                                _stream()), form.bwd)
+        return None, g_a.reshape(shape), None, None, None
 
 
-class CosineFeatureLoss(torch.autograd.Function):
-    """feature_loss (dm/DFM_pose_refine.py:211-233, per_pixel=False) on [C, ...] maps: 1 - mean over channels of the cosine
-    similarity over pixels; two launches forward, one backward (to `a` only: the target carries no gradient)."""
-
-    @staticmethod
-    def forward(ctx, a, b, out=None):
-        Cc = a.shape[0]
-        af, bf = _f32(a).reshape(Cc, -1), _f32(b).reshape(Cc, -1)
-        if af.shape != bf.shape:
-            raise ValueError(f"nefes_amd: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
-        lib = L.load()
-        scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(Cc), dtype=torch.float64, device=af.device)
-        loss = _loss_buffer(out, af.device)
-        L.check(lib.nefes_cosine_loss_fwd(Cc, af.shape[1], _chk(af, "a"), _chk(bf, "b"), _chk(scratch, "scratch", torch.float64),
-                                          _chk(loss, "loss"), _stream()), "nefes_cosine_loss_fwd")
-        ctx.save_for_backward(af, bf, scratch)
-        ctx.shape = a.shape
-        cos = scratch[:4 * Cc].view(Cc, 4)[:, 3]          # float64 cosine similarity per channel (a view of the scratch)
-        ctx.set_materialize_grads(False)                  # no zero-filled gradient for `cos` in the backward
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
-
-    @staticmethod
-    def backward(ctx, g, _g_cos):
-        if g is None:
-            return (None,) * 3
-        af, bf, scratch = ctx.saved_tensors
-        gf = _f32(g).reshape(1)
-        g_a = torch.empty_like(af)
-        L.check(L.load().nefes_cosine_loss_bwd(af.shape[0], af.shape[1], _chk(af, "a"), _chk(bf, "b"),
-                                               _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), _chk(g_a, "g_a"), _stream()),
-                "nefes_cosine_loss_bwd")
-        return g_a.reshape(ctx.shape), None, None
+def _feature_loss(stem, a, b, geom, groups, mask, out, return_cos):
+    form = _LOSS_FORMS[stem, mask is not None]
+    loss, cos = FeatureLoss.apply((form, geom, groups), a, b, mask, out)
+    if mask is None and not form.per_pixel and int(groups) > 1:
+        loss = loss * float(int(groups))
+    return (loss, cos) if return_cos else loss
 
 
 def cosine_feature_loss(a, b, return_cos=False, out=None, groups=1, mask=None):
@@ -1878,18 +1913,32 @@ def cosine_feature_loss(a, b, return_cos=False, out=None, groups=1, mask=None):
     `groups` = G > 1: the leading dimension is G groups (images) of C channels and the value is the SUM over the groups of each one's
     loss.  `mask`: uint8 [G, ...pixels] on the inputs' device, one plane per group shared by its channels -- the sums of every channel
     run over the pixels with mask != 0 only (the reference's masked_feature_loss); values at the others are never read and their
-    gradient is exactly 0.  None: today's unmasked kernels (G > 1: their mean over all G*C channels times G -- the same number)."""
-    if mask is not None:
-        loss, cos = MaskedCosineFeatureLoss.apply(a, b, mask, groups, out)
-        return (loss, cos) if return_cos else loss
-    G = _groups_of(a.shape[0], groups, "cosine_feature_loss")
-    if G > 1 and out is not None:
-        raise ValueError("nefes_amd: cosine_feature_loss: `out` takes the kernel's own value; with groups > 1 and no mask the sum over "
-                         "the groups is formed after it")
-    loss, cos = CosineFeatureLoss.apply(a, b, out)
-    if G > 1:
-        loss = loss * float(G)
-    return (loss, cos) if return_cos else loss
+    gradient is exactly 0.  None: the unmasked kernels (G > 1: their mean over all G*C channels times G -- the same number; no `out`)."""
+    return _feature_loss("cosine", a, b, None, groups, mask, out, return_cos)
+
+
+def upsampled_cosine_loss(x, target, size, crop=0, return_cos=False, out=None, groups=1, mask=None):
+    """1 - mean over channels of the cosine similarity (over pixels) between the bicubically up-sampled, cropped x and target.
+    `out`, `groups` and `mask` (uint8 [groups, OH-2crop, OW-2crop]: of the up-sampled, cropped pixels) as in cosine_feature_loss.
+    One-pass kernels; a masked loss has no prepared-target (Gram) form: sum_p m_p up_p^2 does not separate into the two axes."""
+    return _feature_loss("upcos", x, target, (int(size[0]), int(size[1]), int(crop)), groups, mask, out, return_cos)
+
+
+def pixel_cosine_loss(a, b, groups=1, return_cos=False, out=None, mask=None):
+    """The per-pixel feature loss (`--per_pixel`): a, b [groups * C, ...]; per group 1 - mean over pixels of the cosine similarity over
+    its C channels (torch.nn.CosineSimilarity(dim=0, eps=1e-6)), summed over the groups -- every group's value and gradient are what a
+    call on that group alone gives.  `return_cos` adds the per-group mean cosines (float64, no gradient); `out` as in
+    cosine_feature_loss.  `mask`: uint8 [groups, ...pixels]; the mean is over the group's pixels with mask != 0 (values at the others are
+    never read, their gradient is exactly 0; a group without one gives NaN, as the reference's mean of an empty tensor); None: the
+    unmasked kernels."""
+    return _feature_loss("pixcos", a, b, None, groups, mask, out, return_cos)
+
+
+def upsampled_pixel_cosine_loss(x, target, size, crop=0, groups=1, return_cos=False, out=None, mask=None):
+    """pixel_cosine_loss of the bicubically up-sampled, cropped x against target, one pass each way.  `out` as in cosine_feature_loss;
+    `mask` (uint8 [groups, OH-2crop, OW-2crop]: of the up-sampled, cropped pixels) as in pixel_cosine_loss.  There is no prepared-target
+    form of this loss: the normalisation is per pixel."""
+    return _feature_loss("uppixcos", x, target, (int(size[0]), int(size[1]), int(crop)), groups, mask, out, return_cos)
 
 
 def psnr_ssim(x, y):
@@ -1942,312 +1991,6 @@ def bicubic_gather_tables(h, w, OH, OW, crop, device):
     return (bicubic_gather_table(w, OW, crop, OW - 2 * crop, device, T), bicubic_gather_table(h, OH, crop, OH - 2 * crop, device, T))
 
 
-class UpsampledCosineLoss(torch.autograd.Function):
-    """cosine_feature_loss(bicubic_upsample(x, size, crop), target) for x [C,h,w] (or [1,C,h,w]) without the up-sampled image:
-    csrc/refine.hip upcos kernels.  Returns (loss, per-channel cosine similarities) like CosineFeatureLoss."""
-
-    @staticmethod
-    def forward(ctx, x, target, OH, OW, crop, out=None):
-        xf = _f32(x)
-        Cc, h, w = xf.shape[-3:]
-        xf = xf.reshape(Cc, h, w)
-        tf = _f32(target).reshape(Cc, OH - 2 * crop, OW - 2 * crop)
-        lib = L.load()
-        scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(Cc), dtype=torch.float64, device=xf.device)
-        loss = _loss_buffer(out, xf.device)
-        with _timed("upcos_loss_fwd"):
-            L.check(lib.nefes_upcos_loss_fwd(Cc, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"), _chk(scratch, "scratch", torch.float64),
-                                             _chk(loss, "loss"), _stream()), "nefes_upcos_loss_fwd")
-        ctx.save_for_backward(xf, tf, scratch)
-        ctx.cfg = (x.shape, OH, OW, crop)
-        cos = scratch[:4 * Cc].view(Cc, 4)[:, 3]
-        ctx.set_materialize_grads(False)                  # no zero-filled gradient for `cos` in the backward
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
-
-    @staticmethod
-    def backward(ctx, g, _g_cos):
-        if g is None:
-            return (None,) * 6
-        xf, tf, scratch = ctx.saved_tensors
-        shape, OH, OW, crop = ctx.cfg
-        Cc, h, w = xf.shape
-        gf = _f32(g).reshape(1)
-        tmp = torch.empty(Cc, OH - 2 * crop, w, device=xf.device)
-        g_x = torch.empty_like(xf)
-        (fx, cx, wx, T), (fy, cy, wy, _) = bicubic_gather_tables(h, w, OH, OW, crop, xf.device)
-        with _timed("upcos_loss_bwd"):
-            L.check(L.load().nefes_upcos_loss_bwd(Cc, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"), _chk(scratch, "scratch", torch.float64),
-                                                  _chk(gf, "g_loss"), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), fy.data_ptr(), cy.data_ptr(),
-                                                  wy.data_ptr(), T, _chk(tmp, "tmp"), _chk(g_x, "g_x"), _stream()), "nefes_upcos_loss_bwd")
-        return g_x.reshape(shape), None, None, None, None, None
-
-
-class MaskedUpsampledCosineLoss(torch.autograd.Function):
-    """UpsampledCosineLoss for G groups with a uint8 mask [G, OH-2crop, OW-2crop] of the up-sampled, cropped pixels: MaskedCosineFeatureLoss
-    of the up-sampled image without the up-sampled image.  One-pass kernels only: sum_p m_p up_p^2 does not separate into the two axes, so
-    there is no prepared-target (Gram) form."""
-
-    @staticmethod
-    def forward(ctx, x, target, mask, OH, OW, crop, groups, out=None):
-        xf = _f32(x)
-        GC, h, w = xf.shape[-3:]
-        G = _groups_of(GC, groups, "upsampled_cosine_loss")
-        if xf.numel() != GC * h * w:
-            raise ValueError(f"nefes_amd: features {tuple(x.shape)} are not [C,h,w] (or [1,C,h,w]) maps")
-        CH, CW = OH - 2 * crop, OW - 2 * crop
-        xf = xf.reshape(GC, h, w)
-        tf = _f32(target).reshape(GC, CH, CW)
-        mk = _loss_mask(mask, G, (CH, CW), xf.device, "upsampled_cosine_loss")
-        lib = L.load()
-        scratch = torch.empty(lib.nefes_cosine_loss_scratch_doubles(GC), dtype=torch.float64, device=xf.device)
-        loss = _loss_buffer(out, xf.device)
-        with _timed("upcos_loss_masked_fwd"):
-            L.check(lib.nefes_upcos_loss_masked_fwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
-                                                    _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
-                                                    _chk(loss, "loss"), _stream()), "nefes_upcos_loss_masked_fwd")
-        ctx.save_for_backward(xf, tf, mk, scratch)
-        ctx.cfg = (x.shape, OH, OW, crop, G)
-        cos = scratch[:4 * GC].view(GC, 4)[:, 3]
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
-
-    @staticmethod
-    def backward(ctx, g, _g_cos):
-        if g is None:
-            return (None,) * 8
-        xf, tf, mk, scratch = ctx.saved_tensors
-        shape, OH, OW, crop, G = ctx.cfg
-        GC, h, w = xf.shape
-        gf = _f32(g).reshape(1)
-        tmp = torch.empty(GC, OH - 2 * crop, w, device=xf.device)
-        g_x = torch.empty_like(xf)
-        (fx, cx, wx, T), (fy, cy, wy, _) = bicubic_gather_tables(h, w, OH, OW, crop, xf.device)
-        with _timed("upcos_loss_masked_bwd"):
-            L.check(L.load().nefes_upcos_loss_masked_bwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
-                                                         _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
-                                                         _chk(gf, "g_loss"), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), fy.data_ptr(),
-                                                         cy.data_ptr(), wy.data_ptr(), T, _chk(tmp, "tmp"), _chk(g_x, "g_x"), _stream()),
-                    "nefes_upcos_loss_masked_bwd")
-        return (g_x.reshape(shape),) + (None,) * 7
-
-
-def upsampled_cosine_loss(x, target, size, crop=0, return_cos=False, out=None, groups=1, mask=None):
-    """1 - mean over channels of the cosine similarity (over pixels) between the bicubically up-sampled, cropped x and target.
-    `out`, `groups` and `mask` (uint8 [groups, OH-2crop, OW-2crop]: of the up-sampled, cropped pixels) as in cosine_feature_loss."""
-    if mask is not None:
-        loss, cos = MaskedUpsampledCosineLoss.apply(x, target, mask, int(size[0]), int(size[1]), int(crop), int(groups), out)
-        return (loss, cos) if return_cos else loss
-    G = _groups_of(x.shape[-3], groups, "upsampled_cosine_loss")
-    if G > 1 and out is not None:
-        raise ValueError("nefes_amd: upsampled_cosine_loss: `out` takes the kernel's own value; with groups > 1 and no mask the sum over "
-                         "the groups is formed after it")
-    loss, cos = UpsampledCosineLoss.apply(x, target, int(size[0]), int(size[1]), int(crop), out)
-    if G > 1:
-        loss = loss * float(G)
-    return (loss, cos) if return_cos else loss
-
-
-class PixelCosineLoss(torch.autograd.Function):
-    """feature_loss (dm/DFM_pose_refine.py:211-233) with per_pixel=True on [G*C, ...] maps: per group 1 - mean over pixels of the cosine
-    similarity over the C channels, summed over the G groups; two launches forward, one backward (to `a` only)."""
-
-    @staticmethod
-    def forward(ctx, a, b, groups, out=None):
-        G = int(groups)
-        if G < 1 or a.shape[0] % G:
-            raise ValueError(f"nefes_amd: {a.shape[0]} leading channels do not split into {groups} groups")
-        Cc = a.shape[0] // G
-        af, bf = _f32(a).reshape(G, Cc, -1), _f32(b).reshape(G, Cc, -1)
-        if af.shape != bf.shape:
-            raise ValueError(f"nefes_amd: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
-        lib = L.load()
-        P = af.shape[2]
-        scratch = torch.empty(lib.nefes_pixcos_scratch_doubles(G, P), dtype=torch.float64, device=af.device)
-        loss = _loss_buffer(out, af.device)
-        with _timed("pixcos_loss_fwd"):
-            L.check(lib.nefes_pixcos_loss_fwd(G, Cc, P, _chk(af, "a"), _chk(bf, "b"), _chk(scratch, "scratch", torch.float64),
-                                              _chk(loss, "loss"), _stream()), "nefes_pixcos_loss_fwd")
-        ctx.save_for_backward(af, bf, scratch)
-        ctx.shape = a.shape
-        cos = scratch[:G]                                 # float64 mean cosine similarity per group (a view of the scratch)
-        ctx.set_materialize_grads(False)                  # no zero-filled gradient for `cos` in the backward
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
-
-    @staticmethod
-    def backward(ctx, g, _g_cos):
-        if g is None:
-            return (None,) * 4
-        af, bf, scratch = ctx.saved_tensors
-        gf = _f32(g).reshape(1)
-        g_a = torch.empty_like(af)
-        with _timed("pixcos_loss_bwd"):
-            L.check(L.load().nefes_pixcos_loss_bwd(af.shape[0], af.shape[1], af.shape[2], _chk(af, "a"), _chk(bf, "b"),
-                                                   _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), _chk(g_a, "g_a"), _stream()),
-                    "nefes_pixcos_loss_bwd")
-        return g_a.reshape(ctx.shape), None, None, None
-
-
-class MaskedPixelCosineLoss(torch.autograd.Function):
-    """masked_feature_loss (dm/DFM_pose_refine.py:257-288) with per_pixel=True: PixelCosineLoss with the mean over each group's VALID
-    pixels (uint8 mask [G, pixels]); a group without one gives NaN, as the reference's mean of an empty tensor."""
-
-    @staticmethod
-    def forward(ctx, a, b, mask, groups, out=None):
-        G = _groups_of(a.shape[0], groups, "pixel_cosine_loss")
-        Cc = a.shape[0] // G
-        af, bf = _f32(a).reshape(G, Cc, -1), _f32(b).reshape(G, Cc, -1)
-        if af.shape != bf.shape:
-            raise ValueError(f"nefes_amd: feature maps of different shapes: {tuple(a.shape)} vs {tuple(b.shape)}")
-        mk = _loss_mask(mask, G, a.shape[1:], af.device, "pixel_cosine_loss")
-        lib = L.load()
-        P = af.shape[2]
-        scratch = torch.empty(lib.nefes_pixcos_masked_scratch_doubles(G, P), dtype=torch.float64, device=af.device)
-        loss = _loss_buffer(out, af.device)
-        with _timed("pixcos_loss_masked_fwd"):
-            L.check(lib.nefes_pixcos_loss_masked_fwd(G, Cc, P, _chk(af, "a"), _chk(bf, "b"), _chk(mk, "mask", torch.uint8),
-                                                     _chk(scratch, "scratch", torch.float64), _chk(loss, "loss"), _stream()),
-                    "nefes_pixcos_loss_masked_fwd")
-        ctx.save_for_backward(af, bf, mk, scratch)
-        ctx.shape = a.shape
-        cos = scratch[:G]
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
-
-    @staticmethod
-    def backward(ctx, g, _g_cos):
-        if g is None:
-            return (None,) * 5
-        af, bf, mk, scratch = ctx.saved_tensors
-        gf = _f32(g).reshape(1)
-        g_a = torch.empty_like(af)
-        with _timed("pixcos_loss_masked_bwd"):
-            L.check(L.load().nefes_pixcos_loss_masked_bwd(af.shape[0], af.shape[1], af.shape[2], _chk(af, "a"), _chk(bf, "b"),
-                                                          _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
-                                                          _chk(gf, "g_loss"), _chk(g_a, "g_a"), _stream()), "nefes_pixcos_loss_masked_bwd")
-        return g_a.reshape(ctx.shape), None, None, None, None
-
-
-def pixel_cosine_loss(a, b, groups=1, return_cos=False, out=None, mask=None):
-    """The per-pixel feature loss (`--per_pixel`): a, b [groups * C, ...]; per group 1 - mean over pixels of the cosine similarity over
-    its C channels (torch.nn.CosineSimilarity(dim=0, eps=1e-6)), summed over the groups -- every group's value and gradient are what a
-    call on that group alone gives.  `return_cos` adds the per-group mean cosines (float64, no gradient); `out` as in
-    cosine_feature_loss.  `mask`: uint8 [groups, ...pixels]; the mean is over the group's pixels with mask != 0 (values at the others are
-    never read, their gradient is exactly 0); None: today's unmasked kernels."""
-    if mask is not None:
-        loss, cos = MaskedPixelCosineLoss.apply(a, b, mask, groups, out)
-        return (loss, cos) if return_cos else loss
-    loss, cos = PixelCosineLoss.apply(a, b, groups, out)
-    return (loss, cos) if return_cos else loss
-
-
-class UpsampledPixelCosineLoss(torch.autograd.Function):
-    """pixel_cosine_loss(bicubic_upsample(x, size, crop), target, groups) for x [groups * C, h, w] (or [1, ., h, w]) without the
-    up-sampled image: csrc/refine.hip uppixcos kernels.  There is no prepared-target form of this loss (the normalisation is per pixel)."""
-
-    @staticmethod
-    def forward(ctx, x, target, OH, OW, crop, groups, out=None):
-        xf = _f32(x)
-        GC, h, w = xf.shape[-3:]
-        G = int(groups)
-        if G < 1 or GC % G or xf.numel() != GC * h * w:
-            raise ValueError(f"nefes_amd: features {tuple(x.shape)} do not split into {groups} groups of [C,h,w] maps")
-        xf = xf.reshape(GC, h, w)
-        tf = _f32(target).reshape(GC, OH - 2 * crop, OW - 2 * crop)
-        lib = L.load()
-        scratch = torch.empty(lib.nefes_uppixcos_scratch_doubles(G, OH, OW, crop), dtype=torch.float64, device=xf.device)
-        loss = _loss_buffer(out, xf.device)
-        with _timed("uppixcos_loss_fwd"):
-            L.check(lib.nefes_uppixcos_loss_fwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
-                                                _chk(scratch, "scratch", torch.float64), _chk(loss, "loss"), _stream()), "nefes_uppixcos_loss_fwd")
-        ctx.save_for_backward(xf, tf, scratch)
-        ctx.cfg = (x.shape, OH, OW, crop, G)
-        cos = scratch[:G]
-        ctx.set_materialize_grads(False)                  # no zero-filled gradient for `cos` in the backward
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
-
-    @staticmethod
-    def backward(ctx, g, _g_cos):
-        if g is None:
-            return (None,) * 7
-        xf, tf, scratch = ctx.saved_tensors
-        shape, OH, OW, crop, G = ctx.cfg
-        GC, h, w = xf.shape
-        gf = _f32(g).reshape(1)
-        tmp = torch.empty(GC, OH - 2 * crop, w, device=xf.device)
-        g_x = torch.empty_like(xf)
-        (fx, cx, wx, T), (fy, cy, wy, _) = bicubic_gather_tables(h, w, OH, OW, crop, xf.device)
-        with _timed("uppixcos_loss_bwd"):
-            L.check(L.load().nefes_uppixcos_loss_bwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
-                                                     _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), fx.data_ptr(), cx.data_ptr(),
-                                                     wx.data_ptr(), fy.data_ptr(), cy.data_ptr(), wy.data_ptr(), T, _chk(tmp, "tmp"),
-                                                     _chk(g_x, "g_x"), _stream()), "nefes_uppixcos_loss_bwd")
-        return g_x.reshape(shape), None, None, None, None, None, None
-
-
-class MaskedUpsampledPixelCosineLoss(torch.autograd.Function):
-    """UpsampledPixelCosineLoss with a uint8 mask [G, OH-2crop, OW-2crop] of the up-sampled, cropped pixels (MaskedPixelCosineLoss of the
-    up-sampled image without the up-sampled image)."""
-
-    @staticmethod
-    def forward(ctx, x, target, mask, OH, OW, crop, groups, out=None):
-        xf = _f32(x)
-        GC, h, w = xf.shape[-3:]
-        G = int(groups)
-        if G < 1 or GC % G or xf.numel() != GC * h * w:
-            raise ValueError(f"nefes_amd: features {tuple(x.shape)} do not split into {groups} groups of [C,h,w] maps")
-        CH, CW = OH - 2 * crop, OW - 2 * crop
-        xf = xf.reshape(GC, h, w)
-        tf = _f32(target).reshape(GC, CH, CW)
-        mk = _loss_mask(mask, G, (CH, CW), xf.device, "upsampled_pixel_cosine_loss")
-        lib = L.load()
-        scratch = torch.empty(lib.nefes_uppixcos_masked_scratch_doubles(G, OH, OW, crop), dtype=torch.float64, device=xf.device)
-        loss = _loss_buffer(out, xf.device)
-        with _timed("uppixcos_loss_masked_fwd"):
-            L.check(lib.nefes_uppixcos_loss_masked_fwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
-                                                       _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
-                                                       _chk(loss, "loss"), _stream()), "nefes_uppixcos_loss_masked_fwd")
-        ctx.save_for_backward(xf, tf, mk, scratch)
-        ctx.cfg = (x.shape, OH, OW, crop, G)
-        cos = scratch[:G]
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
-
-    @staticmethod
-    def backward(ctx, g, _g_cos):
-        if g is None:
-            return (None,) * 8
-        xf, tf, mk, scratch = ctx.saved_tensors
-        shape, OH, OW, crop, G = ctx.cfg
-        GC, h, w = xf.shape
-        gf = _f32(g).reshape(1)
-        tmp = torch.empty(GC, OH - 2 * crop, w, device=xf.device)
-        g_x = torch.empty_like(xf)
-        (fx, cx, wx, T), (fy, cy, wy, _) = bicubic_gather_tables(h, w, OH, OW, crop, xf.device)
-        with _timed("uppixcos_loss_masked_bwd"):
-            L.check(L.load().nefes_uppixcos_loss_masked_bwd(G, GC // G, h, w, OH, OW, crop, _chk(xf, "x"), _chk(tf, "target"),
-                                                            _chk(mk, "mask", torch.uint8), _chk(scratch, "scratch", torch.float64),
-                                                            _chk(gf, "g_loss"), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), fy.data_ptr(),
-                                                            cy.data_ptr(), wy.data_ptr(), T, _chk(tmp, "tmp"), _chk(g_x, "g_x"), _stream()),
-                    "nefes_uppixcos_loss_masked_bwd")
-        return (g_x.reshape(shape),) + (None,) * 7
-
-
-def upsampled_pixel_cosine_loss(x, target, size, crop=0, groups=1, return_cos=False, out=None, mask=None):
-    """pixel_cosine_loss of the bicubically up-sampled, cropped x against target, one pass each way.  `out` as in cosine_feature_loss;
-    `mask` (uint8 [groups, OH-2crop, OW-2crop]: of the up-sampled, cropped pixels) as in pixel_cosine_loss."""
-    if mask is not None:
-        loss, cos = MaskedUpsampledPixelCosineLoss.apply(x, target, mask, int(size[0]), int(size[1]), int(crop), int(groups), out)
-        return (loss, cos) if return_cos else loss
-    loss, cos = UpsampledPixelCosineLoss.apply(x, target, int(size[0]), int(size[1]), int(crop), int(groups), out)
-    return (loss, cos) if return_cos else loss
-
-
 _GRAMS = {}
 
 
@@ -2264,13 +2007,13 @@ def bicubic_gram(n_in, n_out, o0, n_win, device):
     return t
 
 
-UPCOS_GRAM_LDS_MAX = 96 * 1024          # csrc/refine.hip NEFES_UPCOS_GRAM_LDS_MAX
+UPCOS_GRAM_LDS_MAX = 96 * 1024          # csrc/feature_loss.hip NEFES_UPCOS_GRAM_LDS_MAX
 
 
 class UpcosTarget:
     """What upsampled_cosine_loss needs of a FIXED target [C, OH-2crop, OW-2crop] (the refinement loop's: one target for all
     iterations of an image): Tt = Uy^T target Ux [C,h,w], |target|^2 per channel, and the Gram matrices of the two axes.  `update(target)`
-    refills the same buffers (a captured graph keeps reading them).  csrc/refine.hip upcos_prep_* / upcos_gram_*."""
+    refills the same buffers (a captured graph keeps reading them).  csrc/feature_loss.hip upcos_prep_* / upcos_gram_*."""
 
     def __init__(self, C, h, w, OH, OW, crop, device):
         self.C, self.h, self.w, self.OH, self.OW, self.crop = int(C), int(h), int(w), int(OH), int(OW), int(crop)
@@ -2299,7 +2042,7 @@ class UpcosTarget:
 
 
 class UpsampledCosineLossPrepared(torch.autograd.Function):
-    """UpsampledCosineLoss against a prepared target (UpcosTarget): two small launches forward, one backward, on [C,h,w] data only."""
+    """upsampled_cosine_loss (FeatureLoss, "upcos") against a prepared target (UpcosTarget): two small launches forward, one backward, on [C,h,w] data only."""
 
     @staticmethod
     def forward(ctx, x, prep, out=None):
@@ -2318,10 +2061,7 @@ class UpsampledCosineLossPrepared(torch.autograd.Function):
                                              _chk(pmat, "pmat", torch.float64), _chk(loss, "loss"), _stream()), "nefes_upcos_gram_fwd")
         ctx.save_for_backward(scratch, pmat)
         ctx.prep, ctx.shape = prep, x.shape
-        cos = scratch[:4 * prep.C].view(prep.C, 4)[:, 3]
-        ctx.set_materialize_grads(False)                  # no zero-filled gradient for `cos` in the backward
-        ctx.mark_non_differentiable(cos)
-        return loss, cos
+        return _loss_outputs(ctx, loss, scratch, False, 1, prep.C)
 
     @staticmethod
     def backward(ctx, g, _g_cos):

@@ -149,7 +149,7 @@ class PoseRefiner:
 
     FUSED_UPSAMPLED_LOSS = True      # False: bicubic up-sampling and cosine loss as separate kernels (the tests compare the two)
     # The loop's target is fixed for all iterations of an image: its share of the up-sampled loss (Uy^T target Ux, |target|^2) is
-    # computed when the target is set and an iteration runs on [C,h,w] data only (ops.UpcosTarget; csrc/refine.hip upcos_gram_*).
+    # computed when the target is set and an iteration runs on [C,h,w] data only (ops.UpcosTarget; csrc/feature_loss.hip upcos_gram_*).
     # False: the one-pass kernels that read the whole target every iteration (the tests compare the two).
     PREPARED_TARGET = os.environ.get("NEFES_PREPARED_TARGET", "1") != "0"
     # Where the factored feature head renders the fine pass (ops.RenderFineFH: frozen width-128 network at test time), the head is not
@@ -289,13 +289,6 @@ class PoseRefiner:
                              pixels=self.pixels, **self.kw, **self._camera())
         return ex["feat_map"].t()
 
-    def _sparse_loss(self):
-        """_loss of PoseRefiner(sparse=K): the feature loss of the K rendered features against self.target [C, K] -- per channel over the
-        pixels, or per pixel over the channels -- on the existing loss kernels; masked: over the pixels with self.mask != 0."""
-        op = ops.pixel_cosine_loss if self.per_pixel else ops.cosine_feature_loss
-        loss = op(self._sparse_features(), self.target, out=self.loss, mask=self.mask)
-        return loss, loss.detach()
-
     def _fused(self):
         """pose -> render -> affine colour transform -> fusion CNN: the fused features [B, C, h, w] of the current state."""
         B = self.B
@@ -357,76 +350,49 @@ class PoseRefiner:
         kernel writes its value straight into the static buffer self.loss (`out=`: no 4-byte copy launch per iteration); everything
         else (images=B, the torch expressions) returns its own tensor and the callers copy it."""
         if self.sparse is not None:
-            return self._sparse_loss()
-        B = self.B
-        out = self.loss if (B == 1 and self.fused_glue) else None
-        fused = self._fused()
-        if self.masked:
-            return self._masked_loss(fused, out)
-        if self.upsample and self.fused_glue and not self.per_pixel and self.FUSED_UPSAMPLED_LOSS:
-            # up-sampling, crop and feature loss in one pass each way: the 34 MB up-sampled image is never written (ops.upsampled_cosine_loss)
-            if self._uses_prepared_target():
-                mean_loss, cos = ops.upsampled_cosine_loss_prepared(fused.reshape(B * self.C, self.h, self.w), self._sync_upcos(), return_cos=True, out=out)
-            else:
-                mean_loss, cos = ops.upsampled_cosine_loss(fused.reshape(B * self.C, self.h, self.w),
-                                                           self.target.reshape(B * self.C, self.H - 20, self.W - 20), (self.H, self.W), crop=10,
-                                                           return_cos=True, out=out)
-            if B > 1:
-                return mean_loss * float(B), (1.0 - cos.view(B, self.C).mean(1)).float()
-            return mean_loss, mean_loss.detach()
-        if self.fused_glue and self.per_pixel:
-            # the per-pixel loss (`--per_pixel`) on its own kernels; up-sampled, again without the up-sampled image.  No prepared-target
-            # form: the normalisation is per pixel (csrc/refine.hip), so self.target is read on every iteration
-            if self.upsample and self.FUSED_UPSAMPLED_LOSS:
-                loss, cos = ops.upsampled_pixel_cosine_loss(fused.reshape(B * self.C, self.h, self.w),
-                                                            self.target.reshape(B * self.C, self.H - 20, self.W - 20), (self.H, self.W), crop=10,
-                                                            groups=B, return_cos=True, out=out)
-            else:
-                if self.upsample:
-                    fused = ops.bicubic_upsample(fused, (self.H, self.W), crop=10)
-                loss, cos = ops.pixel_cosine_loss(fused.reshape(B * self.C, -1), self.target.reshape(B * self.C, -1), groups=B, return_cos=True,
-                                                  out=out)
-            return loss, ((1.0 - cos).float() if B > 1 else loss.detach())
-        if self.upsample:
-            if self.fused_glue:
-                fused = ops.bicubic_upsample(fused, (self.H, self.W), crop=10)
-            else:
-                fused = ops.bicubic_upsample(fused, (self.H, self.W))[:, :, 10:-10, 10:-10]
-        if B > 1:
-            # sum over images of (1 - mean_c cos) = B x (1 - mean over all B*C channels): one launch pair for the whole batch
-            mean_loss, cos = ops.cosine_feature_loss(fused.reshape(B * self.C, -1), self.target.reshape(B * self.C, -1), return_cos=True)
-            return mean_loss * float(B), (1.0 - cos.view(B, self.C).mean(1)).float()
-        # (a view where possible: fused[0] costs a 34 MB zero fill and a copy in the backward)
-        fused = fused.view(fused.shape[1:]) if fused.is_contiguous() else fused[0]
-        if self.fused_glue:
-            loss = ops.cosine_feature_loss(fused, self.target, out=out)
-        else:
-            loss = feature_loss(fused, self.target, per_pixel=self.per_pixel)
-        return loss, loss.detach()
-
-    def _masked_loss(self, fused, out):
-        """_loss's last step with self.mask (PoseRefiner(masked=True)): the masked one-pass kernels of the form the loop runs (up-sampled
-        or not, per pixel or per channel; `groups=B`: the kernels' value is already the sum over the images), or with fused_glue=False
-        the torch expression (masked_feature_loss).  self.target and self.mask are read on every iteration."""
+            # the K rendered features [C, K] against self.target [C, K]; masked: over the pixels with self.mask != 0
+            return self._library_loss(self._sparse_features(), self.target, self.mask, self.loss)
         B, C = self.B, self.C
-        if not self.fused_glue:
+        fused = self._fused()
+        if not self.fused_glue:                            # one image, the torch expressions
             if self.upsample:
                 fused = ops.bicubic_upsample(fused, (self.H, self.W))[:, :, 10:-10, 10:-10]
-            loss = masked_feature_loss(fused[0], self.target, self.mask, per_pixel=self.per_pixel)
+            if self.masked:
+                loss = masked_feature_loss(fused[0], self.target, self.mask, per_pixel=self.per_pixel)
+            else:
+                # (a view where possible: fused[0] costs a 34 MB zero fill and a copy in the backward)
+                fused = fused.view(fused.shape[1:]) if fused.is_contiguous() else fused[0]
+                loss = feature_loss(fused, self.target, per_pixel=self.per_pixel)
             return loss, loss.detach()
+        out = self.loss if B == 1 else None
+        if self._uses_prepared_target():
+            mean_loss, cos = ops.upsampled_cosine_loss_prepared(fused.reshape(B * C, self.h, self.w), self._sync_upcos(), return_cos=True, out=out)
+            if B > 1:
+                return mean_loss * float(B), (1.0 - cos.view(B, C).mean(1)).float()
+            return mean_loss, mean_loss.detach()
         if self.upsample and self.FUSED_UPSAMPLED_LOSS:
+            # up-sampling, crop and feature loss in one pass each way: the 34 MB up-sampled image is never written
+            return self._library_loss(fused.reshape(B * C, self.h, self.w), self.target.reshape(B * C, self.H - 20, self.W - 20), self.mask, out,
+                                      upsampled=True)
+        if self.upsample:
+            fused = ops.bicubic_upsample(fused, (self.H, self.W), crop=10)
+        return self._library_loss(fused.reshape(B * C, -1), self.target.reshape(B * C, -1), None if self.mask is None else self.mask.view(B, -1), out)
+
+    def _library_loss(self, feats, target, mask, out, upsampled=False):
+        """_loss's last step on the library's one-pass loss kernels, in the form the loop runs: per channel or per pixel
+        (self.per_pixel), of feats [B*C, pixels] or -- `upsampled` -- of feats [B*C, h, w] up-sampled and cropped inside the kernels,
+        over all pixels or those with mask != 0.  `groups=B`: the value is already the sum over the images.  self.target (and the
+        mask) are read on every iteration: no form here has a prepared target (csrc/feature_loss.hip says why)."""
+        B = self.B
+        if upsampled:
             op = ops.upsampled_pixel_cosine_loss if self.per_pixel else ops.upsampled_cosine_loss
-            loss, cos = op(fused.reshape(B * C, self.h, self.w), self.target.reshape(B * C, self.H - 20, self.W - 20), (self.H, self.W), crop=10,
-                           groups=B, return_cos=True, out=out, mask=self.mask)
+            loss, cos = op(feats, target, (self.H, self.W), crop=10, groups=B, return_cos=True, out=out, mask=mask)
         else:
-            if self.upsample:
-                fused = ops.bicubic_upsample(fused, (self.H, self.W), crop=10)
             op = ops.pixel_cosine_loss if self.per_pixel else ops.cosine_feature_loss
-            loss, cos = op(fused.reshape(B * C, -1), self.target.reshape(B * C, -1), groups=B, return_cos=True, out=out,
-                           mask=self.mask.view(B, -1))
+            loss, cos = op(feats, target, groups=B, return_cos=True, out=out, mask=mask)
         if B == 1:
             return loss, loss.detach()
-        return loss, (1.0 - (cos if self.per_pixel else cos.view(B, C).mean(1))).float()
+        return loss, (1.0 - (cos if self.per_pixel else cos.view(B, self.C).mean(1))).float()
 
     def _set_mask(self, mask):
         """The image's validity mask into self.mask, IN PLACE (a captured iteration keeps reading the same buffer): thresholded `> 0`

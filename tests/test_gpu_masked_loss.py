@@ -1,4 +1,4 @@
-"""The masked feature-loss kernels (`--semantic`; csrc/refine.hip MASKED instances; the `mask=` keyword of ops.cosine_feature_loss,
+"""The masked feature-loss kernels (`--semantic`; csrc/feature_loss.hip MASKED instances; the `mask=` keyword of ops.cosine_feature_loss,
 ops.upsampled_cosine_loss, ops.pixel_cosine_loss, ops.upsampled_pixel_cosine_loss) against the reference's expression -- compact both maps
 to the valid pixels (`fr[:, valid]`), then CosineSimilarity -- in float64 on the CPU from the same fp32 inputs.
 

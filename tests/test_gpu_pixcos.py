@@ -1,4 +1,4 @@
-"""The per-pixel feature loss kernels (`--per_pixel`; csrc/refine.hip pixcos_* / uppixcos_*, ops.pixel_cosine_loss /
+"""The per-pixel feature loss kernels (`--per_pixel`; csrc/feature_loss.hip pixcos_* / uppixcos_*, ops.pixel_cosine_loss /
 ops.upsampled_pixel_cosine_loss) against the torch expression in float64 on the CPU.
 
 "Equal to float64" throughout is the shared rule parity_log.check(tol=T, factor=1.5): e_hip <= max(T, 1.5 e_ref), where the truth is

@@ -263,7 +263,7 @@ def test_upsampled_cosine_loss_equals_separate_kernels(C, h, w, ts):
                                               (4, 6, 70, 24, 280, 1)])
 def test_prepared_target_loss_equals_one_pass_kernels_and_torch(C, h, w, OH, OW, crop):
     """ops.upsampled_cosine_loss_prepared (the fixed target folded through the up-sampling once: <up, t> = <x, Uy^T t Ux>,
-    |up|^2 = <x, Gy x Gx>; csrc/refine.hip upcos_gram_*) == ops.upsampled_cosine_loss == torch's Upsample + CosineSimilarity in
+    |up|^2 = <x, Gy x Gx>; csrc/feature_loss.hip upcos_gram_*) == ops.upsampled_cosine_loss == torch's Upsample + CosineSimilarity in
     float64 (DFM_APR_refine.py:114-131), value, per-channel similarities and gradient; integer and non-integer scales, with and
     without a crop, one all-zero channel (the eps clamp), and a second target through the same buffers (what a captured graph reads)."""
     from nefes_amd import ops

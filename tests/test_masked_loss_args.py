@@ -1,4 +1,4 @@
-"""What a CPU can check of the masked feature losses (`--semantic`; csrc/refine.hip MASKED instances): the exports, the scratch queries,
+"""What a CPU can check of the masked feature losses (`--semantic`; csrc/feature_loss.hip MASKED instances): the exports, the scratch queries,
 every refusal of the entry points (they return before any HIP call: the pointers are dummies that are never dereferenced), the mask
 validation of the four ops functions (raised before the first device pointer is taken, so CPU tensors show it), and PoseRefiner's
 `masked=` / `mask=`.  The GPU twins are tests/test_gpu_masked_loss.py and tests/test_gpu_refine_masked.py."""

@@ -1,4 +1,4 @@
-"""What a CPU can check of the per-pixel feature loss (`--per_pixel`; csrc/refine.hip pixcos_* / uppixcos_*): the exports, the scratch
+"""What a CPU can check of the per-pixel feature loss (`--per_pixel`; csrc/feature_loss.hip pixcos_* / uppixcos_*): the exports, the scratch
 queries, every refusal of the entry points (they return before any HIP call: the pointers are dummies that are never dereferenced),
 the `out=` validation of the two ops functions, and that PoseRefiner no longer refuses per_pixel=True with pose_model= or images=B.
 The GPU twins are tests/test_gpu_pixcos.py and tests/test_gpu_refine_pp.py."""

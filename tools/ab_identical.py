@@ -24,7 +24,14 @@ prints, instead, the digests of every output of nefes_composite_fwd and nefes_co
 tests/composite_ref.py's case list -- ragged, deep, four-per-lane, every upstream alone, the channel split, and the misaligned cases on
 each of their three pointer offsets: every forward map and the whole g_raw_t -- and of every output of ops.coarse_sample (csrc/sample_pdf.hip)
 at Nc = 64, 128, 256 on a shared depth row and on per-ray depths.  Output buffers carry eight rays of padding, are filled with a fixed
-pattern before the call and digested whole, byte for byte (NaN sign and payload bits included)."""
+pattern before the call and digested whole, byte for byte (NaN sign and payload bits included).
+    python tools/ab_identical.py --feature-loss [--time]
+prints, instead, the digests of the loss, the cosines and the whole gradient of the four feature losses (ops.cosine_feature_loss,
+upsampled_cosine_loss, pixel_cosine_loss, upsampled_pixel_cosine_loss; csrc/feature_loss.hip) at LOW_SHAPES / UP_SHAPES of
+tests/test_gpu_masked_loss.py and the loop's shape -- one shape of each has three groups -- without a mask, with a random one and with
+all ones, and of ops.upsampled_cosine_loss_prepared at four shapes.  Only those five functions are called, so the same file runs in an
+earlier commit's tree (copy it there).  --time: then, per op at the loop's shape, the median and min / max of 200 calls' device time
+each way, around the entry-point call (ops.TIMERS) and around the whole eager call ('# time' lines)."""
 import ctypes as C
 import hashlib, os, sys
 import torch
@@ -276,13 +283,17 @@ def run_train():
 
 
 # (tag, PoseRefiner arguments, what is run): both modes replayed and eager, every route of the up-sampled loss, the torch glue, a batch,
-# a second image through an existing graph (state reset in place), and both stream drivers (rounds of two included)
+# a second image through an existing graph (state reset in place), both stream drivers (rounds of two included), and the per-pixel and
+# masked losses on the up-sampled one-pass kernels and at low resolution
 REFINE_CASES = (("mode3 graph", dict(graph=True), "twice"),
                 ("mode3 eager", dict(graph=False), "once"),
                 ("mode3 upsample prepared", dict(graph=True, upsample=True, plain=True, prepared=True), "once"),
                 ("mode3 upsample one-pass", dict(graph=True, upsample=True, plain=True, prepared=False), "once"),
                 ("mode3 upsample hist world", dict(graph=True, upsample=True), "once"),
                 ("mode3 torch glue", dict(graph=False, fused_glue=False), "once"),
+                ("mode3 upsample per_pixel", dict(graph=True, upsample=True, plain=True, per_pixel=True), "once"),
+                ("mode3 upsample masked", dict(graph=True, upsample=True, plain=True, masked=True), "once"),
+                ("mode3 masked per_pixel", dict(graph=True, masked=True, per_pixel=True), "once"),
                 ("mode3 images=2", dict(graph=True, images=2), "batch"),
                 ("mode2 graph", dict(graph=True, apr=0), "apr twice"),
                 ("mode2 eager", dict(graph=False, apr=0), "apr twice"),
@@ -353,7 +364,9 @@ def run_refine():
         job = lambda k: (T(gd["init_c2w"][k]), target, hist)
         if what in ("once", "twice"):
             r = refiner(shared, **kw)
-            show(tag, r.refine(*job(0), iters=iters))
+            # (a masked refiner gets a mask: about 60 % of the target's pixels valid)
+            mask = (torch.rand(target.shape[-2:], generator=torch.Generator().manual_seed(5)) < 0.6) if kw.get("masked") else None
+            show(tag, r.refine(*job(0), iters=iters, **({} if mask is None else {"mask": mask})))
             if what == "twice":
                 show(tag + ", next image", r.refine(*job(3), iters=iters))
         elif what == "batch":
@@ -418,7 +431,86 @@ def run_composite():
             out(f"coarse_sample Nc{nc} Ni{ni} N{n} {what}", z_fine=z_fine, z_samples=z_samples, weights=weights)
 
 
+def run_feature_loss(timed):
+    os.environ.setdefault("NEFES_PARITY_LOG", os.devnull)      # (the test modules' shared helpers record parity numbers; not here)
+    from tests.test_gpu_masked_loss import LOOP_SHAPE, LOW_SHAPES, UP_SHAPES, low_case, up_case
+    UPSTREAM, FILL = 3.0, 0.123
+    loop_low = (LOOP_SHAPE[0], LOOP_SHAPE[1], (LOOP_SHAPE[4] - 2 * LOOP_SHAPE[6]) * (LOOP_SHAPE[5] - 2 * LOOP_SHAPE[6]))
+    low_ops = (("cosine", ops.cosine_feature_loss), ("pixcos", ops.pixel_cosine_loss))
+    up_ops = (("upcos", ops.upsampled_cosine_loss), ("uppixcos", ops.upsampled_pixel_cosine_loss))
+
+    def calls():
+        """(tag, function of the features alone -> (loss, cos), features) of every case: each form at every shape (one of them three
+        groups) without a mask, with a random one and with all ones; the prepared form at four shapes"""
+        for shapes, fns, case in ((LOW_SHAPES + [loop_low], low_ops, low_case), (UP_SHAPES + [LOOP_SHAPE], up_ops, up_case)):
+            for shape in shapes:
+                for kind in (None, "random", "ones"):
+                    x, t, m = (v.to(dev) for v in case(*shape, kind or "ones"))
+                    kw = dict(groups=shape[0], return_cos=True, mask=None if kind is None else m)
+                    if len(shape) == 7:
+                        kw.update(size=shape[4:6], crop=shape[6])
+                    for name, fn in fns:
+                        yield f"{name} {shape} mask {kind}", (lambda v, fn=fn, t=t, kw=kw: fn(v, t, **kw)), x
+        for shape in UP_SHAPES[:3] + [LOOP_SHAPE]:
+            x, t, _ = (v.to(dev) for v in up_case(*shape, "ones"))
+            prep = ops.UpcosTarget(*shape[1:], dev)
+            if not prep.fits:
+                print(f"# prepared {shape}: beyond the Gram kernel's LDS ceiling")
+                continue
+            prep.update(t)
+            yield f"prepared {shape}", (lambda v, prep=prep: ops.upsampled_cosine_loss_prepared(v, prep, return_cos=True)), x
+
+    def both_ways(fn, x):
+        """(loss, cos, the whole gradient buffer, was it pre-filled?).  The ops allocate their gradient themselves, so the pre-fill is
+        best effort: a block of the gradient's size is filled with FILL and freed just before the backward, and where the caching
+        allocator hands the backward that very block (checked by address) what its kernels leave unwritten shows in the digest."""
+        xr = x.clone().requires_grad_()
+        loss, cos = fn(xr)
+        up = torch.tensor(UPSTREAM, device=dev)
+        pattern = torch.full_like(x, FILL)
+        where = pattern.data_ptr()
+        del pattern
+        (grad,) = torch.autograd.grad(loss, xr, up)
+        return loss, cos, grad, grad.data_ptr() == where
+
+    for tag, fn, x in calls():
+        loss, cos, grad, filled = both_ways(fn, x)
+        if not filled:
+            print(f"# {tag}: the gradient came in another block than the pre-filled one")
+        out(tag, loss=loss, cos=cos, grad=grad)
+    if not timed:
+        return
+    # per op at the loop's shape, 200 calls after 20, two brackets of HIP events each way: the one ops.TIMERS records around the
+    # entry-point call (the unmasked channel-wise loss has no key), and one around the whole eager call -- the same work on any two
+    # revisions of the host code, Python included.  Two decimals: the event clock's step shows in the min / max columns.
+    WARM, CALLS = 20, 200
+    for tag, fn, x in calls():
+        if str(LOOP_SHAPE) not in tag and str(loop_low) not in tag or "ones" in tag:
+            continue
+        ops.TIMERS, whole = {}, {"whole call fwd": [], "whole call bwd": []}
+        up = torch.tensor(UPSTREAM, device=dev)
+        for _ in range(WARM + CALLS):
+            xr = x.clone().requires_grad_()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+            loss, _ = fn(xr)
+            ev[1].record()
+            ev[2].record()
+            torch.autograd.grad(loss, xr, up)
+            ev[3].record()
+            whole["whole call fwd"].append((ev[0], ev[1]))
+            whole["whole call bwd"].append((ev[2], ev[3]))
+        torch.cuda.synchronize()
+        timers, ops.TIMERS = ops.TIMERS, None
+        for key, pairs in sorted(timers.items()) + sorted(whole.items()):
+            us = sorted(a.elapsed_time(b) * 1e3 for a, b in pairs[-CALLS:])
+            print(f"# time {tag:48s} {key:28s} median {us[len(us) // 2]:8.2f} us  min {us[0]:8.2f}  max {us[-1]:8.2f}", flush=True)
+
+
 print("# lib", os.environ.get("NEFES_HIP_LIB") or "shipped", "ABI", L.ABI_VERSION)
+if "--feature-loss" in sys.argv[1:]:
+    run_feature_loss("--time" in sys.argv[1:])
+    sys.exit(0)
 if "--composite" in sys.argv[1:]:
     run_composite()
     sys.exit(0)
