@@ -1293,13 +1293,15 @@ class HashGrid:
 
     `table` is a plain fp32 tensor [entries, 2] that does not require grad: the grid is frozen and every path runs as it always did.
     `grid.table.requires_grad_(True)` makes it trainable -- HashGridEncode then returns d loss / d table (nefes_hashgrid_bwd_table),
-    render() routes the grid through the separate encode + field launches, and `grid.parameters()` hands it to an optimiser."""
+    render() routes the grid through the separate encode + field launches, and `grid.parameters()` hands it to an optimiser.
+    `n_levels=1` is one level of scale `base_resolution - 1`; a geometry the library refuses raises RuntimeError."""
 
     def __init__(self, bound, table=None, n_levels=16, log2_hashmap_size=19, base_resolution=16, max_resolution=2048,
                  device="cuda"):
         import math
-        self.desc = L.NefesHashGridDesc(n_levels, 2, log2_hashmap_size, base_resolution,
-                                        math.exp(math.log(max_resolution / base_resolution) / (n_levels - 1)), float(bound))
+        # a single level has no growth factor: its scale is base_resolution - 1 and max_resolution is not used
+        growth = math.exp(math.log(max_resolution / base_resolution) / (n_levels - 1)) if n_levels > 1 else 1.0
+        self.desc = L.NefesHashGridDesc(n_levels, 2, log2_hashmap_size, base_resolution, growth, float(bound))
         self.n_out = 2 * n_levels
         n = L.load().nefes_hashgrid_table_entries(self.desc)
         if n == 0:
