@@ -114,7 +114,8 @@ int nefes_pack_device(const float* flat, int64_t n_params, const uint32_t* map, 
 
 /* ---- rays (script/models/ray_utils.py) ------------------------------------------------------- */
 /* get_rays (:5-16) + viewdirs = d/|d| (rendering.py:217) for image rows [row0, row0+nrows).
- * c2w: dev, 12 floats row-major 3x4.  Outputs dev [nrows*W, 3]. */
+ * c2w: dev, 12 floats row-major 3x4.  Outputs dev [nrows*W, 3].  The three pairs below are instances of one kernel body
+ * (csrc/rays.hip): this one takes its camera, (focal, focal, (float)(W*.5), (float)(H*.5)), as launch arguments. */
 int nefes_raygen_fwd(int H, int W, float focal, const float* c2w, int row0, int nrows, float* rays_o, float* rays_d,
                      float* viewdirs, void* stream);
 /* backward of the above: g_c2w[12] (dev) = sum over rays.  g_* may be NULL (treated as zero).
@@ -125,8 +126,8 @@ int nefes_raygen_bwd(int H, int W, float focal, const float* c2w, int row0, int 
 /* The same for a pinhole camera with intrinsics: dirs = [(col - cx)/fx, -(row - cy)/fy, -1].
  * intr: dev, 4 floats (fx, fy, cx, cy), READ FROM DEVICE MEMORY when the kernel runs -- not a launch argument, so that a captured graph
  * follows a camera updated in place between replays and the backward can return its gradient.  The values cannot be checked here
- * (fx = 0 behaves as focal = 0 does above).  With intr = (focal, focal, (float)(W*.5), (float)(H*.5)) the outputs -- rays and the twelve
- * pose-gradient numbers -- equal nefes_raygen_fwd / _bwd's bit for bit.
+ * (fx = 0 behaves as focal = 0 does above).  One kernel body with the pair above: with intr = (focal, focal, (float)(W*.5), (float)(H*.5))
+ * the outputs -- rays and the twelve pose-gradient numbers -- equal nefes_raygen_fwd / _bwd's bit for bit.
  * backward: g_c2w[12] and, unless NULL, g_intr[4] = d L / d (fx, fy, cx, cy) (dev) = sums over rays.  g_rays_o / g_rays_d / g_viewdirs may
  * be NULL (treated as zero).  workspace: dev, >= nefes_raygen_k_bwd_workspace(nrows*W) bytes. */
 int nefes_raygen_k_fwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, float* rays_o, float* rays_d,
@@ -136,8 +137,8 @@ int nefes_raygen_k_bwd(int H, int W, const float* intr, const float* c2w, int ro
                        const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr, void* stream);
 /* The same rays at a LIST of pixels instead of the frame's grid.  px: dev, float32 [n, 2] rows (x, y) = (column, row) in get_rays' own
  * pixel convention -- an integer coordinate is that pixel, there is no half-pixel offset; fractional coordinates and points outside the
- * frame are legal.  px and intr are both read from device memory when the kernel runs.  Outputs dev [n, 3].  The arithmetic per ray is
- * nefes_raygen_k_fwd's operation for operation (one kernel body): with px the row-major integer pixels of rows [row0, row0+nrows) the
+ * frame are legal.  px and intr are both read from device memory when the kernel runs.  Outputs dev [n, 3].  One kernel body with
+ * nefes_raygen_k_fwd / _bwd: with px the row-major integer pixels of rows [row0, row0+nrows) the
  * rays and the 12 + 4 gradient numbers equal nefes_raygen_k_fwd / _bwd's bit for bit.  backward: as nefes_raygen_k_bwd (g_* and g_intr
  * may be NULL); workspace: dev, >= nefes_raygen_px_bwd_workspace(n) bytes (= nefes_raygen_k_bwd_workspace(n)). */
 int nefes_raygen_px_fwd(int n, const float* px, const float* intr, const float* c2w, float* rays_o, float* rays_d, float* viewdirs,

@@ -5,20 +5,71 @@
 #include "../../include/nefes_hip.h"
 #include "wave.h"
 
-__device__ __forceinline__ void pixel_dir(int H, int W, float focal, int row, int col, float (&dc)[3]) {
-    // dirs = [(i - W/2)/f, -(j - H/2)/f, -1]   (ray_utils.py:10; no half-pixel offset)
-    dc[0] = __fdiv_rn(__fsub_rn((float)col, (float)(W * .5)), focal);
-    dc[1] = -__fdiv_rn(__fsub_rn((float)row, (float)(H * .5)), focal);
+// ---- get_rays + viewdirs, forward and backward: one kernel body over two small functors ----------------------------------------
+// Where ray idx's pixel (x, y) = (column, row) comes from:
+//   GridPixels: the frame's rows from row0 on, row-major (raygen, raygen_k);
+//   ListPixels: a float32 [n, 2] list in device memory, read when the kernel runs like the device camera (raygen_px).  Any value is
+//               legal: an integer coordinate is that pixel (no half-pixel offset), fractions and points outside the frame are rays too.
+// Where the camera (fx, fy, cx, cy) comes from:
+//   ValueCamera:  four launch arguments (raygen: fx = fy = focal, cx = (float)(W*.5), cy = (float)(H*.5), formed by the host).  The
+//                 backward forms the twelve pose sums (kSums = 12).
+//   DeviceCamera: intr[4] READ FROM DEVICE MEMORY when the kernel runs, never passed by value (raygen_k, raygen_px): a captured
+//                 iteration follows a camera that is updated in place between replays, and the backward can hand a gradient to it --
+//                 four more sums, d L / d (fx, fy, cx, cy) (kSums = 16).
+// Both cameras feed the same operations in the same order, so at intr = (focal, focal, (float)(W*.5), (float)(H*.5)) the rays and the
+// twelve pose sums of the two are equal bit for bit, as are a grid's and the list of its row-major integer pixels.  Three pairs are
+// instantiated: (grid, value), (grid, device), (list, device).  A kernel takes its camera as Camera::Arg and builds the functor from it.
+struct GridPixels {
+    int W, row0;
+    __device__ __forceinline__ void operator()(int idx, float& x, float& y) const {
+        x = (float)(idx % W);
+        y = (float)(row0 + idx / W);
+    }
+};
+struct ListPixels {
+    const float* px;
+    __device__ __forceinline__ void operator()(int idx, float& x, float& y) const {
+        x = px[(size_t)idx * 2];
+        y = px[(size_t)idx * 2 + 1];
+    }
+};
+struct ValueCamera {
+    using Arg = ValueCamera;
+    static constexpr int kSums = 12;
+    float fx_, fy_, cx_, cy_;
+    __device__ __forceinline__ float fx() const { return fx_; }
+    __device__ __forceinline__ float fy() const { return fy_; }
+    __device__ __forceinline__ float cx() const { return cx_; }
+    __device__ __forceinline__ float cy() const { return cy_; }
+};
+struct DeviceCamera {
+    using Arg = const float* __restrict__;   // (restrict has to stand on the kernel's own argument to reach the compiler)
+    static constexpr int kSums = 16;
+    const float* intr;
+    __device__ __forceinline__ float fx() const { return intr[0]; }
+    __device__ __forceinline__ float fy() const { return intr[1]; }
+    __device__ __forceinline__ float cx() const { return intr[2]; }
+    __device__ __forceinline__ float cy() const { return intr[3]; }
+};
+
+template <class Camera>
+__device__ __forceinline__ void pixel_dir(const Camera& cam, float x, float y, float (&dc)[3]) {
+    // dirs = [(x - cx)/fx, -(y - cy)/fy, -1]   (ray_utils.py:10; no half-pixel offset)
+    dc[0] = __fdiv_rn(__fsub_rn(x, cam.cx()), cam.fx());
+    dc[1] = -__fdiv_rn(__fsub_rn(y, cam.cy()), cam.fy());
     dc[2] = -1.f;
 }
 
-__global__ __launch_bounds__(256) void raygen_fwd_kernel(int H, int W, float focal, const float* __restrict__ c2w, int row0,
-                                                         int n, float* rays_o, float* rays_d, float* viewdirs) {
+template <class Pixels, class Camera>
+__global__ __launch_bounds__(256) void raygen_fwd_kernel(Pixels pixel, typename Camera::Arg arg, const float* __restrict__ c2w, int n,
+                                                         float* rays_o, float* rays_d, float* viewdirs) {
+    const Camera cam{arg};
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= n) return;
-    const int row = row0 + idx / W, col = idx % W;
+    float x, y;
+    pixel(idx, x, y);
     float dc[3];
-    pixel_dir(H, W, focal, row, col, dc);
+    pixel_dir(cam, x, y, dc);
     float d[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {   // rays_d[a] = sum_b dirs[b] * c2w[a][b]  (:13)
@@ -35,18 +86,29 @@ __global__ __launch_bounds__(256) void raygen_fwd_kernel(int H, int W, float foc
     }
 }
 
-// stage 1: per-block partial of the 12 pose-gradient sums (f64), stage 2: fixed-order final sum.
-__global__ __launch_bounds__(256) void raygen_bwd_kernel(int H, int W, float focal, const float* __restrict__ c2w, int row0,
-                                                         int n, const float* g_o, const float* g_d, const float* g_v,
-                                                         double* partial) {
-    __shared__ double red[4][12];
-    double s[12];
+// stage 1: per-block partial of the kSums sums (f64) -- the 12 pose-gradient sums, then, for a device camera, d L/d (fx, fy, cx, cy);
+// stage 2: fixed-order final sum.  With gd the gradient reaching rays_d and R_a column a of the rotation:
+//     d dirs_0 / d fx = -(x - cx)/fx^2 = -dirs_0/fx     d dirs_0 / d cx = -1/fx
+//     d dirs_1 / d fy = +(y - cy)/fy^2 = -dirs_1/fy     d dirs_1 / d cy = +1/fy
+template <class Pixels, class Camera>
+__global__ __launch_bounds__(256) void raygen_bwd_kernel(Pixels pixel, typename Camera::Arg arg, const float* __restrict__ c2w, int n,
+                                                         const float* g_o, const float* g_d, const float* g_v, double* partial) {
+    constexpr int K = Camera::kSums;
+    const Camera cam{arg};
+    __shared__ double red[4][K];
+    double s[K];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) s[k] = 0.0;
+    for (int k = 0; k < K; ++k) s[k] = 0.0;
+    float ifx = 0.f, ify = 0.f;
+    if constexpr (K == 16) {
+        ifx = __fdiv_rn(1.f, cam.fx());
+        ify = __fdiv_rn(1.f, cam.fy());
+    }
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
-        const int row = row0 + idx / W, col = idx % W;
+        float x, y;
+        pixel(idx, x, y);
         float dc[3];
-        pixel_dir(H, W, focal, row, col, dc);
+        pixel_dir(cam, x, y, dc);
         float gd[3] = {0.f, 0.f, 0.f};
         if (g_d)
 #pragma unroll
@@ -70,23 +132,32 @@ __global__ __launch_bounds__(256) void raygen_bwd_kernel(int H, int W, float foc
             for (int b = 0; b < 3; ++b) s[a * 4 + b] += (double)gd[a] * (double)dc[b];
             if (g_o) s[a * 4 + 3] += (double)g_o[(size_t)idx * 3 + a];
         }
+        if constexpr (K == 16) {   // gd . R_0 and gd . R_1 in fp32, the camera's factor in fp32, the product and the sum in f64
+            const float r0 = __fadd_rn(__fadd_rn(__fmul_rn(gd[0], c2w[0]), __fmul_rn(gd[1], c2w[4])), __fmul_rn(gd[2], c2w[8]));
+            const float r1 = __fadd_rn(__fadd_rn(__fmul_rn(gd[0], c2w[1]), __fmul_rn(gd[1], c2w[5])), __fmul_rn(gd[2], c2w[9]));
+            s[12] += (double)(-__fmul_rn(dc[0], ifx)) * (double)r0;   // fx
+            s[13] += (double)(-__fmul_rn(dc[1], ify)) * (double)r1;   // fy
+            s[14] += (double)(-ifx) * (double)r0;                     // cx
+            s[15] += (double)ify * (double)r1;                        // cy
+        }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) {
+    for (int k = 0; k < K; ++k) {
         const double v = wave_sum(s[k]);
         if (lane == 0) red[wave][k] = v;
     }
     __syncthreads();
-    if (threadIdx.x < 12) partial[(size_t)blockIdx.x * 12 + threadIdx.x] =
+    if (threadIdx.x < K) partial[(size_t)blockIdx.x * K + threadIdx.x] =
         ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
-__global__ void raygen_bwd_final(const double* partial, int nblocks, float* g_c2w) {
+__global__ void raygen_bwd_final(const double* partial, int nblocks, int nsums, float* g_c2w, float* g_intr) {
     const int k = threadIdx.x;
-    if (k >= 12) return;
+    if (k >= nsums) return;
     double s = 0.0;
-    for (int b = 0; b < nblocks; ++b) s += partial[(size_t)b * 12 + k];
-    g_c2w[k] = (float)s;
+    for (int b = 0; b < nblocks; ++b) s += partial[(size_t)b * nsums + k];
+    if (k < 12) g_c2w[k] = (float)s;
+    else if (g_intr) g_intr[k - 12] = (float)s;
 }
 
 static int raygen_blocks(int n) {
@@ -94,199 +165,72 @@ static int raygen_blocks(int n) {
     return b > 1024 ? 1024 : (b < 1 ? 1 : b);
 }
 
+template <class Pixels, class Camera>
+static int raygen_fwd_launch(Pixels pixel, typename Camera::Arg cam, const float* c2w, int n, float* rays_o, float* rays_d, float* viewdirs,
+                             void* stream) {
+    raygen_fwd_kernel<Pixels, Camera><<<dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(pixel, cam, c2w, n, rays_o, rays_d,
+                                                                                                  viewdirs);
+    return (int)hipGetLastError();
+}
+template <class Pixels, class Camera>
+static int raygen_bwd_launch(Pixels pixel, typename Camera::Arg cam, const float* c2w, int n, const float* g_rays_o, const float* g_rays_d,
+                             const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr, void* stream) {
+    const int nb = raygen_blocks(n);
+    hipStream_t st = (hipStream_t)stream;
+    raygen_bwd_kernel<Pixels, Camera><<<dim3(nb), dim3(256), 0, st>>>(pixel, cam, c2w, n, g_rays_o, g_rays_d, g_viewdirs,
+                                                                     (double*)workspace);
+    raygen_bwd_final<<<dim3(1), dim3(64), 0, st>>>((const double*)workspace, nb, Camera::kSums, g_c2w, g_intr);
+    return (int)hipGetLastError();
+}
+static size_t raygen_workspace(int n_rays, int sums) { return (size_t)raygen_blocks(n_rays) * sums * sizeof(double); }
+// the focal camera, centred: the double product and the one conversion the focal kernels made per ray, made once
+static ValueCamera focal_camera(int H, int W, float focal) { return ValueCamera{focal, focal, (float)(W * .5), (float)(H * .5)}; }
+
 extern "C" int nefes_raygen_fwd(int H, int W, float focal, const float* c2w, int row0, int nrows, float* rays_o,
                                 float* rays_d, float* viewdirs, void* stream) {
     if (!c2w || !rays_o || !rays_d || H <= 0 || W <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > H) return NEFES_E_BADARG;
-    const int n = nrows * W;
-    hipLaunchKernelGGL(raygen_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, H, W, focal, c2w, row0, n,
-                       rays_o, rays_d, viewdirs);
-    return (int)hipGetLastError();
+    return raygen_fwd_launch<GridPixels, ValueCamera>(GridPixels{W, row0}, focal_camera(H, W, focal), c2w, nrows * W, rays_o, rays_d,
+                                                      viewdirs, stream);
 }
-extern "C" size_t nefes_raygen_bwd_workspace(int n_rays) { return (size_t)raygen_blocks(n_rays) * 12 * sizeof(double); }
+extern "C" size_t nefes_raygen_bwd_workspace(int n_rays) { return raygen_workspace(n_rays, ValueCamera::kSums); }
 extern "C" int nefes_raygen_bwd(int H, int W, float focal, const float* c2w, int row0, int nrows, const float* g_rays_o,
                                 const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w,
                                 void* stream) {
     if (!c2w || !workspace || !g_c2w || H <= 0 || W <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > H) return NEFES_E_BADARG;
-    const int n = nrows * W, nb = raygen_blocks(n);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(raygen_bwd_kernel, dim3(nb), dim3(256), 0, st, H, W, focal, c2w, row0, n, g_rays_o, g_rays_d,
-                       g_viewdirs, (double*)workspace);
-    hipLaunchKernelGGL(raygen_bwd_final, dim3(1), dim3(64), 0, st, (const double*)workspace, nb, g_c2w);
-    return (int)hipGetLastError();
+    return raygen_bwd_launch<GridPixels, ValueCamera>(GridPixels{W, row0}, focal_camera(H, W, focal), c2w, nrows * W, g_rays_o, g_rays_d,
+                                                      g_viewdirs, workspace, g_c2w, nullptr, stream);
 }
 
-// ---- pinhole intrinsics (fx, fy, cx, cy) ---------------------------------------------------------
-// The camera is READ FROM DEVICE MEMORY when the kernel runs (intr[4] = fx, fy, cx, cy), never passed by value: a captured
-// iteration follows a camera that is updated in place between replays, and the backward can hand a gradient to it.  With
-// intr = (focal, focal, (float)(W*.5), (float)(H*.5)) every operation below is the one the focal kernels above perform, in the
-// same order, so rays and the twelve pose sums are theirs bit for bit.
-//
-// Where ray idx's pixel (x, y) = (column, row) comes from -- the per-ray bodies below are written once over it:
-//   GridPixels: the frame's rows from row0 on, row-major (raygen_k);
-//   ListPixels: a float32 [n, 2] list in device memory, read when the kernel runs like the camera (raygen_px).  Any value is legal:
-//               an integer coordinate is that pixel (no half-pixel offset), fractions and points outside the frame are rays too.
-struct GridPixels {
-    int W, row0;
-    __device__ __forceinline__ void operator()(int idx, float& x, float& y) const {
-        x = (float)(idx % W);
-        y = (float)(row0 + idx / W);
-    }
-};
-struct ListPixels {
-    const float* px;
-    __device__ __forceinline__ void operator()(int idx, float& x, float& y) const {
-        x = px[(size_t)idx * 2];
-        y = px[(size_t)idx * 2 + 1];
-    }
-};
-
-__device__ __forceinline__ void pixel_dir_k(const float* __restrict__ intr, float x, float y, float (&dc)[3]) {
-    // dirs = [(x - cx)/fx, -(y - cy)/fy, -1]
-    dc[0] = __fdiv_rn(__fsub_rn(x, intr[2]), intr[0]);
-    dc[1] = -__fdiv_rn(__fsub_rn(y, intr[3]), intr[1]);
-    dc[2] = -1.f;
-}
-
-template <class Pixels>
-__global__ __launch_bounds__(256) void raygen_k_fwd_kernel(Pixels pixel, const float* __restrict__ intr, const float* __restrict__ c2w,
-                                                           int n, float* rays_o, float* rays_d, float* viewdirs) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n) return;
-    float x, y;
-    pixel(idx, x, y);
-    float dc[3];
-    pixel_dir_k(intr, x, y, dc);
-    float d[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float p0 = __fmul_rn(dc[0], c2w[a * 4 + 0]), p1 = __fmul_rn(dc[1], c2w[a * 4 + 1]),
-                    p2 = __fmul_rn(dc[2], c2w[a * 4 + 2]);
-        d[a] = __fadd_rn(__fadd_rn(p0, p1), p2);
-    }
-    const float nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        rays_o[(size_t)idx * 3 + a] = c2w[a * 4 + 3];
-        rays_d[(size_t)idx * 3 + a] = d[a];
-        if (viewdirs) viewdirs[(size_t)idx * 3 + a] = __fdiv_rn(d[a], nrm);
-    }
-}
-
-// stage 1: per-block partial of 16 sums (f64) -- the 12 pose-gradient sums of raygen_bwd_kernel, formed exactly as there, then
-// d L/d (fx, fy, cx, cy); stage 2: fixed-order final sum.  With gd the gradient reaching rays_d and R_a column a of the rotation:
-//     d dirs_0 / d fx = -(x - cx)/fx^2 = -dirs_0/fx     d dirs_0 / d cx = -1/fx
-//     d dirs_1 / d fy = +(y - cy)/fy^2 = -dirs_1/fy     d dirs_1 / d cy = +1/fy
-template <class Pixels>
-__global__ __launch_bounds__(256) void raygen_k_bwd_kernel(Pixels pixel, const float* __restrict__ intr, const float* __restrict__ c2w,
-                                                           int n, const float* g_o, const float* g_d, const float* g_v,
-                                                           double* partial) {
-    __shared__ double red[4][16];
-    double s[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s[k] = 0.0;
-    const float fx = intr[0], fy = intr[1];
-    const float ifx = __fdiv_rn(1.f, fx), ify = __fdiv_rn(1.f, fy);
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
-        float x, y;
-        pixel(idx, x, y);
-        float dc[3];
-        pixel_dir_k(intr, x, y, dc);
-        float gd[3] = {0.f, 0.f, 0.f};
-        if (g_d)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) gd[a] = g_d[(size_t)idx * 3 + a];
-        if (g_v) {   // v = d/|d|  =>  d L/d d += (g - v (v.g)) / |d|
-            float d[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-                d[a] = __fadd_rn(__fadd_rn(__fmul_rn(dc[0], c2w[a * 4]), __fmul_rn(dc[1], c2w[a * 4 + 1])), __fmul_rn(dc[2], c2w[a * 4 + 2]));
-            const float nrm = __fsqrt_rn(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            const float gv0 = g_v[(size_t)idx * 3], gv1 = g_v[(size_t)idx * 3 + 1], gv2 = g_v[(size_t)idx * 3 + 2];
-            const float v0 = d[0] / nrm, v1 = d[1] / nrm, v2 = d[2] / nrm;
-            const float dot = v0 * gv0 + v1 * gv1 + v2 * gv2;
-            gd[0] += (gv0 - v0 * dot) / nrm;
-            gd[1] += (gv1 - v1 * dot) / nrm;
-            gd[2] += (gv2 - v2 * dot) / nrm;
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) s[a * 4 + b] += (double)gd[a] * (double)dc[b];
-            if (g_o) s[a * 4 + 3] += (double)g_o[(size_t)idx * 3 + a];
-        }
-        // gd . R_0 and gd . R_1 in fp32, the camera's factor in fp32, the product and the sum in f64
-        const float r0 = __fadd_rn(__fadd_rn(__fmul_rn(gd[0], c2w[0]), __fmul_rn(gd[1], c2w[4])), __fmul_rn(gd[2], c2w[8]));
-        const float r1 = __fadd_rn(__fadd_rn(__fmul_rn(gd[0], c2w[1]), __fmul_rn(gd[1], c2w[5])), __fmul_rn(gd[2], c2w[9]));
-        s[12] += (double)(-__fmul_rn(dc[0], ifx)) * (double)r0;   // fx
-        s[13] += (double)(-__fmul_rn(dc[1], ify)) * (double)r1;   // fy
-        s[14] += (double)(-ifx) * (double)r0;                     // cx
-        s[15] += (double)ify * (double)r1;                        // cy
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const double v = wave_sum(s[k]);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 16) partial[(size_t)blockIdx.x * 16 + threadIdx.x] =
-        ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-}
-__global__ void raygen_k_bwd_final(const double* partial, int nblocks, float* g_c2w, float* g_intr) {
-    const int k = threadIdx.x;
-    if (k >= 16) return;
-    double s = 0.0;
-    for (int b = 0; b < nblocks; ++b) s += partial[(size_t)b * 16 + k];
-    if (k < 12) g_c2w[k] = (float)s;
-    else if (g_intr) g_intr[k - 12] = (float)s;
-}
-
-template <class Pixels>
-static int raygen_k_fwd_launch(Pixels pixel, const float* intr, const float* c2w, int n, float* rays_o, float* rays_d, float* viewdirs,
-                               void* stream) {
-    hipLaunchKernelGGL(raygen_k_fwd_kernel<Pixels>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pixel, intr, c2w, n,
-                       rays_o, rays_d, viewdirs);
-    return (int)hipGetLastError();
-}
-template <class Pixels>
-static int raygen_k_bwd_launch(Pixels pixel, const float* intr, const float* c2w, int n, const float* g_rays_o, const float* g_rays_d,
-                               const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr, void* stream) {
-    const int nb = raygen_blocks(n);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(raygen_k_bwd_kernel<Pixels>, dim3(nb), dim3(256), 0, st, pixel, intr, c2w, n, g_rays_o, g_rays_d, g_viewdirs,
-                       (double*)workspace);
-    hipLaunchKernelGGL(raygen_k_bwd_final, dim3(1), dim3(64), 0, st, (const double*)workspace, nb, g_c2w, g_intr);
-    return (int)hipGetLastError();
-}
-
+// pinhole intrinsics intr[4] = (fx, fy, cx, cy) in device memory (DeviceCamera)
 extern "C" int nefes_raygen_k_fwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, float* rays_o,
                                   float* rays_d, float* viewdirs, void* stream) {
     if (!intr || !c2w || !rays_o || !rays_d || H <= 0 || W <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > H)
         return NEFES_E_BADARG;
-    return raygen_k_fwd_launch(GridPixels{W, row0}, intr, c2w, nrows * W, rays_o, rays_d, viewdirs, stream);
+    return raygen_fwd_launch<GridPixels, DeviceCamera>(GridPixels{W, row0}, intr, c2w, nrows * W, rays_o, rays_d, viewdirs, stream);
 }
-extern "C" size_t nefes_raygen_k_bwd_workspace(int n_rays) { return (size_t)raygen_blocks(n_rays) * 16 * sizeof(double); }
+extern "C" size_t nefes_raygen_k_bwd_workspace(int n_rays) { return raygen_workspace(n_rays, DeviceCamera::kSums); }
 extern "C" int nefes_raygen_k_bwd(int H, int W, const float* intr, const float* c2w, int row0, int nrows, const float* g_rays_o,
                                   const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr,
                                   void* stream) {
     if (!intr || !c2w || !workspace || !g_c2w || H <= 0 || W <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > H)
         return NEFES_E_BADARG;
-    return raygen_k_bwd_launch(GridPixels{W, row0}, intr, c2w, nrows * W, g_rays_o, g_rays_d, g_viewdirs, workspace, g_c2w, g_intr,
-                               stream);
+    return raygen_bwd_launch<GridPixels, DeviceCamera>(GridPixels{W, row0}, intr, c2w, nrows * W, g_rays_o, g_rays_d, g_viewdirs, workspace,
+                                                       g_c2w, g_intr, stream);
 }
 
 // the same rays and sums at a list of pixels px [n, 2] = (x, y) in device memory (ListPixels)
 extern "C" int nefes_raygen_px_fwd(int n, const float* px, const float* intr, const float* c2w, float* rays_o, float* rays_d,
                                    float* viewdirs, void* stream) {
     if (!px || !intr || !c2w || !rays_o || !rays_d || n <= 0) return NEFES_E_BADARG;
-    return raygen_k_fwd_launch(ListPixels{px}, intr, c2w, n, rays_o, rays_d, viewdirs, stream);
+    return raygen_fwd_launch<ListPixels, DeviceCamera>(ListPixels{px}, intr, c2w, n, rays_o, rays_d, viewdirs, stream);
 }
 extern "C" size_t nefes_raygen_px_bwd_workspace(int n) { return nefes_raygen_k_bwd_workspace(n); }
 extern "C" int nefes_raygen_px_bwd(int n, const float* px, const float* intr, const float* c2w, const float* g_rays_o,
                                    const float* g_rays_d, const float* g_viewdirs, void* workspace, float* g_c2w, float* g_intr,
                                    void* stream) {
     if (!px || !intr || !c2w || !workspace || !g_c2w || n <= 0) return NEFES_E_BADARG;
-    return raygen_k_bwd_launch(ListPixels{px}, intr, c2w, n, g_rays_o, g_rays_d, g_viewdirs, workspace, g_c2w, g_intr, stream);
+    return raygen_bwd_launch<ListPixels, DeviceCamera>(ListPixels{px}, intr, c2w, n, g_rays_o, g_rays_d, g_viewdirs, workspace, g_c2w, g_intr,
+                                                       stream);
 }
 
 // ---- bilinear sample of a [C, H, W] map at a pixel list (the targets of a sparse feature loss) ----------------------------------

@@ -7,7 +7,7 @@ from nefes_amd import ops
 
 def get_rays(H, W, focal, c2w):
     """ray_utils.py:5-16.  Returns rays_o, rays_d [H,W,3] on the GPU, differentiable w.r.t. c2w."""
-    o, d, _ = ops.RayGen.apply(c2w.to("cuda"), int(H), int(W), float(focal), 0, int(H))
+    o, d, _ = ops.rays(c2w.to("cuda"), int(H), int(W), focal)
     return o.reshape(H, W, 3), d.reshape(H, W, 3)
 
 

@@ -74,52 +74,90 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------
 # rays
 # ---------------------------------------------------------------------------------------------
-def raygen_fwd(H, W, focal, c2w, row0=0, nrows=None):
-    nrows = H - row0 if nrows is None else nrows
+def _raygen_call(camera, pixels):
+    """Which of the three entry-point pairs serves (camera, pixels): (their stem, the number of rays, the arguments before c2w, the
+    arguments after it).  `camera`: a Python float (the focal length of a centred camera, a launch argument) or the float32 [4] device
+    tensor (fx, fy, cx, cy) the kernels read when they run (as_intrinsics).  `pixels`: (H, W, row0, nrows), rows of the frame's grid, or
+    the float32 [K, 2] device tensor of (x, y) (as_pixels)."""
+    if torch.is_tensor(pixels):
+        if not torch.is_tensor(camera):
+            raise ValueError("nefes_amd: the rays of a pixel list take their camera from device memory, not a focal length: pass "
+                             "intr=ops.as_intrinsics((focal, focal, W / 2, H / 2), device)")
+        n = pixels.shape[0]
+        return "nefes_raygen_px", n, (n, _px(pixels), _intr(camera)), ()
+    H, W, row0, nrows = pixels
+    if torch.is_tensor(camera):
+        return "nefes_raygen_k", nrows * W, (H, W, _intr(camera)), (row0, nrows)
+    return "nefes_raygen", nrows * W, (H, W, float(camera)), (row0, nrows)
+
+
+def _raygen_fwd(c2w, camera, pixels):
+    """-> (rays_o, rays_d, viewdirs), each [n, 3]."""
+    name, n, head, tail = _raygen_call(camera, pixels)
     c2w = _f32(c2w[:3, :4])
-    n = nrows * W
     o = torch.empty(n, 3, device=c2w.device)
     d = torch.empty_like(o)
     v = torch.empty_like(o)
-    L.check(L.load().nefes_raygen_fwd(H, W, float(focal), _chk(c2w, "c2w"), row0, nrows, _chk(o, "o"), _chk(d, "d"),
-                                      _chk(v, "v"), _stream()), "nefes_raygen_fwd")
+    L.check(getattr(L.load(), name + "_fwd")(*head, _chk(c2w, "c2w"), *tail, _chk(o, "o"), _chk(d, "d"), _chk(v, "v"), _stream()),
+            name + "_fwd")
     return o, d, v
 
 
-def raygen_bwd(H, W, focal, c2w, row0, nrows, g_o, g_d, g_v):
+def _raygen_bwd(c2w, camera, pixels, g_o, g_d, g_v, want_intr=True):
+    """-> (g_c2w [3,4], g_intr [4] or None): None for a focal length, and for a device camera when it is not wanted (the kernel then
+    gets g_intr = NULL)."""
+    name, n, head, tail = _raygen_call(camera, pixels)
     lib = L.load()
     c2w = _f32(c2w[:3, :4])
-    n = nrows * W
-    ws = torch.empty(lib.nefes_raygen_bwd_workspace(n), dtype=torch.uint8, device=c2w.device)
+    ws = torch.empty(getattr(lib, name + "_bwd_workspace")(n), dtype=torch.uint8, device=c2w.device)
     g = torch.empty(3, 4, device=c2w.device)
-    fix = lambda t: None if t is None else _f32(t)
-    g_o, g_d, g_v = fix(g_o), fix(g_d), fix(g_v)
-    L.check(lib.nefes_raygen_bwd(H, W, float(focal), _chk(c2w, "c2w"), row0, nrows, _chk(g_o, "g_o"), _chk(g_d, "g_d"),
-                                 _chk(g_v, "g_v"), _chk(ws, "ws", torch.uint8), _chk(g, "g_c2w"), _stream()),
-            "nefes_raygen_bwd")
-    return g
+    device_camera = torch.is_tensor(camera)
+    gk = torch.empty(4, device=c2w.device) if want_intr and device_camera else None
+    g_o, g_d, g_v = (None if t is None else _f32(t) for t in (g_o, g_d, g_v))
+    L.check(getattr(lib, name + "_bwd")(*head, _chk(c2w, "c2w"), *tail, _chk(g_o, "g_o"), _chk(g_d, "g_d"), _chk(g_v, "g_v"),
+                                        _chk(ws, "ws", torch.uint8), _chk(g, "g_c2w"), *((_chk(gk, "g_intr"),) if device_camera else ()),
+                                        _stream()), name + "_bwd")
+    return g, gk
+
+
+def raygen_fwd(H, W, focal, c2w, row0=0, nrows=None):
+    return _raygen_fwd(c2w, float(focal), (H, W, row0, H - row0 if nrows is None else nrows))
+
+
+def raygen_bwd(H, W, focal, c2w, row0, nrows, g_o, g_d, g_v):
+    return _raygen_bwd(c2w, float(focal), (H, W, row0, nrows), g_o, g_d, g_v)[0]
 
 
 class RayGen(torch.autograd.Function):
-    """get_rays + viewdirs (ray_utils.py:5-16, rendering.py:217) with the backward to the pose."""
+    """get_rays + viewdirs (ray_utils.py:5-16, rendering.py:217) for every camera and pixel set (`rays` below), with the backward to the
+    pose and -- when `intr` asks for it -- to (fx, fy, cx, cy).  The pixels are positions, not parameters: no gradient reaches them."""
 
     @staticmethod
-    def forward(ctx, c2w, H, W, focal, row0, nrows):
-        o, d, v = raygen_fwd(H, W, focal, c2w, row0, nrows)
-        ctx.save_for_backward(c2w)
-        ctx.geom = (H, W, focal, row0, nrows)
-        return o, d, v
+    def forward(ctx, c2w, intr, px, focal, grid):
+        ctx.save_for_backward(c2w, intr, px)
+        ctx.focal, ctx.grid = focal, grid
+        return _raygen_fwd(c2w, focal if intr is None else intr, grid if px is None else px)
 
     @staticmethod
     def backward(ctx, g_o, g_d, g_v):
-        (c2w,) = ctx.saved_tensors
-        H, W, focal, row0, nrows = ctx.geom
-        g = raygen_bwd(H, W, focal, c2w, row0, nrows, g_o, g_d, g_v)
-        if tuple(c2w.shape) == (3, 4) and c2w.dtype == torch.float32:
-            return g, None, None, None, None, None         # (the refinement loop's case: no zero fill + copy for a row that is not there)
-        out = torch.zeros_like(c2w)
-        out[:3, :4] = g
-        return out, None, None, None, None, None
+        c2w, intr, px = ctx.saved_tensors
+        g, gk = _raygen_bwd(c2w, ctx.focal if intr is None else intr, ctx.grid if px is None else px, g_o, g_d, g_v,
+                            want_intr=ctx.needs_input_grad[1])
+        if not (tuple(c2w.shape) == (3, 4) and c2w.dtype == torch.float32):     # (the refinement loop's 3x4 float32 pose: no zero
+            out = torch.zeros_like(c2w)                                         #  fill + copy for a row that is not there)
+            out[:3, :4] = g
+            g = out
+        return g, gk, None, None, None
+
+
+def rays(c2w, H, W, focal=None, intr=None, px=None, row0=0, nrows=None):
+    """(rays_o, rays_d, viewdirs), each [n, 3], of the pose c2w ([3,4] or [4,4]), differentiable w.r.t. it.  The camera is `intr`, the
+    float32 [4] device tensor (fx, fy, cx, cy) of as_intrinsics -- read from device memory by the kernels, and handed a gradient when it
+    requires one -- or, without it, the centred camera of the focal length `focal`.  The rays are those of the pixel list `px` (as_pixels;
+    needs `intr`) or, without it, of rows [row0, row0 + nrows) of the H x W frame, row-major."""
+    if intr is None and focal is None:
+        raise ValueError("nefes_amd: rays() needs a camera: focal= or intr=")
+    return RayGen.apply(c2w, intr, px, None if intr is not None else float(focal), (H, W, row0, H - row0 if nrows is None else nrows))
 
 
 def as_intrinsics(x, device):
@@ -164,54 +202,12 @@ def _intr(intr):
 
 def raygen_k_fwd(H, W, intr, c2w, row0=0, nrows=None):
     """raygen_fwd for the camera intr = (fx, fy, cx, cy), a float32 [4] DEVICE tensor the kernel reads when it runs."""
-    nrows = H - row0 if nrows is None else nrows
-    c2w = _f32(c2w[:3, :4])
-    n = nrows * W
-    o = torch.empty(n, 3, device=c2w.device)
-    d = torch.empty_like(o)
-    v = torch.empty_like(o)
-    L.check(L.load().nefes_raygen_k_fwd(H, W, _intr(intr), _chk(c2w, "c2w"), row0, nrows, _chk(o, "o"), _chk(d, "d"),
-                                        _chk(v, "v"), _stream()), "nefes_raygen_k_fwd")
-    return o, d, v
+    return _raygen_fwd(c2w, intr, (H, W, row0, H - row0 if nrows is None else nrows))
 
 
 def raygen_k_bwd(H, W, intr, c2w, row0, nrows, g_o, g_d, g_v, want_intr=True):
     """-> (g_c2w [3,4], g_intr [4] or None)."""
-    lib = L.load()
-    c2w = _f32(c2w[:3, :4])
-    n = nrows * W
-    ws = torch.empty(lib.nefes_raygen_k_bwd_workspace(n), dtype=torch.uint8, device=c2w.device)
-    g = torch.empty(3, 4, device=c2w.device)
-    gk = torch.empty(4, device=c2w.device) if want_intr else None
-    fix = lambda t: None if t is None else _f32(t)
-    g_o, g_d, g_v = fix(g_o), fix(g_d), fix(g_v)
-    L.check(lib.nefes_raygen_k_bwd(H, W, _intr(intr), _chk(c2w, "c2w"), row0, nrows, _chk(g_o, "g_o"), _chk(g_d, "g_d"),
-                                   _chk(g_v, "g_v"), _chk(ws, "ws", torch.uint8), _chk(g, "g_c2w"), _chk(gk, "g_intr"), _stream()),
-            "nefes_raygen_k_bwd")
-    return g, gk
-
-
-class RayGenK(torch.autograd.Function):
-    """RayGen for a pinhole camera with intrinsics: apply(c2w, intr, H, W, row0, nrows) -> (o, d, v), backward to the pose and -- when
-    `intr` asks for it -- to (fx, fy, cx, cy).  `intr` is read from device memory by the kernels (as_intrinsics)."""
-
-    @staticmethod
-    def forward(ctx, c2w, intr, H, W, row0, nrows):
-        o, d, v = raygen_k_fwd(H, W, intr, c2w, row0, nrows)
-        ctx.save_for_backward(c2w, intr)
-        ctx.geom = (H, W, row0, nrows)
-        return o, d, v
-
-    @staticmethod
-    def backward(ctx, g_o, g_d, g_v):
-        c2w, intr = ctx.saved_tensors
-        H, W, row0, nrows = ctx.geom
-        g, gk = raygen_k_bwd(H, W, intr, c2w, row0, nrows, g_o, g_d, g_v, want_intr=ctx.needs_input_grad[1])
-        if not (tuple(c2w.shape) == (3, 4) and c2w.dtype == torch.float32):
-            out = torch.zeros_like(c2w)
-            out[:3, :4] = g
-            g = out
-        return g, gk, None, None, None, None
+    return _raygen_bwd(c2w, intr, (H, W, row0, nrows), g_o, g_d, g_v, want_intr)
 
 
 def as_pixels(x, device):
@@ -253,50 +249,12 @@ def _px(px):
 def raygen_px_fwd(px, intr, c2w):
     """raygen_k_fwd at the pixel list px (as_pixels) instead of the frame's grid: (rays_o, rays_d, viewdirs), each [K, 3].  px and intr are
     float32 DEVICE tensors the kernel reads when it runs."""
-    c2w = _f32(c2w[:3, :4])
-    n = px.shape[0]
-    o = torch.empty(n, 3, device=c2w.device)
-    d = torch.empty_like(o)
-    v = torch.empty_like(o)
-    L.check(L.load().nefes_raygen_px_fwd(n, _px(px), _intr(intr), _chk(c2w, "c2w"), _chk(o, "o"), _chk(d, "d"), _chk(v, "v"), _stream()),
-            "nefes_raygen_px_fwd")
-    return o, d, v
+    return _raygen_fwd(c2w, intr, px)
 
 
 def raygen_px_bwd(px, intr, c2w, g_o, g_d, g_v, want_intr=True):
     """-> (g_c2w [3,4], g_intr [4] or None): raygen_k_bwd's 12 + 4 sums over the rays of px."""
-    lib = L.load()
-    c2w = _f32(c2w[:3, :4])
-    n = px.shape[0]
-    ws = torch.empty(lib.nefes_raygen_px_bwd_workspace(n), dtype=torch.uint8, device=c2w.device)
-    g = torch.empty(3, 4, device=c2w.device)
-    gk = torch.empty(4, device=c2w.device) if want_intr else None
-    fix = lambda t: None if t is None else _f32(t)
-    g_o, g_d, g_v = fix(g_o), fix(g_d), fix(g_v)
-    L.check(lib.nefes_raygen_px_bwd(n, _px(px), _intr(intr), _chk(c2w, "c2w"), _chk(g_o, "g_o"), _chk(g_d, "g_d"), _chk(g_v, "g_v"),
-                                    _chk(ws, "ws", torch.uint8), _chk(g, "g_c2w"), _chk(gk, "g_intr"), _stream()), "nefes_raygen_px_bwd")
-    return g, gk
-
-
-class RayGenPx(torch.autograd.Function):
-    """RayGenK at a pixel list: apply(c2w, intr, px) -> (o, d, v), each [K, 3]; backward to the pose and -- when `intr` asks for it -- to
-    (fx, fy, cx, cy).  The pixels are positions, not parameters: no gradient reaches them."""
-
-    @staticmethod
-    def forward(ctx, c2w, intr, px):
-        o, d, v = raygen_px_fwd(px, intr, c2w)
-        ctx.save_for_backward(c2w, intr, px)
-        return o, d, v
-
-    @staticmethod
-    def backward(ctx, g_o, g_d, g_v):
-        c2w, intr, px = ctx.saved_tensors
-        g, gk = raygen_px_bwd(px, intr, c2w, g_o, g_d, g_v, want_intr=ctx.needs_input_grad[1])
-        if not (tuple(c2w.shape) == (3, 4) and c2w.dtype == torch.float32):
-            out = torch.zeros_like(c2w)
-            out[:3, :4] = g
-            g = out
-        return g, gk, None
+    return _raygen_bwd(c2w, intr, px, g_o, g_d, g_v, want_intr)
 
 
 def sample_pixels(map, px, out=None):

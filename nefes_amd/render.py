@@ -2,7 +2,7 @@
 (script/models/rendering.py:23-243), executed by the HIP kernels of libnefes_hip.so.
 
 Kernel sequence of one render() at test time (perturb=0, test_time=True):
-    RayGen (get_rays + viewdirs)                 -> rays_o, rays_d, viewdirs          [grad -> c2w]
+    ops.rays (get_rays + viewdirs)               -> rays_o, rays_d, viewdirs          [grad -> c2w, intrinsics]
     coarse_depths                                -> z_coarse [N,Nc]
     field_fwd SIGMA (coarse net, no grad)        -> sigma [N,1,Nc]
     composite_fwd variant D                      -> weights [N,Nc]
@@ -290,22 +290,14 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
 
 
 def _rays_for(H, W, focal, c2w, c2w_staticcam, row_range, intr=None, px=None):
-    if px is not None:                                              # the K rays of a pixel list (ops.as_pixels) replace the grid
-        if intr is None:                                            # the centred camera of the focal kernels, as a device tensor
-            intr = torch.tensor([float(focal), float(focal), float(W * .5), float(H * .5)], dtype=torch.float32, device=_DEV)
-        rays_o, rays_d, viewdirs = ops.RayGenPx.apply(c2w.to(_DEV), intr, px)
-        if c2w_staticcam is not None:                               # the same pixels for both cameras
-            rays_o, rays_d, _ = ops.RayGenPx.apply(c2w_staticcam.to(_DEV), intr, px)
-        return rays_o, rays_d, viewdirs
+    """The rays of `c2w`: of the pixel list `px` (ops.as_pixels) when given, else of the frame's grid (`row_range` of it); through the
+    camera `intr` (ops.as_intrinsics; `focal` is then not read) when given, else the centred camera of `focal`."""
+    if px is not None and intr is None:                             # the centred camera of the focal kernels, as a device tensor
+        intr = torch.tensor([float(focal), float(focal), float(W * .5), float(H * .5)], dtype=torch.float32, device=_DEV)
     row0, nrows = (0, H) if row_range is None else row_range
-    if intr is not None:                                            # a camera with intrinsics (ops.as_intrinsics): `focal` is not read
-        rays_o, rays_d, viewdirs = ops.RayGenK.apply(c2w.to(_DEV), intr, H, W, row0, nrows)
-        if c2w_staticcam is not None:
-            rays_o, rays_d, _ = ops.RayGenK.apply(c2w_staticcam.to(_DEV), intr, H, W, row0, nrows)
-        return rays_o, rays_d, viewdirs
-    rays_o, rays_d, viewdirs = ops.RayGen.apply(c2w.to(_DEV), H, W, float(focal), row0, nrows)
+    rays_o, rays_d, viewdirs = ops.rays(c2w.to(_DEV), H, W, focal, intr, px, row0, nrows)
     if c2w_staticcam is not None:                                   # rays of the static camera, view directions of c2w (:211-216)
-        rays_o, rays_d, _ = ops.RayGen.apply(c2w_staticcam.to(_DEV), H, W, float(focal), row0, nrows)
+        rays_o, rays_d, _ = ops.rays(c2w_staticcam.to(_DEV), H, W, focal, intr, px, row0, nrows)
     return rays_o, rays_d, viewdirs
 
 
@@ -386,7 +378,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         rays_o, rays_d = rays_o.to(_DEV).reshape(-1, 3).float(), rays_d.to(_DEV).reshape(-1, 3).float()
         viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)             # caller-supplied rays: torch glue
         if c2w_staticcam is not None:
-            rays_o, rays_d, _ = ops.RayGen.apply(c2w_staticcam.to(_DEV), int(H), int(W), float(focal), 0, int(H))
+            rays_o, rays_d, _ = ops.rays(c2w_staticcam.to(_DEV), int(H), int(W), focal)
     if ndc:
         rays_o, rays_d = ops.NdcRays.apply(rays_o, rays_d, H, W, float(focal), 1.)
     all_ret = _render_batch(rays_o, rays_d, viewdirs, near, far, chunk, kwargs, cfg)

@@ -31,7 +31,14 @@ upsampled_cosine_loss, pixel_cosine_loss, upsampled_pixel_cosine_loss; csrc/feat
 tests/test_gpu_masked_loss.py and the loop's shape -- one shape of each has three groups -- without a mask, with a random one and with
 all ones, and of ops.upsampled_cosine_loss_prepared at four shapes.  Only those five functions are called, so the same file runs in an
 earlier commit's tree (copy it there).  --time: then, per op at the loop's shape, the median and min / max of 200 calls' device time
-each way, around the entry-point call (ops.TIMERS) and around the whole eager call ('# time' lines)."""
+each way, around the entry-point call (ops.TIMERS) and around the whole eager call ('# time' lines).
+    python tools/ab_identical.py --rays
+prints, instead, the digests of every output of the nine ray-generation entry points (csrc/rays.hip: the focal, intrinsics and pixel-list
+pairs) and of the six ops.raygen_* functions over them at RAY_GRIDS -- the focal pair at the centred camera, the intrinsics pair at a
+centred and an off-centre one, the list pair on each grid's row-major integer pixels -- and at the sub-pixel lists of
+tests/test_gpu_pixels.py (RAY_LISTS): the forward, and the backward with all three upstream gradients and with each alone, with and
+without the camera's gradient.  The C ABI's buffers, the workspace included, are filled with a fixed pattern before the call and digested
+whole.  Only those names are called, so the same file runs in an earlier commit's tree (copy it there)."""
 import ctypes as C
 import hashlib, os, sys
 import torch
@@ -507,7 +514,68 @@ def run_feature_loss(timed):
             print(f"# time {tag:48s} {key:28s} median {us[len(us) // 2]:8.2f} us  min {us[0]:8.2f}  max {us[-1]:8.2f}", flush=True)
 
 
+# (H, W, focal, row shards): one block, row shards, nine blocks and a one-row shard, more rays than the 1024-block cap holds at once
+RAY_GRIDS = ((6, 8, 7.3, ((0, 6),)), (10, 7, 9.1, ((0, 3), (3, 3), (6, 4), (0, 10))), (33, 65, 58.0, ((11, 1), (0, 33))), (513, 512, 400.0, ((0, 513),)))
+RAY_LISTS = (1, 15, 257, 2305)
+
+
+def run_rays():
+    os.environ.setdefault("NEFES_PARITY_LOG", os.devnull)
+    from oracle import ref_cpu as O
+    from tests import pixels_ref as R
+    from tests.test_gpu_intrinsics import centred, off_centre, upstream
+    from tests.test_gpu_pixels import subpixel_list
+    PAD, FILL = 8, 0.123
+    c2w = O.bench_pose().to(dev)
+    full = lambda *shape: torch.full(shape, FILL, device=dev)
+    names = ("rays_o", "rays_d", "viewdirs")
+
+    def pair(tag, stem, n, head, tail, ops_fwd, ops_bwd, camera):
+        """Forward and every backward of one entry-point pair: through the C ABI on patterned buffers PAD rays (numbers) longer than
+        what the kernels write, the workspace included, and through the ops.raygen_* functions of the same name."""
+        ups_all = [t.to(dev) for t in upstream(n)]
+        o, d, v = full(n + PAD, 3), full(n + PAD, 3), full(n + PAD, 3)
+        L.check(getattr(lib, stem + "_fwd")(*head, P(c2w), *tail, P(o), P(d), P(v), None), tag)
+        out(f"{tag} fwd", rays_o=o, rays_d=d, viewdirs=v)
+        out(f"{tag} fwd ops", **dict(zip(names, ops_fwd())))
+        ws_bytes = getattr(lib, stem + "_bwd_workspace")(n)
+        for present in ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1)):
+            ups = [t if p else None for t, p in zip(ups_all, present)]
+            for want in ((True, False) if camera else (None,)):
+                ws = torch.full((ws_bytes + 64,), 0x5a, dtype=torch.uint8, device=dev)
+                g12, g4 = full(12 + PAD), full(4 + PAD)
+                more = (P(g4) if want else None,) if camera else ()
+                L.check(getattr(lib, stem + "_bwd")(*head, P(c2w), *tail, *(P(t) for t in ups), P(ws), P(g12), *more, None), tag)
+                got = ops_bwd(*ups) if not camera else ops_bwd(*ups, want_intr=want)
+                got = (got, None) if torch.is_tensor(got) else got
+                zero = torch.zeros(0)
+                out(f"{tag} bwd {present} want_intr {want}", g_c2w=g12, g_intr=g4, workspace=ws, ops_g_c2w=got[0],
+                    ops_g_intr=zero if got[1] is None else got[1])
+
+    def list_pair(tag, px, K):
+        n = px.shape[0]
+        pair(tag, "nefes_raygen_px", n, (n, P(px), P(K)), (), lambda: ops.raygen_px_fwd(px, K, c2w),
+             lambda *g, **kw: ops.raygen_px_bwd(px, K, c2w, *g, **kw), True)
+
+    for H, W, f, shards in RAY_GRIDS:
+        Kc, Ko = centred(H, W, f).to(dev), off_centre(H, W, f).to(dev)
+        for row0, nr in shards:
+            tag = f"{H}x{W} rows {row0}+{nr}"
+            pair(f"raygen {tag}", "nefes_raygen", nr * W, (H, W, f), (row0, nr), lambda: ops.raygen_fwd(H, W, f, c2w, row0, nr),
+                 lambda *g: ops.raygen_bwd(H, W, f, c2w, row0, nr, *g), False)
+            for name, K in (("centred", Kc), ("off-centre", Ko)):
+                pair(f"raygen_k {tag} {name}", "nefes_raygen_k", nr * W, (H, W, P(K)), (row0, nr), lambda: ops.raygen_k_fwd(H, W, K, c2w, row0, nr),
+                     lambda *g, **kw: ops.raygen_k_bwd(H, W, K, c2w, row0, nr, *g, **kw), True)
+            list_pair(f"raygen_px {tag} integer list", R.grid_pixels(W, row0, nr).to(dev), Ko)
+    H, W, f = 33, 65, 58.0
+    for n in RAY_LISTS:
+        list_pair(f"raygen_px sub-pixel list n={n}", subpixel_list(n, H, W, seed=n).to(dev), off_centre(H, W, f).to(dev))
+
+
 print("# lib", os.environ.get("NEFES_HIP_LIB") or "shipped", "ABI", L.ABI_VERSION)
+if "--rays" in sys.argv[1:]:
+    run_rays()
+    sys.exit(0)
 if "--feature-loss" in sys.argv[1:]:
     run_feature_loss("--time" in sys.argv[1:])
     sys.exit(0)
