@@ -151,6 +151,22 @@ int nefes_raygen_px_bwd(int n, const float* px, const float* intr, const float* 
  * row: at an integer coordinate the result is the map's value exactly, and nothing outside the map is read for any input.  Forward
  * only (it samples targets). */
 int nefes_sample_px(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream);
+/* Draw such lists on the device: for each of B images, K distinct pixels of the H x W frame, uniform among the valid pixels of a mask,
+ * reproducible, with no host read (csrc/draw.hip).  All pointers dev.  mask: uint8 [B, H, W], pixel i = y*W + x of image b is valid iff
+ * mask == NULL or mask[b*H*W + i] != 0.  state: two 64-bit words {seed, tick}, READ FROM DEVICE MEMORY when the kernels run, like the
+ * camera: epoch = tick / period.  The pixel's sort key is (o0 << 32) | o1 of Philox-4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85) at counter (i, b, epoch & 0xffffffff, epoch >> 32), key (seed & 0xffffffff, seed >> 32).  Image b's
+ * draw is its K valid pixels with the smallest (key, i), written to px[b] (float32 [B, K, 2], rows (x, y) = ((float)(i % W),
+ * (float)(i / W)) as nefes_raygen_px_fwd reads them) in ascending i: a function of (seed, epoch, b, mask[b]) alone, whatever the launch
+ * geometry and the order in which the kernels' integer atomics arrive.  n_valid ([B] int32, may be NULL): the number of valid pixels.
+ * 0 < n_valid[b] < K: the valid pixels in ascending order, repeated cyclically (px[b, j] = valid[j % n_valid]); n_valid[b] == 0: rows of
+ * (0, 0).  advance != 0: tick becomes tick + 1 after every key of the call has been formed from the tick it found (a replayed graph
+ * draws a new batch every `period` replays); 0 leaves the state alone.  NEFES_E_BADARG before any HIP call for B, H, W, K, period <= 0,
+ * K > H*W, H*W > 1 << 24, NULL state / px / workspace.  workspace: >= nefes_draw_pixels_workspace(B, H, W) bytes (keys, bitmap,
+ * histograms, candidate lists; the call zeroes what it counts in); 8-byte aligned. */
+size_t nefes_draw_pixels_workspace(int B, int H, int W);
+int nefes_draw_pixels(int B, int H, int W, const uint8_t* mask, int K, int period, uint64_t* state, int advance, float* px,
+                      int32_t* n_valid, void* workspace, void* stream);
 /* ndc_rays (:27-44) and its backward to (rays_o, rays_d). */
 int nefes_ndc_fwd(int H, int W, float focal, float near, int n, const float* rays_o, const float* rays_d, float* out_o,
                   float* out_d, void* stream);

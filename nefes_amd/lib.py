@@ -100,6 +100,8 @@ SIGNATURES = {
     "nefes_raygen_px_bwd_workspace": (_sz, [_i]),
     "nefes_raygen_px_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_sample_px": (_i, [_i, _i, _i, _p, _i, _p, _p, _p]),
+    "nefes_draw_pixels_workspace": (_sz, [_i, _i, _i]),
+    "nefes_draw_pixels": (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
     "nefes_ndc_fwd": (_i, [_i, _i, _f, _f, _i, _p, _p, _p, _p, _p]),
     "nefes_ndc_bwd": (_i, [_i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_coarse_depths": (_i, [_i, _i, _f, _f, _i, _p, _p, _p, _p]),

@@ -273,6 +273,75 @@ def sample_pixels(map, px, out=None):
     return out
 
 
+def draw_state(seed, device):
+    """The {seed, tick} words of a draw sequence (draw_pixels): the int64 [2] tensor {seed, 0} on `device`.  0 <= seed < 2^63."""
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 63:
+        raise ValueError(f"nefes_amd: draw_state: seed = {seed} must be in [0, 2^63)")
+    return torch.tensor([seed, 0], dtype=torch.int64, device=torch.device(device))
+
+
+def _draw_workspace(state, B, H, W):
+    """draw_pixels' workspace, allocated once per (B, H, W, device) -- and per draw sequence: it is kept ON the state tensor, not in a
+    table of the module, because two sequences may run on two streams at once (refine_concurrently: one refiner, one state each), and
+    a captured graph holds its address for as long as it holds the state's."""
+    cache = getattr(state, "_nefes_draw_workspace", None)
+    if cache is None:
+        cache = state._nefes_draw_workspace = {}
+    key = (int(B), int(H), int(W), str(state.device))
+    ws = cache.get(key)
+    if ws is None:
+        nbytes = int(L.load().nefes_draw_pixels_workspace(B, H, W))
+        if nbytes <= 0:
+            raise ValueError(f"nefes_amd: draw_pixels: B, H, W = {B}, {H}, {W} must be positive with H * W <= 2^24")
+        ws = cache[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=state.device)
+    return ws
+
+
+def draw_pixels(H, W, K, state, B=1, mask=None, period=1, advance=True, out=None, n_valid=None):
+    """K distinct pixels of the H x W frame for each of B images, drawn ON THE DEVICE, uniform among the valid pixels of `mask`:
+    float32 [B, K, 2] rows (x, y), ascending in y*W + x, contiguous -- px[b] is a legal `pixels=` list (render, sample_pixels) without a
+    copy.  Nothing here reads the device, so the call can sit in a captured graph.
+    state: draw_state's int64 [2] {seed, tick}, read by the kernels when they run: the draw is a function of (seed, tick // period, b,
+    mask[b]) alone (include/nefes_hip.h gives the keys; tests/draw_ref.py restates them).  advance: the tick is incremented behind the
+    draw, so the next call -- or the next replay of a graph that holds this one -- draws a new batch every `period` calls.
+    mask: a uint8 or bool [B, H, W] (or [H, W] for B = 1) device tensor, read in place, valid where != 0; None: every pixel.  An image
+    with fewer than K valid pixels gets them all, repeated cyclically; with none, rows of (0, 0): n_valid tells.
+    out: a contiguous float32 [B, K, 2] (or, B = 1, [K, 2]) tensor written in place;  n_valid: an int32 [B] tensor that receives the
+    number of valid pixels per image.  No gradient: pixel indices carry none."""
+    B, H, W, K, period = int(B), int(H), int(W), int(K), int(period)
+    if tuple(state.shape) != (2,):
+        raise RuntimeError(f"nefes_amd: draw_pixels: `state` must be the int64 [2] tensor of draw_state; got {tuple(state.shape)}")
+    dev = state.device
+    if min(B, H, W, K, period) <= 0 or K > H * W or H * W > 1 << 24:
+        raise ValueError(f"nefes_amd: draw_pixels: B, H, W, K, period = {B}, {H}, {W}, {K}, {period} must be positive with K <= H * W "
+                         f"<= 2^24")
+    if mask is not None:
+        if mask.dtype not in (torch.uint8, torch.bool):
+            raise RuntimeError(f"nefes_amd: draw_pixels: `mask` must be uint8 or bool (got {mask.dtype})")
+        if tuple(mask.shape) != (B, H, W) and not (B == 1 and tuple(mask.shape) == (H, W)):
+            raise RuntimeError(f"nefes_amd: draw_pixels: `mask` must be [{B}, {H}, {W}]; got {tuple(mask.shape)}")
+        if mask.device != dev:
+            raise RuntimeError(f"nefes_amd: draw_pixels: `mask` is on {mask.device}, the state on {dev}")
+    if out is None:
+        out = torch.empty(B, K, 2, device=dev)
+        res = out
+    else:
+        if tuple(out.shape) != (B, K, 2) and not (B == 1 and tuple(out.shape) == (K, 2)):
+            raise RuntimeError(f"nefes_amd: draw_pixels: `out` must be [{B}, {K}, 2]; got {tuple(out.shape)}")
+        if out.device != dev:
+            raise RuntimeError(f"nefes_amd: draw_pixels: `out` is on {out.device}, the state on {dev}")
+        res = out.view(B, K, 2) if out.is_contiguous() else out
+    if n_valid is not None and (tuple(n_valid.shape) != (B,) or n_valid.device != dev):
+        raise RuntimeError(f"nefes_amd: draw_pixels: `n_valid` must be int32 [{B}] on {dev}; got {tuple(n_valid.shape)} on {n_valid.device}")
+    ws = _draw_workspace(state, B, H, W)
+    L.check(L.load().nefes_draw_pixels(B, H, W, _chk(mask, "mask", torch.bool if mask is not None and mask.dtype == torch.bool else torch.uint8),
+                                       K, period, _chk(state, "state", torch.int64), int(bool(advance)), _chk(out, "out"),
+                                       _chk(n_valid, "n_valid", torch.int32), _chk(ws, "workspace", torch.int64), _stream()),
+            "nefes_draw_pixels")
+    return res
+
+
 class NdcRays(torch.autograd.Function):
     """ndc_rays (ray_utils.py:27-44)."""
 

@@ -145,7 +145,13 @@ class PoseRefiner:
     features sampled at the same pixels; no colour transform and no FusionNet (the reference's non-fusion branch,
     DFM_pose_refine.py:330-333, with img_in=False).  `refine(..., pixels=)` takes the [K, 2] points (x, y) of the rendered (h, w) frame
     (None: K distinct integer pixels drawn with a generator seeded by `seed=`, among the mask's valid ones on a masked refiner);
-    `set_pixels` moves them in place, and a captured iteration follows."""
+    `set_pixels` moves them in place, and a captured iteration follows.
+
+    `redraw=R` (with sparse=K) draws a fresh batch every R iterations, as iNeRF-style optimisers do: the iteration begins with
+    ops.draw_pixels -- K distinct pixels, uniform among the mask's valid ones, drawn on the device from the persistent words
+    `draw_state` = {seed, tick} -- and a re-sample of the target there, both inside the captured graph: no host read per image or per
+    iteration.  Every image starts from {seed=, 0}: its batches depend on (seed, mask) alone.  Such a refiner takes no `pixels=` and no
+    `set_pixels`.  None (default): the fixed list described above."""
 
     FUSED_UPSAMPLED_LOSS = True      # False: bicubic up-sampling and cosine loss as separate kernels (the tests compare the two)
     # The loop's target is fixed for all iterations of an image: its share of the up-sampled loss (Uy^T target Ux, |target|^2) is
@@ -164,11 +170,17 @@ class PoseRefiner:
     def __init__(self, render_kwargs, args, hwf, near, far, tinyscale=4, lr_r=0.01, lr_t=0.1, lietorch=False,
                  upsample=False, per_pixel=False, world_setup=None, graph=True, device="cuda", adam_capturable=None,
                  fused_glue=True, images=1, pose_model=None, svd_reg=False, learning_rate=1e-5, bn_running_stats=True,
-                 intrinsics=None, learn_focal=False, lr_f=1e-3, masked=False, sparse=None, seed=0):
+                 intrinsics=None, learn_focal=False, lr_f=1e-3, masked=False, sparse=None, seed=0, redraw=None):
         self.kw, self.args = dict(render_kwargs), args
         self.sparse = None if sparse is None else int(sparse)
         if self.sparse is not None:
             _refuse_sparse(self.sparse, pose_model, images, upsample, fused_glue, lietorch)
+        self.redraw = None if redraw is None else int(redraw)
+        if self.redraw is not None:
+            if self.sparse is None:
+                raise ValueError(f"nefes_amd: PoseRefiner(redraw={redraw}) redraws the pixels of a sparse refiner: it needs sparse=K")
+            if self.redraw < 1:
+                raise ValueError(f"nefes_amd: PoseRefiner(redraw={redraw}): the number of iterations per draw must be at least 1")
         # False: FusionNet's train-mode BatchNorm leaves its running statistics and batch counter alone in this refiner's iterations
         # (nothing in the loop reads them; the reference never puts the net in eval mode).  REQUIRED for refiners that share a
         # FusionNet and run at the same time (refine_concurrently): the update is a read-modify-write of the shared module's buffers.
@@ -254,6 +266,14 @@ class PoseRefiner:
             self.mask = torch.ones(1, K, dtype=torch.uint8, device=self.dev) if self.masked else None
             self._frame, self._frame_mask = None, None
             self._draw = torch.Generator().manual_seed(int(seed))
+            if self.redraw is not None:
+                # redraw=R: the iteration itself begins with ops.draw_pixels into self.pixels (a new batch every R iterations, from the
+                # persistent {seed, tick} words self.draw_state, which _reset rewrites per image) and a re-sample of the target there.
+                # The draw reads the image's mask from ONE persistent uint8 frame, all ones until a mask is given; a drawn pixel is
+                # valid by construction, so self.mask [1, K] stays all ones.
+                self.draw_state = ops.draw_state(int(seed), self.dev)
+                self._state0 = self.draw_state.clone()     # (what _reset copies over draw_state: a device-to-device write)
+                self._mask_u8 = torch.ones(1, self.h, self.w, dtype=torch.uint8, device=self.dev) if self.masked else None
         self._affine = None            # static [1,12] buffer with the image's colour transform when the exposure network is frozen
         self.graph, self.apr_graph = None, None
 
@@ -472,7 +492,17 @@ class PoseRefiner:
             self.loss.copy_(per_image)
         return self.loss
 
+    def _redraw(self):
+        """redraw=R: a new batch of pixels into self.pixels -- every R calls, the tick in self.draw_state is advanced by the draw itself
+        -- and the image's target sampled there: two launch sequences with no host read, captured with the iteration behind them."""
+        with torch.no_grad():
+            ops.draw_pixels(self.h, self.w, self.sparse, self.draw_state, mask=self._mask_u8, period=self.redraw, advance=True,
+                            out=self.pixels)
+            ops.sample_pixels(self._frame, self.pixels, out=self.target)
+
     def _iteration(self):
+        if self.redraw is not None:
+            self._redraw()
         self.loss_and_grad()
         self.opt.step()
 
@@ -519,14 +549,42 @@ class PoseRefiner:
         if frame.numel() != self.C * h * w:
             raise ValueError(f"nefes_amd: a sparse refiner samples its target from the rendered frame's features [{self.C}, {h}, {w}]; got "
                              f"{tuple(feature_target.shape)}")
+        if self.redraw is not None:
+            return self._set_redrawn_frame(frame.reshape(self.C, h, w), self._frame_mask_of(mask), pixels)
         self._frame, self._frame_mask = frame.reshape(self.C, h, w).contiguous(), self._frame_mask_of(mask)
         self.set_pixels(self._draw_pixels(self._frame_mask) if pixels is None else pixels)
+
+    def _set_redrawn_frame(self, frame, frame_mask, pixels):
+        """redraw=R: the image's state IN PLACE, where the captured draw and re-sample read it: the feature frame, the mask as the uint8
+        frame the draw selects from (all ones without one), and {seed, 0} in self.draw_state -- which also undoes the ticks that the
+        warm-up iterations of a first capture consumed: an image's batches depend on (seed, mask) and not on what the refiner did
+        before.  With a mask, one host read per image, outside the loop: fewer than K valid pixels are refused as _draw_pixels does."""
+        if pixels is not None:
+            raise ValueError("nefes_amd: pixels= on a PoseRefiner(redraw=R): it draws its pixels itself, every R iterations; build it "
+                             "without redraw= to refine at a given list")
+        if frame_mask is not None:
+            valid = int(frame_mask.sum())
+            if valid < self.sparse:
+                raise ValueError(f"nefes_amd: {self.sparse} distinct pixels asked for, the frame {(self.h, self.w)} has {valid} valid ones")
+        with torch.no_grad():
+            if self._frame is None:
+                self._frame = torch.empty(self.C, self.h, self.w, device=self.dev)
+            self._frame.copy_(frame)
+            self._frame_mask = frame_mask
+            if self.masked:
+                if frame_mask is None:
+                    self._mask_u8.fill_(1)
+                else:
+                    self._mask_u8.copy_(frame_mask.reshape(self._mask_u8.shape))
+            self.draw_state.copy_(self._state0)
 
     def set_pixels(self, px):
         """sparse: new pixels [K, 2] (ops.as_pixels) into self.pixels IN PLACE, and the image's target -- and mask, nearest -- re-sampled
         there in place: a captured iteration reads all three from memory and follows without a re-capture."""
         if self.sparse is None:
             raise RuntimeError("nefes_amd: set_pixels needs a PoseRefiner(sparse=K)")
+        if self.redraw is not None:
+            raise ValueError("nefes_amd: set_pixels on a PoseRefiner(redraw=R): it draws its pixels itself, every R iterations")
         if self._frame is None:
             raise RuntimeError("nefes_amd: set_pixels re-samples the image's target: give the refiner an image first (refine)")
         px = ops.as_pixels(px, self.dev)
@@ -656,6 +714,11 @@ class PoseRefiner:
         """The job tuple of an image: with a fourth element, its mask, on a masked refiner (None: all valid); on a sparse refiner a
         fourth and a fifth, mask and pixels (None: drawn)."""
         if self.sparse is not None:
+            if self.redraw is not None:                    # (nothing is drawn here: the iteration draws)
+                if pixels is not None:
+                    raise ValueError("nefes_amd: pixels= on a PoseRefiner(redraw=R): it draws its pixels itself, every R iterations; "
+                                     "build it without redraw= to refine at a given list")
+                return job + (None if mask is None else torch.as_tensor(mask), None)
             # (drawn HERE, once per image: _run writes the image's state twice around a first capture)
             px = self._draw_pixels(self._frame_mask_of(mask)) if pixels is None else pixels
             return job + (None if mask is None else torch.as_tensor(mask), ops.as_pixels(px, self.dev))

@@ -8,6 +8,11 @@ translation, 4.75 degrees, directions drawn from seed 0).  Per run 50 captured i
 the host clock around the 8 x 50 iterations, ending in a device synchronise, after one untimed image (capture, plans, allocator).
 `--repeats` runs per configuration, every run printed: their spread is the run-to-run spread on this box.
 
+Where the tree has PoseRefiner(sparse=K, redraw=R) the sparse loops also run with a new device-side draw every R iterations
+(`--redraw`, K below the whole frame), every loop's per-image set-up (the job and the state, host clock ending in a synchronise) is timed
+with and without a 75 % mask, and `--draw` times ops.draw_pixels alone by device events (`--draw-calls` calls after a warm-up) at
+`DRAW_SHAPES`, next to the time the bytes it cannot avoid -- the mask and the list -- would take at `--hbm-tbs` TB/s.
+
 `--root DIR` times another checkout of this project (e.g. the parent commit) with this same script; a tree without PoseRefiner(sparse=)
 runs the dense loop only.  Prints one JSON line per configuration."""
 import argparse
@@ -24,6 +29,11 @@ ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspat
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--pixels", type=int, nargs="*", default=[256, 1024, 4800])
+ap.add_argument("--redraw", type=int, nargs="*", default=[1, 5])
+ap.add_argument("--setups", type=int, default=40, help="per-image set-ups timed per configuration")
+ap.add_argument("--draw", action="store_true", help="time ops.draw_pixels alone as well")
+ap.add_argument("--draw-calls", type=int, default=200)
+ap.add_argument("--hbm-tbs", type=float, default=6.29, help="HBM rate the bound is stated at (a measured float4 copy on MI355X)")
 ap.add_argument("--tag", default="this")
 a = ap.parse_args()
 ROOT = os.path.abspath(a.root)
@@ -79,8 +89,25 @@ def perturbed(n, dt, deg, seed=0):
 starts = perturbed(8, float(g["init_err"][0][0]), float(g["init_err"][0][1]))
 
 
-def measure(name, make, target, extra):
-    """`a.repeats` runs of 8 starts x a.iters iterations on one refiner: ms per iteration of each run, pose errors of the last."""
+mask75 = (torch.rand(h, w, generator=torch.Generator().manual_seed(0)) < 0.75).to(torch.uint8)
+
+
+def setup_us(r, target, mask):
+    """Median microseconds of one image's set-up on refiner r -- the job (a sparse refiner without redraw= draws its pixels here, on the
+    host) and the state written in place -- host clock, ending in a device synchronise."""
+    m, more, us = r._mode(), ({} if mask is None else {"mask": mask}), []
+    for k in range(a.setups + 3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m.set_state(*m.on_device(r._job(starts[k % len(starts)], target, hist, **more)))
+        torch.cuda.synchronize()
+        us.append((time.perf_counter() - t0) * 1e6)
+    return round(statistics.median(us[3:]), 1)
+
+
+def measure(name, make, target, extra, masked_setup=True):
+    """`a.repeats` runs of 8 starts x a.iters iterations on one refiner: ms per iteration of each run, pose errors of the last; then the
+    per-image set-up alone, without a mask and (a refiner built with masked=True) with a 75 % one."""
     r = make()
     r.refine(starts[0], target, hist, a.iters)                               # capture, plans, allocator: not timed
     ms, errs = [], []
@@ -91,6 +118,9 @@ def measure(name, make, target, extra):
         torch.cuda.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3 / (len(starts) * a.iters))
         errs = [bench._pose_error(true.numpy(), p[:3, :4].cpu().numpy()) for p in poses]
+    if a.setups > 0:
+        extra = dict(extra, setup_us=setup_us(r, target, None),
+                     setup_us_masked=setup_us(make(masked=True), target, mask75) if masked_setup else None)
     rec = dict(tag=a.tag, loop=name, iters=a.iters, starts=len(starts), ms_per_iteration=[round(v, 4) for v in ms],
                median_ms=round(statistics.median(ms), 4), spread_ms=round(max(ms) - min(ms), 4),
                start_error=[round(float(v), 4) for v in g["init_err"][0]],
@@ -99,19 +129,48 @@ def measure(name, make, target, extra):
     print(json.dumps(rec), flush=True)
 
 
-dense = lambda: PoseRefiner(kw, args, (H, W, focal), float(g["near"]), float(g["far"]), **common)
-probe = dense()
+base = lambda **more: PoseRefiner(kw, args, (H, W, focal), float(g["near"]), float(g["far"]), **common, **more)
+probe = base()
 probe._reset(true.to(dev), torch.zeros(C, h, w, device=dev), hist)
-measure("dense 60x80", dense, probe.features()[0], dict(rays=h * w))
+measure("dense 60x80", base, probe.features()[0], dict(rays=h * w))
 del probe
 
-if "sparse" in inspect.signature(PoseRefiner.__init__).parameters:
+params = inspect.signature(PoseRefiner.__init__).parameters
+if "sparse" in params:
     n = h * w
     grid = torch.stack([torch.arange(n) % w, torch.arange(n) // w], -1).float().to(dev)
-    probe = PoseRefiner(kw, args, (H, W, focal), float(g["near"]), float(g["far"]), sparse=n, **common)
+    probe = base(sparse=n)
     probe._reset(true.to(dev), torch.zeros(C, h, w, device=dev), hist, None, grid)
     frame = probe.features().reshape(C, h, w)                                # the field's feat_map at the true pose, as a frame
     del probe
     for K in a.pixels:
-        measure(f"sparse K={K}", lambda: PoseRefiner(kw, args, (H, W, focal), float(g["near"]), float(g["far"]), sparse=K, seed=0, **common),
-                frame, dict(rays=K))
+        measure(f"sparse K={K}", lambda **more: base(sparse=K, seed=0, **more), frame, dict(rays=K),
+                masked_setup=K <= int(mask75.sum()))                             # (more pixels than the mask has valid ones: refused)
+        for every in (a.redraw if "redraw" in params and K < n else []):
+            measure(f"sparse K={K} redraw={every}", lambda **more: base(sparse=K, seed=0, redraw=every, **more), frame,
+                    dict(rays=K, redraw=every))
+
+# ---- the draw alone: device events around a.draw_calls calls, after a warm-up ---------------------------------------------------
+DRAW_SHAPES = ((1, 60, 80, 256), (1, 240, 427, 1024), (1, 480, 854, 4096), (8, 120, 213, 1536))
+if a.draw:
+    from nefes_amd import ops
+    for B, dh, dw, K in DRAW_SHAPES:
+        for masked in (False, True):
+            m = (torch.rand(B, dh, dw, generator=torch.Generator().manual_seed(1)) < 0.75).to(torch.uint8).to(dev) if masked else None
+            state, out = ops.draw_state(0, dev), torch.empty(B, K, 2, device=dev)
+            call = lambda: ops.draw_pixels(dh, dw, K, state, B=B, mask=m, out=out)
+            for _ in range(20):
+                call()
+            us = []
+            for _ in range(3):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                for _ in range(a.draw_calls):
+                    call()
+                t1.record()
+                torch.cuda.synchronize()
+                us.append(round(t0.elapsed_time(t1) * 1e3 / a.draw_calls, 2))
+            nbytes = (B * dh * dw if masked else 0) + B * K * 8              # the mask read once, the list written once
+            print(json.dumps(dict(tag=a.tag, draw=[B, dh, dw, K], masked=masked, calls=a.draw_calls, us_per_call=us,
+                                  mask_and_list_bytes=nbytes, us_of_those_bytes_at_hbm_rate=round(nbytes / (a.hbm_tbs * 1e12) * 1e6, 4),
+                                  hbm_tbs=a.hbm_tbs)), flush=True)
