@@ -263,15 +263,17 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
 #pragma unroll
             for (int e = 0; e < 8 * KR16; ++e) dr[e] = 0.f;
         }
-        // head activation derivatives from the outputs: sigmoid' = y(1-y), softplus' = 1 - exp(-y)
+        // head activation derivatives from the outputs: sigmoid' = y(1-y), softplus' = 1 - exp(-y) = -expm1(-y).  expm1f, not 1 - expf:
+        // a saturated softplus (y = e^x below 1e-7) keeps its derivative's relative accuracy, which the per-sample comparison with
+        // float64 (tests/test_gpu_field_samples.py, one upstream channel at a time) holds it to.
         float dth[3];
         if (h == 0) {   // rows 0 (rgb_t0), 2 (rgb_t2), 4 (beta)
             dth[0] = g_th[0] * (y_th[0] * (1.f - y_th[0]));
             dth[1] = g_th[1] * (y_th[1] * (1.f - y_th[1]));
-            dth[2] = g_th[2] * (1.f - expf(-y_th[2]));
+            dth[2] = g_th[2] * (-expm1f(-y_th[2]));
         } else {        // rows 1 (rgb_t1), 3 (sigma_t), pad
             dth[0] = g_th[0] * (y_th[0] * (1.f - y_th[0]));
-            dth[1] = g_th[1] * (1.f - expf(-y_th[1]));
+            dth[1] = g_th[1] * (-expm1f(-y_th[1]));
             dth[2] = 0.f;
         }
         // values needed only at the end of the tile wait in LDS, not in registers
@@ -280,7 +282,7 @@ __global__ __launch_bounds__(256, NEFES_H3B_WG_PER_CU(W)) void field_bwd_h3_kern
             STASH(c) = a.pts ? in_o[c] : add_rn(in_o[c], mul_rn(in_d[c], in_z));
             STASH(3 + c) = v[c];
         }
-        const float d_sigma = h == 0 ? g_sg * (1.f - expf(-y_sg)) : 0.f;
+        const float d_sigma = h == 0 ? g_sg * (-expm1f(-y_sg)) : 0.f;
         STASH(6) = d_sigma;
         if constexpr (TRAIN) {
             // The head blocks of the gradient buffer -- d raw for the rgb+feature channels, the sigma and transient-head

@@ -244,10 +244,14 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
                 const char* bp8 = bias_half + 7 * W * 4;                                  // the tiles are layer 8's, without its bias
                 nbias = ReluBiasSplitH<false, NTW, WT>::prime(bp8);
                 mma_run_h3<1, W / 16, 0, true>(ring, ring_lane, ReluBiasSplitH<false, NTW, WT>{X, bits, pow2i(tau_x - es_x), mdummy, bp8, pow2i(es_x), nbias},
-                                               bias_at(B_SIG, es), sg);
+                                               ZeroInit{}, sg);
             } else
             mma_run_h3<1, W / 16, 0, true>(ring, ring_lane, ReluSplitH<false, NTW, WT>{X, bits, pow2i(tau_x - es_x), mdummy},
-                                           bias_at(B_SIG, es), sg);
+                                           ZeroInit{}, sg);
+            // The head's bias joins BEHIND the run, with one rounding: as the accumulators' start value it made every chained MFMA
+            // round a sum of the bias's size, and a product that is small beside its bias (static_sigma x 40; dir_encoding with small
+            // weights, below) came out 4 - 19 x further from float64 than plain fp32 (tests/test_gpu_field_samples.py).
+            sg[0] += bias_at(B_SIG, es)(0);
             float* col = raw_col();
             if (col && h == 0) {
                 const int ch = (MODE == NEFES_FIELD_SIGMA) ? 0 : 3 + a.C;
@@ -355,6 +359,14 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
                 __device__ __forceinline__ f32x16 operator()(int t) const { return t < NTH ? a(t) : b(t - NTH); }
             };
             int es_dt;
+            auto add_stack_bias = [&](f32x16 (&acc)[NDT], int es) {
+                const Bias2 b{bias_at(B_DIR, es), bias_at(B_T0, es)};
+                // every tile of the stack is read here with the vector ALU: the wide run's own end statement ties its two youngest
+                // tiles only (the older ones' readers used to sit in the next run), so all of them are tied to the wait states here
+                mfma_results_fence_tiles<12, NDT, 0>(acc);
+#pragma unroll
+                for (int t = 0; t < NDT; ++t) acc[t] += b(t);      // (STATIC: NDT = NTH, the dir tiles alone)
+            };
             if constexpr (FOLD) {
                 sigma_head(B, es_b, tau_of(M, wexp(NEFES_H3F_SIG)));                   // static_sigma on relu(h8), as behind the unfolded layer 8
                 // the stacked head on relu(h8): M bounds h8, the head's first W columns are the packer's W_head[:, :W] W_final
@@ -370,12 +382,13 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
                     const char* bp8 = bias_half + 7 * W * 4;                            // layer 8's tiles come without its bias
                     nbias = ReluBiasSplitH<CAP, NTW, WT>::prime(bp8);
                     const ReluBiasSplitH<CAP, NTW, WT> src8{B, bits, pow2i(tau - es_b), mx, bp8, pow2i(es_b), nbias};
-                    mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, src8, Bias2{bias_at(B_DIR, es_dt), bias_at(B_T0, es_dt)}, dt);
+                    mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, src8, ZeroInit{}, dt);
                 } else {
                     const ReluSplitH<CAP, NTW, WT> src8{B, bits, pow2i(tau - es_b), mx};
-                    mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, src8, Bias2{bias_at(B_DIR, es_dt), bias_at(B_T0, es_dt)}, dt);
+                    mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, src8, ZeroInit{}, dt);
                 }
                 mma_run_h3<NDT, 2, 0, false>(ring, ring_lane, ArraySplitH<16>{Dv, pow2i(tau)}, ZeroInit{}, dt);
+                add_stack_bias(dt, es_dt);                                            // (the biases behind both runs: sigma_head's note)
                 M = rbh_ * (pair_max(mx) * pow2i(-es_b)) + rbd_ * mD + bm_;
                 put_masks(bits, WT);                                                  // mask of layer 8
             } else {
@@ -388,14 +401,15 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
                     const char* bpf = bias_half + B_FINAL * 4;                          // xyz_encoding_final's tiles come without its bias
                     nbias = ReluBiasSplitH<false, 1, 1>::prime(bpf);
                     const IdentBiasSplitH<NTW> srcf{A, pow2i(tau - es_a), mx, bpf, pow2i(es_a), nbias};
-                    if constexpr (FULL) mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, srcf, Bias2{bias_at(B_DIR, es_dt), bias_at(B_T0, es_dt)}, dt);
-                    else mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, srcf, bias_at(B_DIR, es_dt), dt);
+                    if constexpr (FULL) mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, srcf, ZeroInit{}, dt);
+                    else mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, srcf, ZeroInit{}, dt);
                 } else if constexpr (FULL)
                     mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, IdentSplitH<NTW, 0>{A, pow2i(tau - es_a), mx},
-                                                     Bias2{bias_at(B_DIR, es_dt), bias_at(B_T0, es_dt)}, dt);
+                                                     ZeroInit{}, dt);
                 else
-                    mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, IdentSplitH<NTW, 0>{A, pow2i(tau - es_a), mx}, bias_at(B_DIR, es_dt), dt);
+                    mma_run_h3<NDT, W / 16, 0, true>(ring, ring_lane, IdentSplitH<NTW, 0>{A, pow2i(tau - es_a), mx}, ZeroInit{}, dt);
                 mma_run_h3<NDT, 2, 0, false>(ring, ring_lane, ArraySplitH<16>{Dv, pow2i(tau)}, ZeroInit{}, dt);
+                add_stack_bias(dt, es_dt);                                            // (the biases behind both runs: sigma_head's note)
                 M = rowb(NEFES_H3F_DT_H) * (pair_max(mx) * pow2i(-es_a)) + rowb(NEFES_H3F_DT_D) * mD
                     + (FULL ? fmaxf(bmax(NEFES_H3BB_DIR), bmax(NEFES_H3BB_T0)) : bmax(NEFES_H3BB_DIR));   // both halves of the stacked output
                 if constexpr (TRAIN) {
@@ -425,7 +439,7 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
                 const int ew = wexp(NEFES_H3F_RGB), tau = tau_of(M, ew), es = tau + ew;
                 float mdummy = 0.f;
                 mma_run_h3<NTR, W / 32, 0, true>(ring, ring_lane, ReluSplitH<true, NDT, WH>{dt, bits2, pow2i(tau - es_dt), mdummy},
-                                                 bias_at(B_RGB, es), ar);
+                                                 ZeroInit{}, ar);
                 put_masks(bits2, WH);                                 // dir_encoding
                 float* col = raw_col();
                 if (col) {
@@ -437,17 +451,20 @@ __global__ __launch_bounds__(256, W == 128 ? 2 : 1) void field_fwd_h3_kernel(Fie
                     int S_t = a.S, c3 = FH ? 3 : 3 + a.C;         // opaque per tile: the 16 NTR row offsets cu * S and the channel tests
                     asm volatile("" : "+s"(S_t), "+s"(c3));      // are recomputed by the scalar ALU here instead of being hoisted out
                     const int full = c3 >> 5;                     // of the tile loop into (spilled) registers
+                    const BiasInitScaled brgb = bias_at(B_RGB, es);     // the bias joins behind the run, tile by tile (sigma_head's note)
 #pragma unroll
                     for (int t = 0; t < NTR; ++t) {
                         if (t < full) {
+                            const f32x16 bt = brgb(t);
 #pragma unroll
                             for (int r = 0; r < 16; ++r)
-                                __builtin_nontemporal_store(ar[t][r] * inv, &ph[(size_t)(32 * t + nefes_rho(0, r)) * S_t]);
+                                __builtin_nontemporal_store((ar[t][r] + bt[r]) * inv, &ph[(size_t)(32 * t + nefes_rho(0, r)) * S_t]);
                         } else if (32 * t < c3) {
+                            const f32x16 bt = brgb(t);
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
                                 const int cu = 32 * t + nefes_rho(0, r);
-                                if (cu + 4 * h < c3) __builtin_nontemporal_store(ar[t][r] * inv, &ph[(size_t)cu * S_t]);
+                                if (cu + 4 * h < c3) __builtin_nontemporal_store((ar[t][r] + bt[r]) * inv, &ph[(size_t)cu * S_t]);
                             }
                         }
                     }
