@@ -151,6 +151,11 @@ int nefes_raygen_px_bwd(int n, const float* px, const float* intr, const float* 
  * row: at an integer coordinate the result is the map's value exactly, and nothing outside the map is read for any input.  Forward
  * only (it samples targets). */
 int nefes_sample_px(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream);
+/* Nearest-tap sample of the same map at the same kind of list (one kernel body with nefes_sample_px): out[c, i] is the map's value at
+ * column clamp(floor(x + 0.5), 0, W-1), row clamp(floor(y + 0.5), 0, H-1) -- the sum formed in double, so exact for every float32
+ * coordinate; a NaN coordinate reads column / row 0.  For maps that must not be blended: a depth frame with holes in it, a depth
+ * edge.  At integer coordinates it equals nefes_sample_px bit for bit. */
+int nefes_sample_px_nearest(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream);
 /* Draw such lists on the device: for each of B images, K distinct pixels of the H x W frame, uniform among the valid pixels of a mask,
  * reproducible, with no host read (csrc/draw.hip).  All pointers dev.  mask: uint8 [B, H, W], pixel i = y*W + x of image b is valid iff
  * mask == NULL or mask[b*H*W + i] != 0.  state: two 64-bit words {seed, tick}, READ FROM DEVICE MEMORY when the kernels run, like the
@@ -647,6 +652,26 @@ int nefes_uppixcos_loss_masked_bwd(int G, int C, int h, int w, int OH, int OW, i
                                    const uint8_t* mask, const double* scratch, const float* g_loss, const int* tx_first,
                                    const int* tx_count, const float* tx_wt, const int* ty_first, const int* ty_count, const float* ty_wt,
                                    int T, float* tmp, float* g_x, void* stream);
+/* A robust loss between NORMALISED rendered depth and a measured depth map (csrc/depth_loss.hip; an RGB-D query's geometric term).
+ * disp dev [G,P]: the compositor's disparity, 1 / max(1e-10, depth / sum of the weights the variant normalises by), so 1 / disp is
+ * the normalised depth in every variant; target dev [G,P] float32 in the scene's units; mask dev uint8 [G,P] or NULL.  A pixel is
+ * VALID iff target is finite and > 0 (sensor holes: 0, Inf, NaN), disp is finite and > 0 (a ray without density has disp = NaN) and
+ * its mask byte, if there is a mask, is != 0.  A select, as in the masked feature losses: an invalid pixel's values enter no
+ * arithmetic and its gradient is exactly 0.
+ *     e = 1 / disp - target;   rho(e) = e^2 / (2 delta) if |e| <= delta, else |e| - delta / 2     (torch SmoothL1Loss(beta = delta))
+ *     L_g = mean of rho over the group's valid pixels (0, with a zero gradient, when it has none);   value = weight * sum_g L_g.
+ * Per-pixel arithmetic in double from the float32 inputs (reciprocal and branch test included), sums in double in a fixed order, no
+ * atomics; every output is rounded to float32 once.  accumulate != 0: loss[0] becomes loss[0] (as found, widened to double) + value,
+ * rounded once -- a total lands in the caller's buffer without an add of its own.  scratch: dev doubles,
+ * nefes_depth_loss_scratch_doubles(G) = 2 G of them, kept for the backward: L_g [G] (weight not applied), then the valid counts [G].
+ * backward: g_disp [G,P] = g_loss[0] * weight * rho'(e) / n_g * (-1 / disp^2), g_loss a device scalar.
+ * NEFES_E_BADARG before any HIP call: G <= 0 or > 65535, P <= 0, a NULL pointer (mask excepted), delta <= 0 or not finite, weight not
+ * finite; NEFES_E_UNSUPPORTED where the backward's grid (one thread per pixel, 256 per block) would pass 2^31 - 1 blocks. */
+size_t nefes_depth_loss_scratch_doubles(int G);
+int nefes_depth_loss_fwd(int G, int64_t P, const float* disp, const float* target, const uint8_t* mask, double delta, double weight,
+                         int accumulate, double* scratch, float* loss, void* stream);
+int nefes_depth_loss_bwd(int G, int64_t P, const float* disp, const float* target, const uint8_t* mask, double delta, double weight,
+                         const double* scratch, const float* g_loss, float* g_disp, void* stream);
 /* The same loss for a FIXED target (the refinement loop holds the query image's features for all opt_iter iterations of an image:
  * DFM_APR_refine.py:100-131), through the Gram matrices of the up-sampling.  Per channel up = Uy X Ux^T, so
  *     <up, target> = <X, Tt>, Tt = Uy^T target Ux;   |up|^2 = <X, Gy X Gx>, Gy = Uy^T Uy, Gx = Ux^T Ux;   |target|^2 a constant,

@@ -238,12 +238,22 @@ extern "C" int nefes_raygen_px_bwd(int n, const float* px, const float* intr, co
 // into cell and fraction; the second tap's index is clamped to the last column / row, so x = W-1 reads nothing past the row.  Each
 // interpolation is a + f (b - a): at an integer coordinate f = 0 and the value is the map's own, exactly.  A NaN coordinate clamps
 // to 0 (fmaxf returns the other operand): no index leaves the map for any input.
+// NEAREST (nefes_sample_px_nearest): the one tap at column clamp(floor(x + 0.5), 0, W-1), row clamp(floor(y + 0.5), 0, H-1) instead -- the
+// sum in double, exact for every float32 coordinate; NaN clamps to 0 as above.  For maps that must not be blended (a depth frame with
+// holes); at an integer coordinate both instances return the map's own value.
+template <bool NEAREST>
 __global__ __launch_bounds__(256) void sample_px_kernel(int C, int H, int W, const float* __restrict__ map, int n,
                                                         const float* __restrict__ px, float* out) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (size_t)C * n) return;
     const int i = (int)(t % n);
     const size_t c = t / n;
+    if (NEAREST) {
+        const int xn = (int)fmin(fmax(floor((double)px[(size_t)i * 2] + 0.5), 0.0), (double)(W - 1));
+        const int yn = (int)fmin(fmax(floor((double)px[(size_t)i * 2 + 1] + 0.5), 0.0), (double)(H - 1));
+        out[t] = map[c * (size_t)H * W + (size_t)yn * W + xn];
+        return;
+    }
     const float x = fminf(fmaxf(px[(size_t)i * 2], 0.f), (float)(W - 1));
     const float y = fminf(fmaxf(px[(size_t)i * 2 + 1], 0.f), (float)(H - 1));
     const int x0 = (int)x, y0 = (int)y;                      // x, y >= 0: truncation is the floor
@@ -255,12 +265,19 @@ __global__ __launch_bounds__(256) void sample_px_kernel(int C, int H, int W, con
     const float bot = __fadd_rn(m10, __fmul_rn(fx, __fsub_rn(m11, m10)));
     out[t] = __fadd_rn(top, __fmul_rn(fy, __fsub_rn(bot, top)));
 }
-extern "C" int nefes_sample_px(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream) {
+template <bool NEAREST>
+static int sample_px_launch(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream) {
     if (!map || !px || !out || C <= 0 || H <= 0 || W <= 0 || n <= 0) return NEFES_E_BADARG;
     const size_t total = (size_t)C * n;
-    hipLaunchKernelGGL(sample_px_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, C, H, W, map, n, px,
-                       out);
+    hipLaunchKernelGGL(sample_px_kernel<NEAREST>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, C, H, W, map, n,
+                       px, out);
     return (int)hipGetLastError();
+}
+extern "C" int nefes_sample_px(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream) {
+    return sample_px_launch<false>(C, H, W, map, n, px, out, stream);
+}
+extern "C" int nefes_sample_px_nearest(int C, int H, int W, const float* map, int n, const float* px, float* out, void* stream) {
+    return sample_px_launch<true>(C, H, W, map, n, px, out, stream);
 }
 
 // ---- ndc_rays (ray_utils.py:27-44) ------------------------------------------------------------

@@ -65,7 +65,8 @@ def replicate_pose(c2w: torch.Tensor, group=None) -> torch.Tensor:
 def render_sharded(render_fn, H, W, focal, c2w, rank=None, world=None, group=None, intrinsics=None, **kw):
     """render() restricted to this rank's rows, with the pose-gradient all-reduce attached.  `intrinsics` (render()'s keyword: the
     camera (fx, fy, cx, cy), read from device memory by the ray kernels) is passed through; a tensor that requires a gradient is wrapped
-    in the same all-reduce, so every rank ends up with the full d loss / d K."""
+    in the same all-reduce, so every rank ends up with the full d loss / d K.  Every other keyword of render() goes through as it is
+    (`depth_map=True`: a rank without rows returns an empty extras["depth_map"] too)."""
     if rank is None:
         rank = dist.get_rank(group) if dist.is_initialized() else 0
     if world is None:
@@ -83,7 +84,10 @@ def render_sharded(render_fn, H, W, focal, c2w, rank=None, world=None, group=Non
         if torch.is_tensor(intrinsics) and intrinsics.requires_grad:
             z = z + (intrinsics.sum() * 0.).reshape(1, 1)
         C = getattr(kw.get("network_fn", None), "W_features", 0)
-        return [z.expand(0, 3), z.expand(0, 1)[:, 0], z.expand(0, 1)[:, 0], {"feat_map": z.expand(0, C)}]
+        extras = {"feat_map": z.expand(0, C)}
+        if kw.get("depth_map", False):                               # (render()'s keyword: the key is there only when asked for)
+            extras["depth_map"] = z.expand(0, 1)[:, 0]
+        return [z.expand(0, 3), z.expand(0, 1)[:, 0], z.expand(0, 1)[:, 0], extras]
     return render_fn(H, W, focal, c2w=pose, row_range=(row0, nrows), **kw)
 
 

@@ -100,6 +100,7 @@ SIGNATURES = {
     "nefes_raygen_px_bwd_workspace": (_sz, [_i]),
     "nefes_raygen_px_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "nefes_sample_px": (_i, [_i, _i, _i, _p, _i, _p, _p, _p]),
+    "nefes_sample_px_nearest": (_i, [_i, _i, _i, _p, _i, _p, _p, _p]),
     "nefes_draw_pixels_workspace": (_sz, [_i, _i, _i]),
     "nefes_draw_pixels": (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
     "nefes_ndc_fwd": (_i, [_i, _i, _f, _f, _i, _p, _p, _p, _p, _p]),
@@ -193,6 +194,9 @@ SIGNATURES = {
     "nefes_uppixcos_masked_scratch_doubles": (_sz, [_i, _i, _i, _i]),
     "nefes_uppixcos_loss_masked_fwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "nefes_uppixcos_loss_masked_bwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "nefes_depth_loss_scratch_doubles": (_sz, [_i]),
+    "nefes_depth_loss_fwd": (_i, [_i, C.c_int64, _p, _p, _p, C.c_double, C.c_double, _i, _p, _p, _p]),
+    "nefes_depth_loss_bwd": (_i, [_i, C.c_int64, _p, _p, _p, C.c_double, C.c_double, _p, _p, _p, _p]),
     "nefes_train_loss_scratch_doubles": (_sz, [_i]),
     "nefes_train_loss_fwd": (_i, [C.POINTER(NefesTrainLossDesc)] + [_p] * 13),
     "nefes_train_loss_bwd": (_i, [C.POINTER(NefesTrainLossDesc)] + [_p] * 20),

@@ -257,10 +257,12 @@ def raygen_px_bwd(px, intr, c2w, g_o, g_d, g_v, want_intr=True):
     return _raygen_bwd(c2w, intr, px, g_o, g_d, g_v, want_intr)
 
 
-def sample_pixels(map, px, out=None):
+def sample_pixels(map, px, out=None, nearest=False):
     """Bilinear sample of a [C, H, W] float32 map at the pixel list px (as_pixels): [C, K], channel-major as the feature-loss kernels read
     it.  Coordinates are clamped to the frame; at an integer coordinate the value is the map's own, exactly.  No gradient (it samples
-    targets).  `out`: a contiguous float32 [C, K] tensor on the map's device that the kernel writes (None: a fresh one)."""
+    targets).  `out`: a contiguous float32 [C, K] tensor on the map's device that the kernel writes (None: a fresh one).
+    `nearest`: the one tap at (clamp(floor(x + 0.5), 0, W-1), clamp(floor(y + 0.5), 0, H-1)) instead (nefes_sample_px_nearest): for maps
+    that must not be blended, such as a depth frame with holes in it."""
     if map.dim() != 3:
         raise RuntimeError(f"nefes_amd: sample_pixels: `map` must be [C, H, W]; got {tuple(map.shape)}")
     Cc, H, W = (int(v) for v in map.shape)
@@ -269,7 +271,8 @@ def sample_pixels(map, px, out=None):
         out = torch.empty(Cc, n, device=map.device)
     elif tuple(out.shape) != (Cc, n):
         raise RuntimeError(f"nefes_amd: sample_pixels: `out` must be [{Cc}, {n}]; got {tuple(out.shape)}")
-    L.check(L.load().nefes_sample_px(Cc, H, W, _chk(map.detach(), "map"), n, _px(px), _chk(out, "out"), _stream()), "nefes_sample_px")
+    name = "nefes_sample_px_nearest" if nearest else "nefes_sample_px"
+    L.check(getattr(L.load(), name)(Cc, H, W, _chk(map.detach(), "map"), n, _px(px), _chk(out, "out"), _stream()), name)
     return out
 
 
@@ -1008,16 +1011,18 @@ class RenderFineFH(torch.autograd.Function):
     compositing -> per-ray feature head; and back: feature head -> compositing backward, which leaves the static weight where the g
     channels' gradient would go (COMP_FEAT_WEIGHTS_ONLY) -> field backward, which forms d loss / d g = w_s g_gmap[ray] itself.  One node
     because that backward hands TWO tensors from the compositor's stage to the field's (g_raw_t and the per-ray g_gmap).
-    -> (rgb [N,3], feat [N,C], disp [N], acc [N]); differentiable w.r.t. rays_o, rays_d, viewdirs."""
+    -> (rgb [N,3], feat [N,C], disp [N], acc [N]); differentiable w.r.t. rays_o, rays_d, viewdirs.
+    `want_depth`: a fifth output, the compositor's depth [N] = sum_s w_s z_s over the weights the variant uses, with its gradient
+    handed to the compositing backward (g_depth); without it the node returns and launches exactly what it did before."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, z, pk, w_f, w_f_t, b_f, flags, beta_min, emit_gmap=False):
+    def forward(ctx, rays_o, rays_d, viewdirs, z, pk, w_f, w_f_t, b_f, flags, beta_min, emit_gmap=False, want_depth=False):
         rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
         N, S = z.shape
         need = any(ctx.needs_input_grad[:3])
         Cg = pk.width // 2
         raw_t, masks = _fh_fwd(pk, rays_o, rays_d, viewdirs, z, need)
-        rgb, gmap, disp, acc, _, _, _ = composite_fwd(raw_t, z, Cg + 1, flags, beta_min)
+        rgb, gmap, disp, acc, depth, _, _ = composite_fwd(raw_t, z, Cg + 1, flags, beta_min)
         if emit_gmap:
             # the caller applies the feature head itself, folded into whatever linear layer consumes the features (the refinement loop:
             # FusionNet's first convolution, FusionNet.forward_prepared_gmap): feat = [N, Cg + 1] = (sum_s w_s g_s, sum_s w_s)
@@ -1032,19 +1037,19 @@ class RenderFineFH(torch.autograd.Function):
         ctx.pk, ctx.have, ctx.pk_gen, ctx.cfg, ctx.emit_gmap = pk, need, pk.generation, (Cg, int(flags)), bool(emit_gmap)
         if need:
             ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks, w_f, b_f)
-        return rgb, feat, disp, acc
+        return (rgb, feat, disp, acc, depth) if want_depth else (rgb, feat, disp, acc)
 
     @staticmethod
-    def backward(ctx, g_rgb, g_feat, g_disp, g_acc):
+    def backward(ctx, g_rgb, g_feat, g_disp, g_acc, g_depth=None):
         if not ctx.have:
-            return (None,) * 11
+            return (None,) * 12
         rays_o, rays_d, viewdirs, z, raw_t, masks, w_f, b_f = ctx.saved_tensors
         N, S = z.shape
         pk = ctx.pk
         pk.check_generation(ctx.pk_gen)
         Cg, flags = ctx.cfg
         fix = lambda g: None if (g is None or g.numel() == 0) else _f32(g)
-        g_rgb, g_feat, g_disp, g_acc = fix(g_rgb), fix(g_feat), fix(g_disp), fix(g_acc)
+        g_rgb, g_feat, g_disp, g_acc, g_depth = fix(g_rgb), fix(g_feat), fix(g_disp), fix(g_acc), fix(g_depth)
         g_gmap = None
         if g_feat is not None and ctx.emit_gmap:
             g_gmap = g_feat                                  # already d loss / d (sum_s w_s g_s, sum_s w_s)
@@ -1058,9 +1063,9 @@ class RenderFineFH(torch.autograd.Function):
         g_raw_t = torch.empty_like(raw_t)          # (the g channels' rows beyond the first are neither written nor read)
         with _timed("composite_bwd"):
             L.check(L.load().nefes_composite_bwd(N, S, Cg + 1, flags | L.COMP_FEAT_WEIGHTS_ONLY, _chk(raw_t, "raw_t"), _chk(z, "z"),
-                                                 _chk(g_rgb, "g_rgb"), None, _chk(g_disp, "g_disp"), _chk(g_acc, "g_acc"), None, None, None,
-                                                 _chk(g_raw_t, "g_raw_t"), _stream()), "nefes_composite_bwd")
-        return _fh_bwd(pk, rays_o, rays_d, viewdirs, z, raw_t, g_raw_t, g_gmap, masks) + (None,) * 8
+                                                 _chk(g_rgb, "g_rgb"), None, _chk(g_disp, "g_disp"), _chk(g_acc, "g_acc"), _chk(g_depth, "g_depth"),
+                                                 None, None, _chk(g_raw_t, "g_raw_t"), _stream()), "nefes_composite_bwd")
+        return _fh_bwd(pk, rays_o, rays_d, viewdirs, z, raw_t, g_raw_t, g_gmap, masks) + (None,) * 9
 
 
 class FieldFromPoints(torch.autograd.Function):
@@ -1968,6 +1973,77 @@ def upsampled_pixel_cosine_loss(x, target, size, crop=0, groups=1, return_cos=Fa
     `mask` (uint8 [groups, OH-2crop, OW-2crop]: of the up-sampled, cropped pixels) as in pixel_cosine_loss.  There is no prepared-target
     form of this loss: the normalisation is per pixel."""
     return _feature_loss("uppixcos", x, target, (int(size[0]), int(size[1]), int(crop)), groups, mask, out, return_cos)
+
+
+class DepthLoss(torch.autograd.Function):
+    """depth_loss below as one autograd node: one launch forward (nefes_depth_loss_fwd), one backward (nefes_depth_loss_bwd), to
+    `disp` only.  Returns (loss, per_group): per_group the float64 values L_g [G] at the head of the kernel's scratch (weight not
+    applied; a view, no gradient).  Every check runs before anything is launched."""
+
+    @staticmethod
+    def forward(ctx, disp, target, mask, cfg, out):
+        delta, weight, accumulate = cfg
+        df = _f32(disp)
+        if df.dim() == 0 or df.numel() == 0:
+            raise ValueError(f"nefes_amd: depth_loss: `disp` must be [P] or [G, ...pixels]; got {tuple(disp.shape)}")
+        G = 1 if df.dim() == 1 else int(df.shape[0])
+        df = df.reshape(G, -1)
+        P = int(df.shape[1])
+        if not torch.is_tensor(target) or target.numel() != G * P or target.dtype != torch.float32:
+            raise ValueError(f"nefes_amd: depth_loss: `target` must be a float32 tensor of disp's {G * P} elements ({tuple(disp.shape)}); got "
+                             + (f"{target.dtype} {tuple(target.shape)}" if torch.is_tensor(target) else type(target).__name__))
+        tf = target.detach().reshape(G, P)
+        mk = None if mask is None else _loss_mask(mask, G, disp.shape[1:] if disp.dim() > 1 else disp.shape, df.device, "depth_loss")
+        if accumulate and out is None:
+            raise ValueError("nefes_amd: depth_loss(accumulate=True) adds the term to the value it finds in `out`: pass out=")
+        loss = _loss_buffer(out, df.device)
+        lib = L.load()
+        scratch = torch.empty(lib.nefes_depth_loss_scratch_doubles(G), dtype=torch.float64, device=df.device)
+        with _timed("depth_loss_fwd"):
+            L.check(lib.nefes_depth_loss_fwd(G, P, _chk(df, "disp"), _chk(tf, "target"), _chk(mk, "mask", torch.uint8), delta, weight,
+                                             int(accumulate), _chk(scratch, "scratch", torch.float64), _chk(loss, "loss"), _stream()),
+                    "nefes_depth_loss_fwd")
+        ctx.save_for_backward(df, tf, mk, scratch)
+        ctx.cfg = (G, P, delta, weight, disp.shape)
+        per_group = scratch[:G]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(per_group)
+        return loss, per_group
+
+    @staticmethod
+    def backward(ctx, g, _g_groups):
+        if g is None:
+            return (None,) * 5
+        df, tf, mk, scratch = ctx.saved_tensors
+        G, P, delta, weight, shape = ctx.cfg
+        gf = _f32(g).reshape(1)
+        g_disp = torch.empty_like(df)
+        with _timed("depth_loss_bwd"):
+            L.check(L.load().nefes_depth_loss_bwd(G, P, _chk(df, "disp"), _chk(tf, "target"), _chk(mk, "mask", torch.uint8), delta, weight,
+                                                  _chk(scratch, "scratch", torch.float64), _chk(gf, "g_loss"), _chk(g_disp, "g_disp"),
+                                                  _stream()), "nefes_depth_loss_bwd")
+        return g_disp.reshape(shape), None, None, None, None
+
+
+def depth_loss(disp, target, mask=None, delta=0.1, weight=1.0, out=None, accumulate=False, return_groups=False):
+    """A Huber loss between NORMALISED rendered depth and a measured depth map (csrc/depth_loss.hip).  disp [P] or [G, ...pixels]: a
+    render's disp_map -- 1 / disp is depth / (sum of the weights the variant normalises by), z-depth in the scene's units; target: float32,
+    the same number of elements, in those units; mask: uint8 [G, ...pixels] or None.  A pixel is valid iff target is finite and > 0 (sensor
+    holes are 0, Inf or NaN), disp is finite and > 0, and its mask byte is != 0: a select -- an invalid pixel's values are never combined
+    and its gradient is exactly 0.  e = 1 / disp - target; rho = e^2 / (2 delta) for |e| <= delta, |e| - delta / 2 beyond
+    (torch.nn.SmoothL1Loss(beta=delta)); per group the mean of rho over its valid pixels (0 when it has none); the value is
+    weight * their sum over the groups.  Arithmetic in double, one rounding to float32.
+    `out` as in cosine_feature_loss; `accumulate=True`: the value written is what `out` held plus the term, rounded once -- so a total
+    of several losses lands in one buffer without an add of its own (differentiate the losses together:
+    torch.autograd.grad([feature, total], ...)).  `return_groups` adds the per-group values L_g [G] (float64, weight not applied, no
+    gradient).  The gradient goes to `disp`; the target carries none."""
+    delta, weight = float(delta), float(weight)
+    if not (delta > 0 and delta != float("inf")):
+        raise ValueError(f"nefes_amd: depth_loss: delta = {delta!r} must be positive and finite (the Huber threshold, in the scene's units)")
+    if weight != weight or weight in (float("inf"), float("-inf")):
+        raise ValueError(f"nefes_amd: depth_loss: weight = {weight!r} must be finite")
+    loss, groups = DepthLoss.apply(disp, target, mask, (delta, weight, bool(accumulate)), out)
+    return (loss, groups) if return_groups else loss
 
 
 def psnr_ssim(x, y):

@@ -151,7 +151,14 @@ class PoseRefiner:
     ops.draw_pixels -- K distinct pixels, uniform among the mask's valid ones, drawn on the device from the persistent words
     `draw_state` = {seed, tick} -- and a re-sample of the target there, both inside the captured graph: no host read per image or per
     iteration.  Every image starts from {seed=, 0}: its batches depend on (seed, mask) alone.  Such a refiner takes no `pixels=` and no
-    `set_pixels`.  None (default): the fixed list described above."""
+    `set_pixels`.  None (default): the fixed list described above.
+
+    `depth_weight=lambda` (with `depth_huber=delta`, the Huber threshold in the scene's units; None: 0.1) adds the geometric term of an
+    RGB-D query to the loss: lambda * ops.depth_loss(the iteration's disp_map, the image's measured depth) -- `refine(..., depth=)` /
+    `refine_apr(..., depth=)`, z-depth in the units of near / far at the rendered frame's resolution [h, w] (images=B: [B, h, w]; holes
+    are 0, Inf or NaN; a sparse refiner samples the frame at its pixels, nearest, with redraw=R inside the captured iteration).  Only
+    depth validity counts for it -- `mask=` stays the feature term's.  `refiner.loss` is the total, `refiner.depth_loss` the term's last
+    value (float64, lambda not applied).  None (default): exactly the refiner without the term."""
 
     FUSED_UPSAMPLED_LOSS = True      # False: bicubic up-sampling and cosine loss as separate kernels (the tests compare the two)
     # The loop's target is fixed for all iterations of an image: its share of the up-sampled loss (Uy^T target Ux, |target|^2) is
@@ -170,8 +177,10 @@ class PoseRefiner:
     def __init__(self, render_kwargs, args, hwf, near, far, tinyscale=4, lr_r=0.01, lr_t=0.1, lietorch=False,
                  upsample=False, per_pixel=False, world_setup=None, graph=True, device="cuda", adam_capturable=None,
                  fused_glue=True, images=1, pose_model=None, svd_reg=False, learning_rate=1e-5, bn_running_stats=True,
-                 intrinsics=None, learn_focal=False, lr_f=1e-3, masked=False, sparse=None, seed=0, redraw=None):
+                 intrinsics=None, learn_focal=False, lr_f=1e-3, masked=False, sparse=None, seed=0, redraw=None, depth_weight=None,
+                 depth_huber=None):
         self.kw, self.args = dict(render_kwargs), args
+        self.depth_weight, self.depth_huber = _depth_term(depth_weight, depth_huber, fused_glue)
         self.sparse = None if sparse is None else int(sparse)
         if self.sparse is not None:
             _refuse_sparse(self.sparse, pose_model, images, upsample, fused_glue, lietorch)
@@ -274,6 +283,16 @@ class PoseRefiner:
                 self.draw_state = ops.draw_state(int(seed), self.dev)
                 self._state0 = self.draw_state.clone()     # (what _reset copies over draw_state: a device-to-device write)
                 self._mask_u8 = torch.ones(1, self.h, self.w, dtype=torch.uint8, device=self.dev) if self.masked else None
+        # depth_weight=lambda: the image's measured depth at the rendered frame's pixels in ONE persistent float32 buffer [B, h*w] (sparse:
+        # [1, K], sampled -- nearest -- from the frame kept in self._depth_frame) that the depth-loss kernels read in place, and the disp_map
+        # of the iteration's own render (self._disp, kept by _fused / _sparse_features).  self.depth_loss: the term's last value (float64,
+        # lambda not applied; [B] with images=B) -- the head of the kernel's scratch, which a captured iteration keeps at one address.
+        self.depth_loss, self._disp = None, None
+        if self.depth_weight is not None:
+            self.depth_target = torch.zeros(self.B, self.h * self.w if self.sparse is None else self.sparse, device=self.dev)
+            self._depth_frame = torch.zeros(1, self.h, self.w, device=self.dev) if self.sparse is not None else None
+            self.depth_loss = torch.zeros((), dtype=torch.float64, device=self.dev) if self.B == 1 else \
+                torch.zeros(self.B, dtype=torch.float64, device=self.dev)
         self._affine = None            # static [1,12] buffer with the image's colour transform when the exposure network is frozen
         self.graph, self.apr_graph = None, None
 
@@ -305,8 +324,9 @@ class PoseRefiner:
         """sparse: pose -> render(pixels=self.pixels) -> feat_map [K, C] -> [C, K], the layout the loss kernels read (a torch
         transposition: plumbing).  With sparse= in place of the frame, what features() returns."""
         c2w = self._composed_pose()
-        _, _, _, ex = render(self.h, self.w, self.focal, c2w=c2w.reshape(3, 4), near=self.near, far=self.far, img_idx=self.hist,
-                             pixels=self.pixels, **self.kw, **self._camera())
+        _, disp, _, ex = render(self.h, self.w, self.focal, c2w=c2w.reshape(3, 4), near=self.near, far=self.far, img_idx=self.hist,
+                                pixels=self.pixels, **self.kw, **self._camera())
+        self._disp = disp if self.depth_weight is not None else None       # (the depth term's input: _with_depth_term)
         return ex["feat_map"].t()
 
     def _fused(self):
@@ -336,12 +356,13 @@ class PoseRefiner:
             kw = dict(kw, feat_as_gmap=True)               # honoured only where render() takes the factored head (extras["feat_is_gmap"])
         if B == 1:
             # (a view, not c2w[0]: indexing costs a zero fill and a copy in the backward)
-            rgb, _, _, ex = render(self.h, self.w, self.focal, c2w=c2w.reshape(3, 4), near=self.near, far=self.far, img_idx=self.hist, **kw,
-                                   **self._camera())
+            rgb, disp, _, ex = render(self.h, self.w, self.focal, c2w=c2w.reshape(3, 4), near=self.near, far=self.far, img_idx=self.hist, **kw,
+                                      **self._camera())
             feat = ex["feat_map"]
         else:
-            rgb, _, _, ex = render_poses(self.h, self.w, self.focal, c2w, near=self.near, far=self.far, **kw, **self._camera())
+            rgb, disp, _, ex = render_poses(self.h, self.w, self.focal, c2w, near=self.near, far=self.far, **kw, **self._camera())
             rgb, feat = rgb.reshape(-1, 3), ex["feat_map"].reshape(-1, ex["feat_map"].shape[-1])
+        self._disp = disp if self.depth_weight is not None else None       # (the depth term's input: _with_depth_term)
         gmap = bool(ex.get("feat_is_gmap", False))
         if fused_input:
             # colour transform + normalisation + the NCHW concatenation as one launch each way (ops.fusion_input)
@@ -365,6 +386,31 @@ class PoseRefiner:
         return fused
 
     def _loss(self):
+        """The iteration's loss: the feature term (_feature_term) and, on a PoseRefiner(depth_weight=), the depth term on the disp_map
+        the same render returned.  Returns (what to differentiate -- a scalar, or the tuple of scalars whose sum is the loss --, per-image
+        totals [B] or the total itself)."""
+        loss, per_image = self._feature_term()
+        if self.depth_weight is None:
+            return loss, per_image
+        return self._with_depth_term(loss, per_image)
+
+    def _with_depth_term(self, loss, per_image):
+        """lambda * ops.depth_loss(disp_map, the image's depth; one group per image) next to the feature term: the two scalars are
+        differentiated together -- they meet in the render's own node, as g_feat and g_disp -- and never added by torch.  One image: the
+        feature kernel left its value in self.loss and the depth kernel adds its term there (`accumulate`): one launch forward, one
+        backward, no arithmetic launch.  images=B: the per-image totals are formed from the kernel's per-group values (torch glue).
+        Only depth validity counts (target and disp): the feature term's mask is not the depth term's."""
+        disp, self._disp = self._disp.reshape(self.B, -1), None            # (not kept: it would hold the iteration's autograd graph)
+        if self.B == 1:
+            total, groups = ops.depth_loss(disp, self.depth_target, delta=self.depth_huber, weight=self.depth_weight, out=self.loss,
+                                           accumulate=True, return_groups=True)
+            self.depth_loss = groups.reshape(())
+            return (loss, total), total.detach()
+        term, groups = ops.depth_loss(disp, self.depth_target, delta=self.depth_huber, weight=self.depth_weight, return_groups=True)
+        self.depth_loss = groups
+        return (loss, term), per_image + (groups * self.depth_weight).float()
+
+    def _feature_term(self):
         """DFM_optimization_NFF (:310-337): pose -> render -> affine colour transform -> fusion CNN -> feature loss.
         Returns (scalar to differentiate, per-image losses [B] or the same scalar).  One image on the fused glue: the library's loss
         kernel writes its value straight into the static buffer self.loss (`out=`: no 4-byte copy launch per iteration); everything
@@ -478,12 +524,16 @@ class PoseRefiner:
             self._one = torch.ones_like(loss)
         return self._one
 
+    def _ones_for(self, loss):
+        """_one_like for what _loss returns to differentiate: a scalar, or a tuple of scalars (one root gradient each, the same tensor)."""
+        return tuple(self._one_like(l) for l in loss) if isinstance(loss, tuple) else self._one_like(loss)
+
     def loss_and_grad(self):
         """Loss at the current (r, t) and its gradient, written into the parameters' static .grad buffers (no optimizer step).
         The gradients are copied over the previous ones: nothing has to be zeroed between iterations."""
         loss, per_image = self._loss()
         params = [self.model.r, self.model.t] + ([] if self.log_f is None else [self.log_f])
-        for p, g in zip(params, torch.autograd.grad(loss, params, grad_outputs=self._one_like(loss))):
+        for p, g in zip(params, torch.autograd.grad(loss, params, grad_outputs=self._ones_for(loss))):
             if p.grad is None:
                 p.grad = torch.empty_like(p)
             if g.data_ptr() != p.grad.data_ptr():          # (the fused pose kernel writes the parameters' .grad itself)
@@ -499,6 +549,8 @@ class PoseRefiner:
             ops.draw_pixels(self.h, self.w, self.sparse, self.draw_state, mask=self._mask_u8, period=self.redraw, advance=True,
                             out=self.pixels)
             ops.sample_pixels(self._frame, self.pixels, out=self.target)
+            if self.depth_weight is not None:              # (a drawn pixel without a valid depth just does not count: no host read)
+                ops.sample_pixels(self._depth_frame, self.pixels, out=self.depth_target, nearest=True)
 
     def _iteration(self):
         if self.redraw is not None:
@@ -593,6 +645,8 @@ class PoseRefiner:
         with torch.no_grad():
             self.pixels.copy_(px)
             ops.sample_pixels(self._frame, self.pixels, out=self.target)
+            if self.depth_weight is not None:              # (nearest: a depth must not be blended across a hole or an edge)
+                ops.sample_pixels(self._depth_frame, self.pixels, out=self.depth_target, nearest=True)
             if self.masked:
                 if self._frame_mask is None:
                     self.mask.fill_(1)
@@ -603,9 +657,10 @@ class PoseRefiner:
                     if not bool(self.mask.any()):
                         raise ValueError("nefes_amd: none of the pixels is valid in the image's mask (mask > 0): nothing to refine against")
 
-    def _reset(self, init_c2w, feature_target, hist, mask=None, pixels=None):
+    def _reset(self, init_c2w, feature_target, hist, mask=None, pixels=None, depth=None):
         if self.sparse is None:
             self._set_mask(mask)
+        self._set_depth(depth)                             # (before the pixels: set_pixels samples the depth frame at them)
         with torch.no_grad():
             self.model.r.zero_()
             self.model.t.zero_()
@@ -710,7 +765,52 @@ class PoseRefiner:
             self._step(m, i, iters, losses, checks)
         return m.finish(m.read(), before, checks, losses)
 
-    def _job(self, *job, mask=None, pixels=None):
+    def _job(self, *job, mask=None, pixels=None, depth=None, apr=False):
+        """The job tuple of an image (_job_without_depth) and, on a PoseRefiner(depth_weight=), the image's measured depth behind it: the
+        sixth element (mode 2, `apr`: the fifth), the ones before it filled with None."""
+        job = self._job_without_depth(*job, mask=mask, pixels=pixels)
+        if self.depth_weight is None:
+            if depth is not None:
+                raise ValueError("nefes_amd: depth= needs a PoseRefiner(depth_weight=...): this one was built without the depth term")
+            return job
+        if depth is None:
+            raise ValueError("nefes_amd: this PoseRefiner was built with depth_weight=: pass the image's measured depth, depth=[h, w] "
+                             f"= {(self.h, self.w)}, the rendered frame's resolution")
+        n = 4 if apr else 5
+        return job + (None,) * (n - len(job)) + (self._checked_depth(depth),)
+
+    def _checked_depth(self, depth):
+        """The image's measured depth as float32 [B, h, w]; a shape other than the rendered frame's is refused, naming both."""
+        if depth is None:
+            raise ValueError("nefes_amd: this PoseRefiner was built with depth_weight=: pass the image's measured depth (depth=)")
+        d = torch.as_tensor(depth)
+        h, w = self.h, self.w
+        ok = {(h, w), (1, h, w)} if self.B == 1 else {(self.B, h, w)}
+        if tuple(d.shape) not in ok:
+            raise ValueError(f"nefes_amd: the depth frame has shape {tuple(d.shape)}; this refiner renders {(h, w)}"
+                             + (f" for each of {self.B} images: [{self.B}, {h}, {w}]" if self.B > 1 else "")
+                             + " (refine.resized_depth brings a full-resolution sensor frame there)")
+        return d.to(torch.float32).reshape(self.B, h, w)
+
+    def _set_depth(self, depth):
+        """The image's measured depth into the static buffers, IN PLACE (a captured iteration keeps reading them).  A frame without a
+        valid pixel (finite and > 0) is refused -- one host read per image, outside the loop.  sparse: the frame is kept and sampled,
+        nearest, at the refiner's pixels (set_pixels; with redraw=R by the captured iteration itself)."""
+        if self.depth_weight is None:
+            if depth is not None:
+                raise ValueError("nefes_amd: depth= needs a PoseRefiner(depth_weight=...): this one was built without the depth term")
+            return
+        d = self._checked_depth(depth).to(self.dev)
+        empty = (~(torch.isfinite(d) & (d > 0)).reshape(self.B, -1).any(1)).nonzero().flatten().tolist()
+        if empty:
+            raise ValueError(f"nefes_amd: the depth frame of image(s) {empty} has no valid pixel (finite and > 0): nothing to compare with")
+        with torch.no_grad():
+            if self.sparse is None:
+                self.depth_target.copy_(d.reshape(self.depth_target.shape))
+            else:
+                self._depth_frame.copy_(d)
+
+    def _job_without_depth(self, *job, mask=None, pixels=None):
         """The job tuple of an image: with a fourth element, its mask, on a masked refiner (None: all valid); on a sparse refiner a
         fourth and a fifth, mask and pixels (None: drawn)."""
         if self.sparse is not None:
@@ -729,14 +829,17 @@ class PoseRefiner:
             return job
         return job + (None if mask is None else torch.as_tensor(mask),)
 
-    def refine(self, init_c2w, feature_target, hist, iters=50, mask=None, pixels=None):
+    def refine(self, init_c2w, feature_target, hist, iters=50, mask=None, pixels=None, depth=None):
         """One image (images=1): (refined 4x4 c2w, losses [iters]) -- with learn_focal (refined c2w, losses, log_f [1]).
         A batch (images=B): init_c2w [B,4,4], feature_target [B,C,h,w], hist [B,10] -> (refined poses [B,4,4], losses [iters,B]), each image as if refined alone.
         mask (PoseRefiner(masked=True)): the image's valid pixels, > 0, in the target's spatial shape [th,tw] or [1,th,tw] (a batch:
         [B,th,tw]); None: all valid.
         pixels (PoseRefiner(sparse=K)): the [K, 2] points (x, y) of the rendered (h, w) frame to match at; feature_target is that frame's
-        features [C, h, w], sampled there once.  None: K distinct integer pixels are drawn."""
-        return self._run(self._mode(), self._job(init_c2w, feature_target, hist, mask=mask, pixels=pixels), iters)
+        features [C, h, w], sampled there once.  None: K distinct integer pixels are drawn.
+        depth (PoseRefiner(depth_weight=)): the image's measured z-depth in the scene's units at the RENDERED frame's resolution, [h,w]
+        (a batch: [B,h,w]; a sparse refiner takes the frame too and samples it, nearest, at its pixels); holes are 0, Inf or NaN
+        (resized_depth brings a full-resolution sensor frame here).  The losses returned are the totals, feature + lambda * depth."""
+        return self._run(self._mode(), self._job(init_c2w, feature_target, hist, mask=mask, pixels=pixels, depth=depth), iters)
 
     refine_batch = refine
 
@@ -747,8 +850,10 @@ class PoseRefiner:
         params = [p for p in self.apr.parameters() if p.requires_grad]
         # loss.backward() in the reference (train_on_batch, DFM_pose_refine.py:318) tolerates parameters the loss never touches --
         # DFNet's adaptation_layers with return_feature=False (feature/dfnet.py:142): their .grad stays None and Adam skips them
-        for p, g in zip(params, torch.autograd.grad(loss, params, grad_outputs=self._one_like(loss), allow_unused=True)):
+        for p, g in zip(params, torch.autograd.grad(loss, params, grad_outputs=self._ones_for(loss), allow_unused=True)):
             p.grad = g
+        if isinstance(loss, tuple):                        # (feature term, total: the depth kernel added its term in self.loss)
+            loss = loss[-1]
         if loss.data_ptr() != self.loss.data_ptr():
             self.loss.copy_(loss.detach())
         return self.loss
@@ -777,12 +882,13 @@ class PoseRefiner:
             pose = (self.apr if net is None else net)(self.photo).reshape(1, 3, 4)
             return (svd_reg(pose) if self.svd_reg else pose)[0]
 
-    def _apr_image_state(self, photo, feature_target, hist, mask=None):
+    def _apr_image_state(self, photo, feature_target, hist, mask=None, depth=None):
         """Per-image state of train_on_batch, written IN PLACE (a captured iteration keeps reading the same buffers): the query image, its
         cropped features (:125), a fresh copy of the regression network (:209), the histogram and the colour transform's twelve numbers;
         on a masked refiner the image's mask of the cropped pixels."""
         dev = self.dev
         self._set_mask(mask)
+        self._set_depth(depth)
         with torch.no_grad():
             self.photo.copy_(photo.to(dev).reshape(self.photo.shape))
             self.target.copy_(feature_target.to(dev).reshape(self.C, self.H, self.W)[:, 10:-10, 10:-10])
@@ -795,8 +901,8 @@ class PoseRefiner:
             self.hist.copy_(hist.to(dev).reshape(1, 10))
             self._exposure_into_affine()
 
-    def _apr_set_state(self, photo, feature_target, hist, mask=None):
-        self._apr_image_state(photo, feature_target, hist, mask)
+    def _apr_set_state(self, photo, feature_target, hist, mask=None, depth=None):
+        self._apr_image_state(photo, feature_target, hist, mask, depth)
         self._apr_fresh_adam()
 
     def _apr_iteration(self):
@@ -831,14 +937,15 @@ class PoseRefiner:
                 pose = first
         return pose.detach().clone(), losses, info
 
-    def refine_apr(self, photo, feature_target, hist, iters=50, verification=True, mask=None):
+    def refine_apr(self, photo, feature_target, hist, iters=50, verification=True, mask=None, depth=None):
         """One query image, `pose_only=2`: `photo` [1,3,H,W], `feature_target` [C,H,W] (the query image's features at full
         resolution; cropped here as :125 does).  Returns (pose [3,4] in the regression network's coordinates, losses [iters],
         info = dict(psnr=(first, last), ssim=(first, last), retreat=bool)).  PoseRefiner(graph=True): the iteration is captured on
         first use and replayed (the regression network must be capturable: no host reads, static shapes).
         mask (PoseRefiner(masked=True)): the valid pixels of the CROPPED full-resolution image, [H-20, W-20] (full_resolution_mask);
         the verification step's PSNR / SSIM stay unmasked, as in the reference."""
-        return self._run(self._mode(apr=True, verification=verification), self._job(photo, feature_target, hist, mask=mask), iters)
+        return self._run(self._mode(apr=True, verification=verification),
+                         self._job(photo, feature_target, hist, mask=mask, depth=depth, apr=True), iters)
 
 
 def _refuse_sparse(K, pose_model, images, upsample, fused_glue, lietorch):
@@ -885,6 +992,39 @@ def resized_intrinsics(K, from_hw, to_hw):
     return (float(fx * sx), float(fy * sy), float((cx + 0.5) * sx - 0.5), float((cy + 0.5) * sy - 0.5))
 
 
+def resized_depth(D, from_hw, to_hw):
+    """A sensor's depth frame [..., H, W] at the rendered resolution (h, w): at each rendered pixel the NEAREST source pixel to its centre,
+    under resized_intrinsics' convention -- the centre of pixel x of the small image lies at (x + 0.5) W / w of the large one's continuous
+    axis, i.e. in source pixel floor((x + 0.5) W / w) (integer arithmetic).  Nothing is blended: holes stay holes and a depth edge stays
+    an edge.  Plain torch indexing, set-up only; the values are not touched (convert units and mark holes before or after)."""
+    D = torch.as_tensor(D)
+    (H, W), (h, w) = (int(v) for v in from_hw), (int(v) for v in to_hw)
+    if tuple(D.shape[-2:]) != (H, W):
+        raise ValueError(f"nefes_amd: resized_depth: the frame has shape {tuple(D.shape)}, from_hw says {(H, W)}")
+    ys = ((2 * torch.arange(h, device=D.device) + 1) * H).div(2 * h, rounding_mode="floor").clamp_(max=H - 1)
+    xs = ((2 * torch.arange(w, device=D.device) + 1) * W).div(2 * w, rounding_mode="floor").clamp_(max=W - 1)
+    return D[..., ys[:, None], xs[None, :]]
+
+
+def _depth_term(depth_weight, depth_huber, fused_glue):
+    """PoseRefiner(depth_weight=lambda, depth_huber=delta) validated: (lambda, delta) as floats, or (None, None) without the term.
+    delta: the Huber threshold in the scene's units (None: 0.1)."""
+    if depth_weight is None:
+        if depth_huber is not None:
+            raise ValueError(f"nefes_amd: PoseRefiner(depth_huber={depth_huber}) without depth_weight=: there is no depth term to apply it to")
+        return None, None
+    lam, delta = float(depth_weight), 0.1 if depth_huber is None else float(depth_huber)
+    if not (lam > 0 and lam != float("inf")):
+        raise ValueError(f"nefes_amd: PoseRefiner(depth_weight={depth_weight}): the weight of the depth term must be positive and finite "
+                         "(None: no depth term)")
+    if not (delta > 0 and delta != float("inf")):
+        raise ValueError(f"nefes_amd: PoseRefiner(depth_huber={depth_huber}): the Huber threshold must be positive and finite, in the "
+                         "scene's units")
+    if not fused_glue:
+        raise NotImplementedError("nefes_amd: PoseRefiner(depth_weight=...) runs on the library's loss kernels (fused_glue=True)")
+    return lam, delta
+
+
 _nothing = lambda *args: None
 
 
@@ -915,7 +1055,7 @@ def _zero_optimizer_state(opt):
                     v.zero_()
 
 
-def _apr_kernels_bit_stable(r, photo, feature_target, hist, mask=None, trials=6):
+def _apr_kernels_bit_stable(r, photo, feature_target, hist, mask=None, depth=None, trials=6):
     """EMPIRICAL guard for refine_apr_concurrently.  The regression network, its backward, torch's Adam and the verification step are the
     CALLER'S / torch's kernels; next to another stream's field kernels such code is exposed to the packed-fp32 finding of DESIGN.md 4.7
     (hipcc vectorises torch's kernels the way it vectorised ours) -- whether a given network's kernels contain the affected forms cannot be
@@ -938,7 +1078,7 @@ def _apr_kernels_bit_stable(r, photo, feature_target, hist, mask=None, trials=6)
     side = torch.cuda.Stream(device=dev)
 
     def run(storm):
-        r._apr_set_state(photo, feature_target, hist, mask)
+        r._apr_set_state(photo, feature_target, hist, mask, depth)
         torch.cuda.synchronize(dev)
         keep = []
         if storm:

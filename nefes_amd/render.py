@@ -41,7 +41,8 @@ def rays_per_launch(cfg, network_fn, network_fine, device, train=False):
     S = cfg.N_samples + cfg.N_importance if not cfg.use_fine_only or cfg.N_importance == 0 else cfg.N_importance
     Wd, C = net.W, net.W_features
     dev = torch.device(device)
-    key = (Wd, C, S, cfg.N_samples, bool(train), dev.type, dev.index)
+    want_depth = bool(getattr(cfg, "depth_map", False))
+    key = (Wd, C, S, cfg.N_samples, bool(train), dev.type, dev.index) + ((True,) if want_depth else ())
     if key in _STEP:
         return _STEP[key]
     R = 3 + C + 6
@@ -50,7 +51,7 @@ def rays_per_launch(cfg, network_fn, network_fine, device, train=False):
         # rows per sample of `acts` and `dacts` (csrc/layout.h nefes_train_row(..., NEFES_TB_END)): the head block is sized by the
         # head CLASS (nefes_head_ntr: one tile for 3 + C <= 32, five otherwise), not by C
         per_sample += 4 * (64 + 32 + 9 * Wd + 2 * Wd + 32 * (1 if 3 + C <= 32 else 5) + 64) * 2
-    per_ray = per_sample * S + (cfg.N_samples * 4) * 4 + 256
+    per_ray = per_sample * S + (cfg.N_samples * 4) * 4 + 256 + (4 if want_depth else 0)      # (depth_map: one more float per ray)
     _PER_RAY[key] = per_ray
     try:
         total = torch.cuda.get_device_properties(dev).total_memory
@@ -67,7 +68,8 @@ def _clamp_to_free_memory(step, cfg, network_fn, network_fine, device):
     net = network_fine if (network_fine is not None and cfg.N_importance > 0) else network_fn
     S = cfg.N_samples + cfg.N_importance if not cfg.use_fine_only or cfg.N_importance == 0 else cfg.N_importance
     dev = torch.device(device)
-    per_ray = _PER_RAY.get((net.W, net.W_features, S, cfg.N_samples, False, dev.type, dev.index))
+    per_ray = _PER_RAY.get((net.W, net.W_features, S, cfg.N_samples, False, dev.type, dev.index)
+                           + ((True,) if getattr(cfg, "depth_map", False) else ()))
     if per_ray is None:
         return step
     try:
@@ -93,7 +95,10 @@ def _cfg(kwargs):
         # nefes_amd-private (the refinement loop sets it): where the factored feature head applies, return its per-ray INPUT
         # (sum_s w_s g_s, sum_s w_s) [N, W/2 + 1] as "feat_map" and say so with extras["feat_is_gmap"]; the caller folds the head into the
         # linear layer that consumes the features (FusionNet's first convolution)
-        feat_as_gmap=bool(kwargs.get("feat_as_gmap", False)))
+        feat_as_gmap=bool(kwargs.get("feat_as_gmap", False)),
+        # depth_map=True: extras["depth_map"] [N], the reference's depth_map (nerfh_nff.py:113,164) = sum_s w_s z_s over the weights the
+        # variant composites with -- z is z-depth (rays_d is unnormalised with camera z = -1) -- differentiable like the other maps
+        depth_map=bool(kwargs.get("depth_map", False)))
 
 
 def _trainable(net):
@@ -171,7 +176,7 @@ def _render_core(rays_o, rays_d, viewdirs, near, far, network_fn, network_fine, 
         raw_c = field(network_fn, pk_c, L.FIELD_STATIC, z)
         if cfg.raw_noise_std > 0.:
             raw_c = _with_density_noise(raw_c, C, cfg.raw_noise_std)
-        rgb0, feat0, disp0, acc0, _, w0, _ = ops.Composite.apply(raw_c, z, C, 0, 0.1)
+        rgb0, feat0, disp0, acc0, depth0, w0, _ = ops.Composite.apply(raw_c, z, C, 0, 0.1)
     if Ni == 0:
         if cfg.test_time:
             raise NotImplementedError("nefes_amd: N_importance == 0 at test time renders nothing in the reference "
@@ -179,6 +184,8 @@ def _render_core(rays_o, rays_d, viewdirs, near, far, network_fn, network_fine, 
         ret = {"rgb_map": rgb0, "disp_map": disp0, "acc_map": acc0}
         if cfg.nerfh_nff:
             ret["feat_map"] = feat0
+        if cfg.depth_map:
+            ret["depth_map"] = depth0
         return ret
     # hierarchical sampling (:132-141); z_samples are detached in the reference
     u = None if cfg.perturb == 0. else torch.rand(N, Ni, device=dev)
@@ -218,9 +225,11 @@ def _fine_pass(rays_o, rays_d, viewdirs, z_fine, z_samples, network_fine, cfg, C
             flags |= L.COMP_STATIC_ONLY
         if cfg.white_bkgd:
             flags |= L.COMP_WHITE_BKGD
-        rgb, feat, disp, acc = ops.RenderFineFH.apply(rays_o, rays_d, viewdirs, z_f, pk_fh, w_f, w_f_t, b_f, flags, float(network_fine.beta_min),
-                                                      cfg.feat_as_gmap)
+        rgb, feat, disp, acc, *depth = ops.RenderFineFH.apply(rays_o, rays_d, viewdirs, z_f, pk_fh, w_f, w_f_t, b_f, flags,
+                                                              float(network_fine.beta_min), cfg.feat_as_gmap, cfg.depth_map)
         ret = {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "feat_map": feat}
+        if cfg.depth_map:
+            ret["depth_map"] = depth[0]
         if cfg.feat_as_gmap:
             ret["feat_is_gmap"] = True
         return ret
@@ -247,6 +256,8 @@ def _fine_pass(rays_o, rays_d, viewdirs, z_fine, z_samples, network_fine, cfg, C
     ret = {"rgb_map": rgb, "disp_map": disp, "acc_map": acc}
     if cfg.nerfh_nff:
         ret["feat_map"] = feat
+    if cfg.depth_map:
+        ret["depth_map"] = depth
     if not cfg.test_time:                                                            # :160-173
         ret["rgb0"], ret["disp0"], ret["acc0"] = rgb0, disp0, acc0
         ret["z_std"] = torch.std(z_samples, dim=-1, unbiased=False)
@@ -363,7 +374,11 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     `intrinsics` (fx, fy, cx, cy) of the rendered H x W image -- a float32 [4] device tensor, a 4-sequence or a 3 x 3 K
     (ops.as_intrinsics) -- replaces `focal` and the centred principal point for the rays of `c2w` and of `c2w_staticcam`.  The kernels
     read it from device memory when they run: a device tensor is used as is, so in-place updates reach a captured graph and a tensor
-    that requires a gradient gets one."""
+    that requires a gradient gets one.
+
+    `depth_map=True` (among the keyword arguments, like the reference's own switches) adds extras["depth_map"] [N]: the reference's
+    depth_map, sum_s w_s z_s over the weights the variant composites with -- z-depth, in the units of near / far -- differentiable like
+    the other maps; chunked renders concatenate it.  Without it the key is absent."""
     if not use_viewdirs:
         raise NotImplementedError("nefes_amd: the NeFeS field always uses view directions (use_viewdirs=True)")
     cfg = _cfg(kwargs)
