@@ -899,62 +899,6 @@ _NO_SIGMA_BWD = ("nefes_amd: the sigma-only field pass has no backward (the refe
                  "nerfh_nff.py:192-202)")
 
 
-class FieldFromRays(torch.autograd.Function):
-    """Fused pts = o + d*z -> embed -> MLP (rendering.py:142 + nerfh_nff.py:217-231, :525-576) on whichever kernels field_route names
-    for `pk` (a tuned or a generic pack).  Returns raw_t [N, R, S].  Differentiable w.r.t. rays_o, rays_d, viewdirs in FULL and
-    STATIC mode (frozen weights)."""
-
-    @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, z, pk, mode):
-        rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
-        N, S = z.shape
-        need = mode in (L.FIELD_FULL, L.FIELD_STATIC) and any(ctx.needs_input_grad[:3])
-        raw_t, masks = _field_fwd(pk, mode, N, S, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs, want_masks=need)
-        ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
-        if need:
-            ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks)
-        return raw_t
-
-    @staticmethod
-    def backward(ctx, g_raw_t):
-        if not ctx.have:
-            raise NotImplementedError(_NO_SIGMA_BWD)
-        rays_o, rays_d, viewdirs, z, raw_t, masks = ctx.saved_tensors
-        N, S = z.shape
-        ctx.pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = _field_bwd(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs)
-        g_o, g_d, g_v = ray_grad_reduce(N, S, z, g_pts, g_vs)
-        return g_o, g_d, g_v, None, None, None
-
-
-class FeatHead(torch.autograd.Function):
-    """The factored head's per-ray part: feat [N, C] = gmap[:, :F] W^T + gmap[:, F:] b (csrc/refine.hip feat_head_*_kernel; W, b frozen)."""
-
-    @staticmethod
-    def forward(ctx, gmap, w, w_t, b):
-        gmap = _f32(gmap)
-        N, F1 = gmap.shape
-        C = w.shape[0]
-        feat = torch.empty(N, C, device=gmap.device)
-        with _timed("feat_head_fwd"):
-            L.check(L.load().nefes_feat_head_fwd(N, C, F1 - 1, _chk(gmap, "gmap"), _chk(w_t, "w_t"), _chk(b, "b"), _chk(feat, "feat"), _stream()),
-                    "nefes_feat_head_fwd")
-        ctx.save_for_backward(w, b)
-        ctx.F1 = F1
-        return feat
-
-    @staticmethod
-    def backward(ctx, g_feat):
-        w, b = ctx.saved_tensors
-        g_feat = _f32(g_feat)
-        N, C = g_feat.shape
-        g_gmap = torch.empty(N, ctx.F1, device=g_feat.device)
-        with _timed("feat_head_bwd"):
-            L.check(L.load().nefes_feat_head_bwd(N, C, ctx.F1 - 1, _chk(g_feat, "g_feat"), _chk(w, "w"), _chk(b, "b"), _chk(g_gmap, "g_gmap"),
-                                                 _stream()), "nefes_feat_head_bwd")
-        return g_gmap, None, None, None
-
-
 def _fh_fwd(pk, rays_o, rays_d, viewdirs, z, want_masks):
     """The factored-head forward launch -> (raw_t [N, 3 + (W/2 + 1) + 6, S] = rgb | g | ones | sigma | transient (5), masks)."""
     N, S = z.shape
@@ -969,7 +913,7 @@ def _fh_fwd(pk, rays_o, rays_d, viewdirs, z, want_masks):
 
 
 def _fh_bwd(pk, rays_o, rays_d, viewdirs, z, raw_t, g_raw_t, g_gmap, masks):
-    """The factored-head backward launch + the reduction over each ray's samples -> (g_o, g_d, g_v).  g_gmap [N, W/2 + 1]: the per-ray
+    """The factored-head backward launch -> (d loss / d pts, d loss / d viewdirs), per sample [N*S, 3].  g_gmap [N, W/2 + 1]: the per-ray
     gradient of the composited g channels (the kernel forms d loss / d g = w_s g_gmap[ray] itself), or None: g_raw_t holds it."""
     N, S = z.shape
     g_pts, g_vs = torch.empty(N * S, 3, device=z.device), torch.empty(N * S, 3, device=z.device)
@@ -978,7 +922,115 @@ def _fh_bwd(pk, rays_o, rays_d, viewdirs, z, raw_t, g_raw_t, g_gmap, masks):
                                                _chk(viewdirs, "viewdirs"), _chk(raw_t, "raw_t"), _chk(g_raw_t, "g_raw_t"),
                                                _chk(g_gmap, "g_gmap"), _chk(masks, "masks", torch.int32), _chk(g_pts, "g_pts"),
                                                _chk(g_vs, "g_vs"), _stream()), "nefes_field_bwd_h3_fh")
-    return ray_grad_reduce(N, S, z, g_pts, g_vs)
+    return g_pts, g_vs
+
+
+# What tells the kinds of frozen-field Function apart; everything else they do is _field_forward / _field_backward.
+#   inputs:  the launchers' keyword of each tensor input, in apply()'s order; the first n_diff are differentiable (z is not)
+#   saved:   the inputs the backward launch reads again (raw_t and the ReLU masks always are)
+#   modes:   (pk, mode) -> this pass has a backward
+#   refusal: what backward() raises where it has none; None: it returns None for every input
+#   per_ray: the per-sample gradients are reduced along each ray with its depths -> (g_o, g_d, g_v).  Otherwise the first input's
+#            gradient is returned per sample and g_v comes from the same reduction on zero depths
+#   n_args:  apply()'s argument count, the length of what backward() returns
+FieldKind = collections.namedtuple("FieldKind", "inputs n_diff saved modes refusal per_ray n_args")
+_RAY_INPUTS = ("rays_o", "rays_d", "viewdirs", "z")
+_full_or_static = lambda pk, mode: mode in (L.FIELD_FULL, L.FIELD_STATIC)
+_RAYS = FieldKind(_RAY_INPUTS, 3, _RAY_INPUTS, _full_or_static, _NO_SIGMA_BWD, True, 6)
+_POINTS = FieldKind(("pts", "viewdirs"), 2, ("pts", "viewdirs"), _full_or_static, _NO_SIGMA_BWD, False, 4)
+# (the generic backward on a supplied encoding has a STATIC mode -- a coarse network with test_time False --, the tuned instances do not)
+_ENC = FieldKind(("xyz_enc", "viewdirs"), 2, ("viewdirs",), lambda pk, mode: mode == L.FIELD_FULL or (mode == L.FIELD_STATIC and is_generic(pk)),
+                 "nefes_amd: field backward is built for the FULL (fine) mode only", False, 4)
+_HASHGRID = FieldKind(_RAY_INPUTS, 3, _RAY_INPUTS, lambda pk, mode: mode == L.FIELD_FULL, _NO_SIGMA_BWD, True, 7)
+_FH = FieldKind(_RAY_INPUTS, 3, _RAY_INPUTS, lambda pk, mode: True, None, True, 5)      # (launched by _fh_fwd / _fh_bwd)
+
+
+def _field_forward(ctx, kind, pk, mode, N, S, *tensors, grid=None, also_save=()):
+    """The forward of every frozen-field Function: `tensors` (kind.inputs, shaped as the launcher takes them) cast to fp32, one launch
+    -> raw_t.  The ReLU masks are written, and ctx keeps (kind.saved, raw_t, masks, *also_save), only where a backward can follow."""
+    x = {k: _f32(t) for k, t in zip(kind.inputs, tensors)}
+    need = kind.modes(pk, mode) and any(ctx.needs_input_grad[:kind.n_diff])
+    if kind is _FH:
+        raw_t, masks = _fh_fwd(pk, want_masks=need, **x)
+    else:
+        raw_t, masks = _field_fwd(pk, mode, N, S, want_masks=need, grid=grid, **x)
+    ctx.kind, ctx.pk, ctx.mode, ctx.NS, ctx.grid, ctx.have, ctx.pk_gen = kind, pk, mode, (N, S), grid, need, pk.generation
+    if need:
+        ctx.save_for_backward(*(x[k] for k in kind.saved), raw_t, masks, *also_save)
+    return raw_t
+
+
+def _field_backward(ctx, g_raw_t, g_gmap=None):
+    """The backward of every frozen-field Function -> one entry per argument of apply().  g_gmap: _fh_bwd's."""
+    kind, pk, (N, S) = ctx.kind, ctx.pk, ctx.NS
+    if not ctx.have:
+        if kind.refusal is None:
+            return (None,) * kind.n_args
+        raise NotImplementedError(kind.refusal)
+    saved, n = ctx.saved_tensors, len(kind.saved)
+    x, (raw_t, masks) = dict(zip(kind.saved, saved)), saved[n:n + 2]
+    pk.check_generation(ctx.pk_gen)
+    if kind is _FH:
+        g_in, g_vs = _fh_bwd(pk, raw_t=raw_t, g_raw_t=_f32(g_raw_t), g_gmap=g_gmap, masks=masks, **x)
+    else:
+        g_in, g_vs = _field_bwd(pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, grid=ctx.grid, enc=kind is _ENC, **x)
+    if kind.per_ray:
+        grads = ray_grad_reduce(N, S, x["z"], g_in, g_vs)
+    else:
+        zeros = torch.zeros(N, S, device=raw_t.device)
+        # (the reduction reads [N*S, 3] in g_pts' place and its g_o, g_d are dropped: an encoding's [N*S, 32] gradient does not go there)
+        grads = g_in.reshape(N, S, -1), ray_grad_reduce(N, S, zeros, g_vs if kind is _ENC else g_in, g_vs)[2]
+    return grads + (None,) * (kind.n_args - len(grads))
+
+
+class FieldFromRays(torch.autograd.Function):
+    """Fused pts = o + d*z -> embed -> MLP (rendering.py:142 + nerfh_nff.py:217-231, :525-576) on whichever kernels field_route names
+    for `pk` (a tuned or a generic pack).  Returns raw_t [N, R, S].  Differentiable w.r.t. rays_o, rays_d, viewdirs in FULL and
+    STATIC mode (frozen weights)."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, viewdirs, z, pk, mode):
+        return _field_forward(ctx, _RAYS, pk, mode, *z.shape, rays_o, rays_d, viewdirs, z)
+
+    backward = staticmethod(_field_backward)
+
+
+class FieldFromPoints(torch.autograd.Function):
+    """run_network_NeRFH_NFF call surface: explicit pts [N,S,3] (+ viewdirs [N,3]) -> raw_t [N,R,S], on a tuned or a generic pack."""
+
+    @staticmethod
+    def forward(ctx, pts, viewdirs, pk, mode):
+        N, S = pts.shape[0], pts.shape[1]
+        viewdirs = torch.zeros(N, 3, device=pts.device) if viewdirs is None else viewdirs
+        return _field_forward(ctx, _POINTS, pk, mode, N, S, pts.reshape(-1, 3), viewdirs)
+
+    backward = staticmethod(_field_backward)
+
+
+class FieldFromEncoding(torch.autograd.Function):
+    """Field MLP on a caller-supplied 32-feature xyz embedding (hash grid, BASELINE config 4): enc [N,S,32], viewdirs [N,3]
+    -> raw_t [N,R,S]; backward to enc and viewdirs: FULL mode on a tuned pack, FULL and STATIC on a generic one (packed_generic of a
+    network with in_channels_xyz=32: any width / depth)."""
+
+    @staticmethod
+    def forward(ctx, enc, viewdirs, pk, mode):
+        N, S = enc.shape[0], enc.shape[1]
+        viewdirs = torch.zeros(N, 3, device=enc.device) if viewdirs is None else viewdirs
+        return _field_forward(ctx, _ENC, pk, mode, N, S, enc.reshape(-1, 32), viewdirs)
+
+    backward = staticmethod(_field_backward)
+
+
+class FieldFromRaysHashGrid(torch.autograd.Function):
+    """pts = o + d z -> hash-grid encoding -> MLP in ONE launch each way (rendering.py:114,142 + nerfh_tcnn.py:151-182): raw_t [N, R, S];
+    differentiable w.r.t. rays_o, rays_d, viewdirs in FULL mode (frozen weights, frozen table).  Forward bit-identical to
+    HashGridEncode + FieldFromEncoding.  The caller asks hashgrid_fused_ok first (NEFES_FUSED_HASHGRID: "0" = those separate launches)."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, viewdirs, z, pk, mode, grid):
+        return _field_forward(ctx, _HASHGRID, pk, mode, *z.shape, rays_o, rays_d, viewdirs, z, grid=grid)
+
+    backward = staticmethod(_field_backward)
 
 
 class FieldFromRaysFH(torch.autograd.Function):
@@ -987,23 +1039,44 @@ class FieldFromRaysFH(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, viewdirs, z, pk):
-        rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
         if z.shape[0] * z.shape[1] >= H3_MAX_SAMPLES:
             raise RuntimeError("nefes_amd: too many samples for one launch of the fp16 two-part kernels (32-bit sample index)")
-        need = any(ctx.needs_input_grad[:3])
-        raw_t, masks = _fh_fwd(pk, rays_o, rays_d, viewdirs, z, need)
-        ctx.pk, ctx.have, ctx.pk_gen = pk, need, pk.generation
-        if need:
-            ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks)
-        return raw_t
+        return _field_forward(ctx, _FH, pk, L.FIELD_FULL, *z.shape, rays_o, rays_d, viewdirs, z)
+
+    backward = staticmethod(_field_backward)
+
+
+def _feat_head_fwd(gmap, w_t, b):
+    """feat [N, C] = gmap[:, :F] W^T + gmap[:, F:] b (csrc/refine.hip feat_head_fwd_kernel); w_t [F, C], the head's matrix transposed."""
+    N, C = gmap.shape[0], w_t.shape[1]
+    feat = torch.empty(N, C, device=gmap.device)
+    with _timed("feat_head_fwd"):
+        L.check(L.load().nefes_feat_head_fwd(N, C, gmap.shape[1] - 1, _chk(gmap, "gmap"), _chk(w_t, "w_t"), _chk(b, "b"), _chk(feat, "feat"), _stream()),
+                "nefes_feat_head_fwd")
+    return feat
+
+
+def _feat_head_bwd(g_feat, w, b):
+    """g_gmap [N, F + 1] of _feat_head_fwd (feat_head_bwd_kernel); w [C, F]."""
+    N, (C, F) = g_feat.shape[0], w.shape
+    g_gmap = torch.empty(N, F + 1, device=g_feat.device)
+    with _timed("feat_head_bwd"):
+        L.check(L.load().nefes_feat_head_bwd(N, C, F, _chk(g_feat, "g_feat"), _chk(w, "w"), _chk(b, "b"), _chk(g_gmap, "g_gmap"), _stream()),
+                "nefes_feat_head_bwd")
+    return g_gmap
+
+
+class FeatHead(torch.autograd.Function):
+    """The factored head's per-ray part: feat [N, C] = gmap[:, :F] W^T + gmap[:, F:] b (csrc/refine.hip feat_head_*_kernel; W, b frozen)."""
 
     @staticmethod
-    def backward(ctx, g_raw_t):
-        if not ctx.have:
-            return None, None, None, None, None
-        rays_o, rays_d, viewdirs, z, raw_t, masks = ctx.saved_tensors
-        ctx.pk.check_generation(ctx.pk_gen)
-        return _fh_bwd(ctx.pk, rays_o, rays_d, viewdirs, z, raw_t, _f32(g_raw_t), None, masks) + (None, None)
+    def forward(ctx, gmap, w, w_t, b):
+        ctx.save_for_backward(w, b)
+        return _feat_head_fwd(_f32(gmap), w_t, b)
+
+    @staticmethod
+    def backward(ctx, g_feat):
+        return _feat_head_bwd(_f32(g_feat), *ctx.saved_tensors), None, None, None
 
 
 class RenderFineFH(torch.autograd.Function):
@@ -1017,85 +1090,37 @@ class RenderFineFH(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, viewdirs, z, pk, w_f, w_f_t, b_f, flags, beta_min, emit_gmap=False, want_depth=False):
-        rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
-        N, S = z.shape
-        need = any(ctx.needs_input_grad[:3])
+        z = _f32(z)                   # (the compositor reads it too)
         Cg = pk.width // 2
-        raw_t, masks = _fh_fwd(pk, rays_o, rays_d, viewdirs, z, need)
+        raw_t = _field_forward(ctx, _FH, pk, L.FIELD_FULL, *z.shape, rays_o, rays_d, viewdirs, z, also_save=(w_f, b_f))
         rgb, gmap, disp, acc, depth, _, _ = composite_fwd(raw_t, z, Cg + 1, flags, beta_min)
-        if emit_gmap:
-            # the caller applies the feature head itself, folded into whatever linear layer consumes the features (the refinement loop:
-            # FusionNet's first convolution, FusionNet.forward_prepared_gmap): feat = [N, Cg + 1] = (sum_s w_s g_s, sum_s w_s)
-            feat = gmap
-        else:
-            C = w_f.shape[0]
-            feat = torch.empty(N, C, device=z.device)
-            with _timed("feat_head_fwd"):
-                L.check(L.load().nefes_feat_head_fwd(N, C, Cg, _chk(gmap, "gmap"), _chk(w_f_t, "w_t"), _chk(b_f, "b"), _chk(feat, "feat"), _stream()),
-                        "nefes_feat_head_fwd")
+        # emit_gmap: the caller applies the feature head itself, folded into whatever linear layer consumes the features (the refinement
+        # loop: FusionNet's first convolution, FusionNet.forward_prepared_gmap): feat = [N, Cg + 1] = (sum_s w_s g_s, sum_s w_s)
+        feat = gmap if emit_gmap else _feat_head_fwd(gmap, w_f_t, b_f)
         ctx.set_materialize_grads(False)
-        ctx.pk, ctx.have, ctx.pk_gen, ctx.cfg, ctx.emit_gmap = pk, need, pk.generation, (Cg, int(flags)), bool(emit_gmap)
-        if need:
-            ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks, w_f, b_f)
+        ctx.cfg, ctx.emit_gmap = (Cg, int(flags)), bool(emit_gmap)
         return (rgb, feat, disp, acc, depth) if want_depth else (rgb, feat, disp, acc)
 
     @staticmethod
     def backward(ctx, g_rgb, g_feat, g_disp, g_acc, g_depth=None):
         if not ctx.have:
             return (None,) * 12
-        rays_o, rays_d, viewdirs, z, raw_t, masks, w_f, b_f = ctx.saved_tensors
-        N, S = z.shape
-        pk = ctx.pk
-        pk.check_generation(ctx.pk_gen)
+        z, raw_t, _, w_f, b_f = ctx.saved_tensors[3:]      # (_field_forward's layout: _FH.saved = the four ray inputs, raw_t, masks, also_save)
+        N, S = ctx.NS
+        ctx.pk.check_generation(ctx.pk_gen)        # (before the head and the compositor are launched, not only before the field)
         Cg, flags = ctx.cfg
         fix = lambda g: None if (g is None or g.numel() == 0) else _f32(g)
         g_rgb, g_feat, g_disp, g_acc, g_depth = fix(g_rgb), fix(g_feat), fix(g_disp), fix(g_acc), fix(g_depth)
-        g_gmap = None
-        if g_feat is not None and ctx.emit_gmap:
-            g_gmap = g_feat                                  # already d loss / d (sum_s w_s g_s, sum_s w_s)
-        elif g_feat is not None:
-            g_gmap = torch.empty(N, Cg + 1, device=z.device)
-            with _timed("feat_head_bwd"):
-                L.check(L.load().nefes_feat_head_bwd(N, w_f.shape[0], Cg, _chk(g_feat, "g_feat"), _chk(w_f, "w"), _chk(b_f, "b"),
-                                                     _chk(g_gmap, "g_gmap"), _stream()), "nefes_feat_head_bwd")
-        else:
+        if g_feat is None:
             g_gmap = torch.zeros(N, Cg + 1, device=z.device)
+        else:                                                # (with emit_gmap it already is d loss / d (sum_s w_s g_s, sum_s w_s))
+            g_gmap = g_feat if ctx.emit_gmap else _feat_head_bwd(g_feat, w_f, b_f)
         g_raw_t = torch.empty_like(raw_t)          # (the g channels' rows beyond the first are neither written nor read)
         with _timed("composite_bwd"):
             L.check(L.load().nefes_composite_bwd(N, S, Cg + 1, flags | L.COMP_FEAT_WEIGHTS_ONLY, _chk(raw_t, "raw_t"), _chk(z, "z"),
                                                  _chk(g_rgb, "g_rgb"), None, _chk(g_disp, "g_disp"), _chk(g_acc, "g_acc"), _chk(g_depth, "g_depth"),
                                                  None, None, _chk(g_raw_t, "g_raw_t"), _stream()), "nefes_composite_bwd")
-        return _fh_bwd(pk, rays_o, rays_d, viewdirs, z, raw_t, g_raw_t, g_gmap, masks) + (None,) * 9
-
-
-class FieldFromPoints(torch.autograd.Function):
-    """run_network_NeRFH_NFF call surface: explicit pts [N,S,3] (+ viewdirs [N,3]) -> raw_t [N,R,S], on a tuned or a generic pack."""
-
-    @staticmethod
-    def forward(ctx, pts, viewdirs, pk, mode):
-        pts = _f32(pts)
-        N, S = pts.shape[0], pts.shape[1]
-        if viewdirs is None:
-            viewdirs = torch.zeros(N, 3, device=pts.device)
-        viewdirs = _f32(viewdirs)
-        need = mode in (L.FIELD_FULL, L.FIELD_STATIC) and any(ctx.needs_input_grad[:2])
-        raw_t, masks = _field_fwd(pk, mode, N, S, pts=pts.reshape(-1, 3), viewdirs=viewdirs, want_masks=need)
-        ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
-        if need:
-            ctx.save_for_backward(pts, viewdirs, raw_t, masks)
-        return raw_t
-
-    @staticmethod
-    def backward(ctx, g_raw_t):
-        if not ctx.have:
-            raise NotImplementedError(_NO_SIGMA_BWD)
-        pts, viewdirs, raw_t, masks = ctx.saved_tensors
-        N, S = pts.shape[0], pts.shape[1]
-        ctx.pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = _field_bwd(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, pts=pts.reshape(-1, 3), viewdirs=viewdirs)
-        zeros = torch.zeros(N, S, device=pts.device)
-        _, _, g_v = ray_grad_reduce(N, S, zeros, g_pts, g_vs)
-        return g_pts.reshape(N, S, 3), g_v, None, None
+        return _field_backward(ctx, g_raw_t, g_gmap) + (None,) * 7
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1195,38 +1220,6 @@ def field_from_rays(rays_o, rays_d, viewdirs, z, pk, mode):
 
 def field_from_points(pts, viewdirs, pk, mode):
     return FieldFromPoints.apply(pts, viewdirs, pk, mode)
-
-
-class FieldFromEncoding(torch.autograd.Function):
-    """Field MLP on a caller-supplied 32-feature xyz embedding (hash grid, BASELINE config 4): enc [N,S,32], viewdirs [N,3]
-    -> raw_t [N,R,S]; backward to enc and viewdirs: FULL mode on a tuned pack, FULL and STATIC on a generic one (packed_generic of a
-    network with in_channels_xyz=32: any width / depth)."""
-
-    @staticmethod
-    def forward(ctx, enc, viewdirs, pk, mode):
-        enc = _f32(enc)
-        N, S = enc.shape[0], enc.shape[1]
-        viewdirs = torch.zeros(N, 3, device=enc.device) if viewdirs is None else _f32(viewdirs)
-        # (the generic backward has a STATIC mode -- a coarse network with test_time False --, the tuned instances on an encoding do not)
-        need = (mode == L.FIELD_FULL or (mode == L.FIELD_STATIC and is_generic(pk))) and any(ctx.needs_input_grad[:2])
-        raw_t, masks = _field_fwd(pk, mode, N, S, xyz_enc=enc.reshape(-1, 32), viewdirs=viewdirs, want_masks=need)
-        ctx.pk, ctx.mode, ctx.have, ctx.pk_gen = pk, mode, need, pk.generation
-        if need:
-            ctx.save_for_backward(viewdirs, raw_t, masks)
-            ctx.shape = (N, S)
-        return raw_t
-
-    @staticmethod
-    def backward(ctx, g_raw_t):
-        if not ctx.have:
-            raise NotImplementedError("nefes_amd: field backward is built for the FULL (fine) mode only")
-        viewdirs, raw_t, masks = ctx.saved_tensors
-        N, S = ctx.shape
-        ctx.pk.check_generation(ctx.pk_gen)
-        g_enc, g_vs = _field_bwd(ctx.pk, ctx.mode, N, S, raw_t, _f32(g_raw_t), masks, viewdirs=viewdirs, enc=True)
-        zeros = torch.zeros(N, S, device=raw_t.device)
-        _, _, g_v = ray_grad_reduce(N, S, zeros, g_vs, g_vs)
-        return g_enc.reshape(N, S, 32), g_v, None, None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1358,35 +1351,6 @@ class HashGrid:
         return torch.is_grad_enabled() and self.table.requires_grad
 
 
-class FieldFromRaysHashGrid(torch.autograd.Function):
-    """pts = o + d z -> hash-grid encoding -> MLP in ONE launch each way (rendering.py:114,142 + nerfh_tcnn.py:151-182): raw_t [N, R, S];
-    differentiable w.r.t. rays_o, rays_d, viewdirs in FULL mode (frozen weights, frozen table).  Forward bit-identical to
-    HashGridEncode + FieldFromEncoding.  The caller asks hashgrid_fused_ok first (NEFES_FUSED_HASHGRID: "0" = those separate launches)."""
-
-    @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, z, pk, mode, grid):
-        rays_o, rays_d, viewdirs, z = _f32(rays_o), _f32(rays_d), _f32(viewdirs), _f32(z)
-        N, S = z.shape
-        need = mode == L.FIELD_FULL and any(ctx.needs_input_grad[:3])
-        raw_t, masks = _field_fwd(pk, mode, N, S, rays_o=rays_o, rays_d=rays_d, z=z, viewdirs=viewdirs, want_masks=need, grid=grid)
-        ctx.pk, ctx.grid, ctx.have, ctx.pk_gen = pk, grid, need, pk.generation
-        if need:
-            ctx.save_for_backward(rays_o, rays_d, viewdirs, z, raw_t, masks)
-        return raw_t
-
-    @staticmethod
-    def backward(ctx, g_raw_t):
-        if not ctx.have:
-            raise NotImplementedError(_NO_SIGMA_BWD)
-        rays_o, rays_d, viewdirs, z, raw_t, masks = ctx.saved_tensors
-        N, S = z.shape
-        ctx.pk.check_generation(ctx.pk_gen)
-        g_pts, g_vs = _field_bwd(ctx.pk, L.FIELD_FULL, N, S, raw_t, _f32(g_raw_t), masks, rays_o=rays_o, rays_d=rays_d, z=z,
-                                 viewdirs=viewdirs, grid=ctx.grid)
-        g_o, g_d, g_v = ray_grad_reduce(N, S, z, g_pts, g_vs)
-        return g_o, g_d, g_v, None, None, None, None
-
-
 def hashgrid_bwd_table(grid, x, g_enc, g_table=None):
     """g_table [entries, 2] (+)= d loss / d table for enc = grid(x), x [M, 3], g_enc [M, 32] (atomics: reproducible to rounding, not
     bitwise; the dense levels are summed in fp64 and rounded once).  g_table=None: a fresh zeroed buffer; otherwise the call adds into
@@ -1466,37 +1430,6 @@ def _conv2d_same(x, wp, cout, ksize, bias, relu, mask=None):
     return y
 
 
-class FrozenConv2d(torch.autograd.Function):
-    """Conv2d(stride 1, "same" zero padding, 3x3 or 5x5) [+ ReLU] with FROZEN weight and bias, differentiable w.r.t. its input:
-    FusionNet's layers in the refinement loop (nerfh_nff.py:356-418; weights carry no gradient there).  Forward and the input
-    gradient are the same implicit-GEMM kernel (csrc/conv.hip); the ReLU derivative is applied to the incoming gradient inside
-    the gradient launch (mask = this layer's output)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, relu):
-        xc = _f32(x)
-        k = weight.shape[-1]
-        y = _conv2d_same(xc, _pack_conv(weight, False), weight.shape[0], k, None if bias is None else _f32(bias.detach()), relu)
-        ctx.weight, ctx.relu = weight, relu
-        if relu:
-            ctx.save_for_backward(y)
-            _tap("conv_relu", y)             # tests: the ReLU branch pattern of this layer (y > 0), tests/branch.py's rule for FusionNet
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        w = ctx.weight
-        y = ctx.saved_tensors[0] if ctx.relu else None
-        gx = _conv2d_same(_f32(g), _pack_conv(w, True), w.shape[1], w.shape[-1], None, False, mask=y)
-        return gx, None, None, None
-
-
-def frozen_conv2d(x, weight, bias, relu=False):
-    if weight.requires_grad or (bias is not None and bias.requires_grad):
-        raise ValueError("nefes_amd: frozen_conv2d is for weights without gradient (use torch's conv2d to train them)")
-    return FrozenConv2d.apply(x, weight, bias, relu)
-
-
 def _conv2d_wgrad(x, gy, mask, cout, ksize, want_bias):
     """(g_w [cout, cin, k, k], g_bias [cout] or None) of nefes_conv2d_wgrad; mask: the layer's output after ReLU, or None."""
     B, cin, H, W = x.shape
@@ -1513,41 +1446,54 @@ def _conv2d_wgrad(x, gy, mask, cout, ksize, want_bias):
     return g_w, g_b
 
 
-class TrainConv2d(torch.autograd.Function):
-    """FrozenConv2d with TRAINABLE weight and bias (FusionNet in the reference's third training stage): the same forward and input
-    gradient launches, and the weight / bias gradients through nefes_conv2d_wgrad (csrc/conv.hip: fp32 MFMA, partial sums per pixel
-    chunk added in a fixed order -- no atomics, bit-identical from call to call).  The ReLU derivative comes from the saved output."""
+class Conv2dSame(torch.autograd.Function):
+    """Conv2d(stride 1, "same" zero padding, 3x3 or 5x5) [+ ReLU], differentiable w.r.t. its input and -- where they require it -- its
+    weight and bias.  Forward and the input gradient are the same implicit-GEMM kernel (csrc/conv.hip); the ReLU derivative is applied
+    to the incoming gradient inside the gradient launches (mask = this layer's saved output).
+    FROZEN weight and bias (FusionNet's layers in the refinement loop, nerfh_nff.py:356-418): nothing else is saved or launched.
+    TRAINABLE ones (FusionNet in the reference's third training stage): the input is saved too, and their gradients come from
+    nefes_conv2d_wgrad (fp32 MFMA, partial sums per pixel chunk added in a fixed order -- no atomics, bit-identical from call to call)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu):
         xc = _f32(x)
-        k = weight.shape[-1]
-        y = _conv2d_same(xc, _pack_conv(weight, False), weight.shape[0], k, None if bias is None else _f32(bias), relu)
-        ctx.weight, ctx.relu, ctx.has_bias = weight, relu, bias is not None
-        ctx.save_for_backward(xc, *([y] if relu else []))
+        y = _conv2d_same(xc, _pack_conv(weight, False), weight.shape[0], weight.shape[-1], None if bias is None else _f32(bias), relu)
+        ctx.weight, ctx.relu, ctx.trains = weight, relu, any(ctx.needs_input_grad[1:3])
+        ctx.save_for_backward(*([xc] if ctx.trains else []), *([y] if relu else []))
         if relu:
-            _tap("conv_relu", y)
+            _tap("conv_relu", y)             # tests: the ReLU branch pattern of this layer (y > 0), tests/branch.py's rule for FusionNet
         return y
 
     @staticmethod
     def backward(ctx, g):
-        w = ctx.weight
-        xc = ctx.saved_tensors[0]
-        y = ctx.saved_tensors[1] if ctx.relu else None
-        gf = _f32(g)
+        w, gf = ctx.weight, _f32(g)
+        y = ctx.saved_tensors[-1] if ctx.relu else None
         gx = g_w = g_b = None
         if ctx.needs_input_grad[0]:
             gx = _conv2d_same(gf, _pack_conv(w, True), w.shape[1], w.shape[-1], None, False, mask=y)
-        want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or want_b:
-            g_w, g_b = _conv2d_wgrad(xc, gf, y, w.shape[0], w.shape[-1], want_b)
+        if ctx.trains:
+            g_w, g_b = _conv2d_wgrad(ctx.saved_tensors[0], gf, y, w.shape[0], w.shape[-1], ctx.needs_input_grad[2])
             if not ctx.needs_input_grad[1]:
                 g_w = None
         return gx, g_w, g_b, None
 
 
+class FrozenConv2d(Conv2dSame):
+    """Conv2dSame under the name its node has in the graphs of the refinement loop (FrozenConv2dBackward): what frozen_conv2d applies."""
+
+
+class TrainConv2d(Conv2dSame):
+    """Conv2dSame under the name its node has in the graph of a FusionNet that trains (TrainConv2dBackward): what conv2d_same_train applies."""
+
+
+def frozen_conv2d(x, weight, bias, relu=False):
+    if weight.requires_grad or (bias is not None and bias.requires_grad):
+        raise ValueError("nefes_amd: frozen_conv2d is for weights without gradient (use torch's conv2d to train them)")
+    return FrozenConv2d.apply(x, weight, bias, relu)
+
+
 def conv2d_same_train(x, weight, bias, relu=False):
-    """Conv2d(stride 1, "same" zero padding, 3x3 or 5x5) [+ ReLU], differentiable w.r.t. input, weight and bias (TrainConv2d)."""
+    """Conv2d(stride 1, "same" zero padding, 3x3 or 5x5) [+ ReLU], differentiable w.r.t. input, weight and bias (Conv2dSame)."""
     return TrainConv2d.apply(x, weight, bias, relu)
 
 
@@ -1625,6 +1571,28 @@ def pose_compose(r, t, init_c2w, pose_scale=1.0, move=(0., 0., 0.), pose_scale2=
     return out[0] if r.dim() == 1 else out
 
 
+def _bn_train_fwd(xf, w, b, bn, per_image, track_stats):
+    """The forward launch of both BatchNorm Functions on xf [B,C,H,W] with the affine parameters w, b (or None) -> (y, save: the float64
+    statistics the backward reads, one set per image with per_image).  Updates bn's running statistics and batch counter as the
+    module does, unless track_stats is off or the statistics are every image's own."""
+    B, Cc = xf.shape[0], xf.shape[1]
+    y = torch.empty_like(xf)
+    groups = B if per_image else 1
+    save = torch.empty(groups * Cc * 2, dtype=torch.float64, device=xf.device)
+    track = bool(track_stats) and (not per_image) and bn.track_running_stats and bn.running_mean is not None
+    momentum = 0.1
+    if track:
+        if bn.momentum is None:
+            raise NotImplementedError("nefes_amd: BatchNorm with momentum=None (cumulative average) takes the torch module")
+        momentum = float(bn.momentum)
+    L.check(L.load().nefes_bn_train_fwd(B, Cc, xf.numel() // (B * Cc), 1 if per_image else 0, _chk(xf, "x"), _chk(w, "weight"), _chk(b, "bias"),
+                                        float(bn.eps), momentum,
+                                        _chk(bn.running_mean, "running_mean") if track else None, _chk(bn.running_var, "running_var") if track else None,
+                                        _chk(bn.num_batches_tracked, "num_batches_tracked", torch.int64) if track and bn.num_batches_tracked is not None else None,
+                                        _chk(y, "y"), _chk(save, "save", torch.float64), _stream()), "nefes_bn_train_fwd")
+    return y, save
+
+
 class BatchNormTrainFrozen(torch.autograd.Function):
     """torch.nn.BatchNorm2d in TRAIN mode with frozen affine parameters on [B,C,H,W] (FusionNet's last layer in the refinement loop,
     nerfh_nff.py:356-418): output normalised by the batch's statistics (running statistics and the batch counter updated as the module
@@ -1634,23 +1602,9 @@ class BatchNormTrainFrozen(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bn, per_image, track_stats=True):
         xf = _f32(x)
-        B, Cc = xf.shape[0], xf.shape[1]
-        P = xf.numel() // (B * Cc)
-        y = torch.empty_like(xf)
-        groups = B if per_image else 1
-        save = torch.empty(groups * Cc * 2, dtype=torch.float64, device=xf.device)
         w = None if bn.weight is None else _f32(bn.weight)
         b = None if bn.bias is None else _f32(bn.bias)
-        track = bool(track_stats) and (not per_image) and bn.track_running_stats and bn.running_mean is not None
-        momentum = 0.1
-        if track:
-            if bn.momentum is None:
-                raise NotImplementedError("nefes_amd: BatchNorm with momentum=None (cumulative average) takes the torch module")
-            momentum = float(bn.momentum)
-        L.check(L.load().nefes_bn_train_fwd(B, Cc, P, 1 if per_image else 0, _chk(xf, "x"), _chk(w, "weight"), _chk(b, "bias"), float(bn.eps), momentum,
-                                            _chk(bn.running_mean, "running_mean") if track else None, _chk(bn.running_var, "running_var") if track else None,
-                                            _chk(bn.num_batches_tracked, "num_batches_tracked", torch.int64) if track and bn.num_batches_tracked is not None else None,
-                                            _chk(y, "y"), _chk(save, "save", torch.float64), _stream()), "nefes_bn_train_fwd")
+        y, save = _bn_train_fwd(xf, w, b, bn, per_image, track_stats)
         ctx.save_for_backward(xf, save)
         ctx.w, ctx.per_image = w, bool(per_image)
         return y
@@ -1683,22 +1637,8 @@ class BatchNormTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, bn, track_stats):
-        xf = _f32(x)
-        B, Cc = xf.shape[0], xf.shape[1]
-        P = xf.numel() // (B * Cc)
-        y = torch.empty_like(xf)
-        save = torch.empty(Cc * 2, dtype=torch.float64, device=xf.device)
-        w, b = _f32(weight), _f32(bias)
-        track = bool(track_stats) and bn.track_running_stats and bn.running_mean is not None
-        momentum = 0.1
-        if track:
-            if bn.momentum is None:
-                raise NotImplementedError("nefes_amd: BatchNorm with momentum=None (cumulative average) takes the torch module")
-            momentum = float(bn.momentum)
-        L.check(L.load().nefes_bn_train_fwd(B, Cc, P, 0, _chk(xf, "x"), _chk(w, "weight"), _chk(b, "bias"), float(bn.eps), momentum,
-                                            _chk(bn.running_mean, "running_mean") if track else None, _chk(bn.running_var, "running_var") if track else None,
-                                            _chk(bn.num_batches_tracked, "num_batches_tracked", torch.int64) if track and bn.num_batches_tracked is not None else None,
-                                            _chk(y, "y"), _chk(save, "save", torch.float64), _stream()), "nefes_bn_train_fwd")
+        xf, w = _f32(x), _f32(weight)
+        y, save = _bn_train_fwd(xf, w, _f32(bias), bn, False, track_stats)
         ctx.save_for_backward(xf, save, w)
         return y
 

@@ -140,7 +140,7 @@ def launch_bwd(case, pk, x, N, S, raw_t, G, masks, keys=None):
     v = _dev(x["v"])
     ops.TIMERS = {}
     try:
-        if case.kind == "fh":       # ops._fh_bwd reduces over each ray's samples: the entry point itself, for the per-sample gradients
+        if case.kind == "fh":       # the entry point itself (what ops._fh_bwd launches), for the per-sample gradients
             g_in, g_vs = torch.empty(N * S, 3, device=DEV), torch.empty(N * S, 3, device=DEV)
             ptr, o, d, z = ops._chk, _dev(x["o"]), _dev(x["d"]), _dev(x["z"])          # (named: they must outlive the launch)
             with ops._timed("field_bwd[h3,fh]"):
